@@ -12,7 +12,17 @@ projection, at 256 pairs per GPU (BASELINE.json metric: "two-view frames/sec at 
 by --precision (default f16: fp16 storage; `dtype` of the line).  Pairs are independent units: every rank owns its own 256 pairs,
 no data-path collective (weak scaling).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+A plain run sets up, warms up (W steps), times the K steps and prints ONE JSON line on rank 0: metric, value (pairs/s over the K
+timed steps, all GPUs), unit, higher_is_better, dtype, ms_per_step (wall time of one timed step) and the configuration.  The timed
+steps carry no instrumentation.
+
+  --dump-outputs DIR   after the timed steps, what the last of them returned (the output dict of the timed path) as
+                       DIR/<name>.npy in float32; an output above 4 MiB keeps a fixed, seeded sample of its rows.  Weights and
+                       inputs are seeded: the same arguments give the same inputs in every run, so two builds compare output for output.
+  --full               everything below as well, after the headline's steps (the timed steps then carry the conv-stack HIP events
+                       the roofline needs).  The options of the "secondary measurements" group act only here.
+
+With --full the line holds these extra objects:
   roofline      SURVEY 8(d): pairs/s x 16.3916 GFLOP per pair against the dense bf16 / fp16 MFMA peak (whole step time); the conv
                 stack alone (its launch count read back from the library, HIP events on the streams that run it) beside it;
                 `traffic` = HBM bytes per STEP from the latest committed PMC pass
@@ -26,6 +36,8 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with extra objec
                 precision="auto" picks for it
   view_split    (N >= 2 ranks) BASELINE config 4: one view per rank, the 136-float partner state exchanged over
                 RCCL pair groups before IEF iterations 2 and 3, hidden behind the partner-independent half of the step
+  and stage_ms_per_step, smplx_tail_roofline, smplx_blend_roofline, parity_of_timed_mode, f16_range_check, b64, airpose_plus and
+  stream_ordered (or overlap_tail): see the code that fills them.
 Every `frac` recomputes from `stage_ms_per_step` and the byte / FLOP constants stated next to it.
 """
 import argparse
@@ -42,6 +54,7 @@ MEAN = os.path.join(REPO, "airpose_amd", "data", "smpl_mean_params.npz")
 PEAK_BF16_DENSE_TFLOPS = 2500.0      # MI355X_MICROARCH.md: ~2.5 PF dense bf16 MFMA
 PEAK_FP32_TFLOPS = 157.3
 PEAK_HBM_GBS = 8000.0
+DUMP_ARRAY_BYTES = 4 << 20           # --dump-outputs: larger outputs keep a seeded sample of their rows (<= 14 outputs: < 64 MB in all)
 
 
 def conv_stack_flops_per_image():
@@ -466,6 +479,31 @@ def view_split_block(args, net, batch, dev, rank, world):
                 dist.get_backend(), " (= RCCL over xGMI)" if dist.get_backend() == "nccl" else " (host-staged: test aid)")}
 
 
+def step_outputs(out):
+    """What a caller of the timed path receives from one step, as name -> tensor: the output dict of TwoViewInference.__call__ /
+    submit (a Pending is waited for first, with the range check it carries), or the four tensors of the network-only forms."""
+    from airpose_amd import pipeline
+    if isinstance(out, pipeline.Pending):
+        out = out.synchronize()
+    if isinstance(out, dict):
+        return dict(out.items())
+    return dict(zip(("pred_pose0", "pred_betas0", "pred_pose1", "pred_betas1"), out))
+
+
+def dump_outputs(outs, d, seed=0):
+    """outs -> d/<name>.npy in float32 (float64 stays float64).  An output above DUMP_ARRAY_BYTES keeps a fixed, seeded sample of its
+    rows (axis 0, sorted; the same rows for every output of that length): pred_vertices_cam* (256 x 10475 x 3) -> 33 bodies."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    for name, t in sorted(outs.items()):
+        a = (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()
+        if a.nbytes > DUMP_ARRAY_BYTES and a.ndim:
+            k = max(1, DUMP_ARRAY_BYTES // (a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(seed).choice(a.shape[0], k, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
+
+
 def self_launch(argv, n):
     """`python bench.py --gpus N` without a launcher's environment: become `python -m torch.distributed.run --standalone`-style
     (explicit 127.0.0.1 rendezvous on a free port: the container hostname may not resolve) with N ranks of this script."""
@@ -490,23 +528,31 @@ def main():
     ap.add_argument("--precision", default="f16", choices=["f16", "bf16", "bf16x2", "fp32"],
                     help="f16 (default) / bf16: the throughput kernels with fp16 / bf16 storage; bf16x2, fp32: the parity-grade modes")
     ap.add_argument("--chunk", type=int, default=0, help="images per depth-first trunk chunk (0 = default)")
-    ap.add_argument("--cpu-sample", type=int, default=16, help="pairs in the CPU baseline sample (0 = skip)")
     ap.add_argument("--no-tail", action="store_true", help="time the network only (BASELINE config 2 shape)")
-    ap.add_argument("--stage-steps", type=int, default=5, help="extra untimed steps with per-stage HIP events")
     ap.add_argument("--force-dist", action="store_true", help="initialise the RCCL process group even with one rank (test aid)")
     ap.add_argument("--dual-stream", type=int, default=1, help="two-view trunk as two concurrent passes (default) or one pass (0)")
-    ap.add_argument("--repeat-blocks", type=int, default=6, help="extra blocks after the contract's K-step one (spread; GPU busy >= 3 s)")
-    ap.add_argument("--repeat-steps", type=int, default=100, help="steps of each extra block")
-    ap.add_argument("--parity-sweep", type=int, default=1, help="every mode vs the CPU oracle over 3 weight seeds x 2 input seeds + a second BN range (0 = skip)")
-    ap.add_argument("--airpose-plus", type=int, default=1, help="BASELINE config 4: 300-iteration fit of 64 frames (0 = skip)")
-    ap.add_argument("--parity-steps", type=int, default=3, help="steps of the parity-grade mode after the main loop (0 = skip)")
-    ap.add_argument("--parity-pairs", type=int, default=128, help="pairs (two input seeds) on which the TIMED mode is checked against the CPU oracle (0 = skip)")
     ap.add_argument("--overlap-tail", type=int, default=1,
                     help="1 (default): steps issued through TwoViewInference.submit (serving form: the passes of step i+1 queue behind "
                          "those of step i, IEF loop + SMPL-X stage of step i on a second stream under them); 0: the stream-ordered "
-                         "forward.  The other form is timed for one more block and reported beside the headline")
-    ap.add_argument("--other-form", type=int, default=1, help="0: skip the extra block that times the other step-issue form (profiling runs)")
-    ap.add_argument("--b64", type=int, default=1, help="also time BASELINE config 1 (batch 64, network only, bf16 and f16): 0 = skip")
+                         "forward.  With --full the other form is timed for one more block and reported beside the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned as DIR/<name>.npy (float32 / float64; a fixed "
+                         "seeded sample of the rows of every output above %d MiB)" % (DUMP_ARRAY_BYTES >> 20))
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement and check after the headline's steps: conv-stack HIP events in the "
+                         "timed steps, roofline and per-stage figures, repeat blocks, the other step-issue form, the fp16 range check, "
+                         "CPU baseline, parity against the CPU oracle, the other precisions, batch 64, AirPose+ fitting, view split")
+    fl = ap.add_argument_group("secondary measurements (with --full only)")
+    fl.add_argument("--cpu-sample", type=int, default=16, help="pairs in the CPU baseline sample (0 = skip)")
+    fl.add_argument("--stage-steps", type=int, default=5, help="extra untimed steps with per-stage HIP events")
+    fl.add_argument("--repeat-blocks", type=int, default=6, help="extra blocks after the contract's K-step one (spread; GPU busy >= 3 s)")
+    fl.add_argument("--repeat-steps", type=int, default=100, help="steps of each extra block")
+    fl.add_argument("--parity-sweep", type=int, default=1, help="every mode vs the CPU oracle over 3 weight seeds x 2 input seeds + a second BN range (0 = skip)")
+    fl.add_argument("--airpose-plus", type=int, default=1, help="BASELINE config 4: 300-iteration fit of 64 frames (0 = skip)")
+    fl.add_argument("--parity-steps", type=int, default=3, help="steps of the parity-grade mode after the main loop (0 = skip)")
+    fl.add_argument("--parity-pairs", type=int, default=128, help="pairs (two input seeds) on which the TIMED mode is checked against the CPU oracle (0 = skip)")
+    fl.add_argument("--other-form", type=int, default=1, help="0: skip the extra block that times the other step-issue form (profiling runs)")
+    fl.add_argument("--b64", type=int, default=1, help="also time BASELINE config 1 (batch 64, network only, bf16 and f16): 0 = skip")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:     # the plain command: launch the N ranks ourselves (never returns)
         self_launch(sys.argv[1:], args.gpus)
@@ -624,10 +670,11 @@ def main():
     for _ in range(max(args.warmup, 1)):
         out = step()
     torch.cuda.synchronize()
-    # Timed region: only the conv stack carries HIP events (the roofline line needs that pair; every event record costs
-    # a ~5 us bubble on the stream).  The per-stage breakdown comes from extra, untimed steps below.
-    net.enable_timing(2)
-    net.timing(reset=True)
+    # Timed region.  --full: the conv stack carries HIP events (the roofline line needs that pair; every event record costs
+    # a ~5 us bubble on the stream), the per-stage breakdown comes from extra, untimed steps below.  A plain run: no events.
+    if args.full:
+        net.enable_timing(2)
+        net.timing(reset=True)
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -638,133 +685,118 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    tm = net.timing(reset=True)
-    launches_timed = net.last_conv_launches()                # conv-stack launches of the last timed step, all passes (ap_net_last_conv_launches)
-    # the same block again, a few times: spread of the headline inside one process (the contract's `value` stays the
-    # first block; the timed region of 20 steps is only ~0.14 s)
-    blocks = [world * B * args.steps / elapsed]
-    rsteps = max(args.repeat_steps, 1)
-    for _ in range(max(args.repeat_blocks, 0)):
-        fence()
-        t1 = time.perf_counter()
-        for _ in range(rsteps):
-            out = step()
-        fence()
-        dt = time.perf_counter() - t1
-        if use_dist:
-            t = torch.tensor([dt], device=dev, dtype=torch.float64)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            dt = float(t.item())
-        blocks.append(world * B * rsteps / dt)
-    # the other form of the same forward, one more block of K steps: stream-ordered __call__ when the headline is the serving form
-    # (TwoViewInference.submit) and the other way round -- same kernels, bit-identical outputs
-    other = None
-    if not args.no_tail and args.other_form:
-        other_step = (lambda: pipe(batch, want_rotmat=True)) if args.overlap_tail else (lambda: pipe.submit(batch, want_rotmat=True))
-        for _ in range(2):
-            pend = other_step()
-        fence()
+    if args.dump_outputs and rank == 0:                      # before anything else reuses the buffers the last step wrote
+        dump_outputs(step_outputs(out), args.dump_outputs)
+    if args.full:
+        tm = net.timing(reset=True)
+        launches_timed = net.last_conv_launches()            # conv-stack launches of the last timed step, all passes (ap_net_last_conv_launches)
+        # the same block again, a few times: spread of the headline inside one process (the contract's `value` stays the
+        # first block; the timed region of 20 steps is only ~0.14 s)
+        blocks = [world * B * args.steps / elapsed]
+        rsteps = max(args.repeat_steps, 1)
+        for _ in range(max(args.repeat_blocks, 0)):
+            fence()
+            t1 = time.perf_counter()
+            for _ in range(rsteps):
+                out = step()
+            fence()
+            dt = time.perf_counter() - t1
+            if use_dist:
+                t = torch.tensor([dt], device=dev, dtype=torch.float64)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                dt = float(t.item())
+            blocks.append(world * B * rsteps / dt)
+        # the other form of the same forward, one more block of K steps: stream-ordered __call__ when the headline is the serving form
+        # (TwoViewInference.submit) and the other way round -- same kernels, bit-identical outputs
+        other = None
+        if not args.no_tail and args.other_form:
+            other_step = (lambda: pipe(batch, want_rotmat=True)) if args.overlap_tail else (lambda: pipe.submit(batch, want_rotmat=True))
+            for _ in range(2):
+                pend = other_step()
+            fence()
+            net.timing(reset=True)
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                pend = other_step()
+            fence()
+            dt = time.perf_counter() - t1
+            tm_other = net.timing(reset=True)
+            del pend
+            if use_dist:
+                t = torch.tensor([dt], device=dev, dtype=torch.float64)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                dt = float(t.item())
+            other = {"pairs_per_s": world * B * args.steps / dt, "ms_per_step": 1e3 * dt / args.steps,
+                     "conv_stack_ms": tm_other["conv_ms"] / max(tm_other["passes"], 1),
+                     "what": ("TwoViewInference.__call__: every step complete in the order of the caller's stream before the next one "
+                              "starts (the reference boundary's semantics)") if args.overlap_tail else
+                             ("TwoViewInference.submit: the passes of step i+1 queue behind those of step i, IEF loop + SMPL-X stage "
+                              "of step i on a second stream under them; outputs ready at Pending.wait")}
         net.timing(reset=True)
-        t1 = time.perf_counter()
-        for _ in range(args.steps):
-            pend = other_step()
-        fence()
-        dt = time.perf_counter() - t1
-        tm_other = net.timing(reset=True)
-        del pend
-        if use_dist:
-            t = torch.tensor([dt], device=dev, dtype=torch.float64)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            dt = float(t.item())
-        other = {"pairs_per_s": world * B * args.steps / dt, "ms_per_step": 1e3 * dt / args.steps,
-                 "conv_stack_ms": tm_other["conv_ms"] / max(tm_other["passes"], 1),
-                 "what": ("TwoViewInference.__call__: every step complete in the order of the caller's stream before the next one "
-                          "starts (the reference boundary's semantics)") if args.overlap_tail else
-                         ("TwoViewInference.submit: the passes of step i+1 queue behind those of step i, IEF loop + SMPL-X stage "
-                          "of step i on a second stream under them; outputs ready at Pending.wait")}
-    net.timing(reset=True)
-    # stage breakdown: a few more steps, fully instrumented, outside the timed region
-    net.enable_timing(1)
-    instrumented[0] = True
-    if not args.no_tail:
-        body.enable_timing(True)
-        body.timing(reset=True)
-    for _ in range(args.stage_steps):
-        out = step()
-    torch.cuda.synchronize()
-    ts = net.timing(reset=True)
-    tb = body.timing(reset=True) if not args.no_tail else None
-    # the tail once more as ONE span (an event in front of its first kernel and one behind its last): every event record between two
-    # kernels costs a bubble of several microseconds on the stream, three of them sit inside the per-stage sum above
-    tail_span_ms = None
-    if not args.no_tail and args.stage_steps > 0:
-        body.enable_timing(2)
-        body.timing(reset=True)
+        # stage breakdown: a few more steps, fully instrumented, outside the timed region
+        net.enable_timing(1)
+        instrumented[0] = True
+        if not args.no_tail:
+            body.enable_timing(True)
+            body.timing(reset=True)
         for _ in range(args.stage_steps):
             out = step()
         torch.cuda.synchronize()
-        t2 = body.timing(reset=True)
-        tail_span_ms = t2["prep_ms"] / max(t2["passes"], 1)
-        body.enable_timing(False)
-    net.enable_timing(0)
-    del out
-    # fp16 storage: the range sentinel (deferred mode: nothing on the hot path) must be silent after everything timed above
-    range_ok = None
-    if args.precision == "f16":
-        net.range_status()                                   # raises airpose_amd._native.RangeError if any pass left the fp16 range
-        range_ok = True
-    cpu, sample, want = (None, None, None)
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
-        cpu, sample, want = cpu_baseline(sd, md, args.cpu_sample)
-    parity = parity_block(args, sd, body, batch, net, sample, want, dev) if (rank == 0 and world == 1 and not args.no_tail) else None
-    timed_parity = None
-    if rank == 0 and world == 1 and not args.no_tail and cpu is not None and args.parity_pairs > 0:
-        timed_parity = timed_mode_parity(sd, md, pipe, dev, cpu["cores"], pairs_per_seed=max(1, args.parity_pairs // 2),
-                                         submit=bool(args.overlap_tail))
-    b64 = None
-    if rank == 0 and world == 1 and args.b64 and args.precision in ("bf16", "f16") and B != 64:
-        b64 = b64_block(args, sd, body, dev)
-    sweep = None
-    if rank == 0 and world == 1 and not args.no_tail and cpu is not None and args.parity_sweep:
-        sweep = parity_sweep(args, md, body, dev, cpu["cores"])
-    fitres = None
-    if rank == 0 and world == 1 and args.airpose_plus and not args.no_tail:
-        try:
-            fitres = airpose_plus_block(md, dev)
-        except Exception as e:                               # noqa: BLE001 (reported, not swallowed)
-            fitres = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
-    # the secondary measurement must never cost the primary one: an exception in the view-split block (it needs the pair
-    # communicators of a multi-GPU node, which no box of this round offered) is reported in the line instead of ending the run
-    vs = None
-    if world >= 2:
-        try:
-            vs = view_split_block(args, net, batch, dev, rank, world)
-        except Exception as e:                               # noqa: BLE001 (reported, not swallowed)
-            vs = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
+        ts = net.timing(reset=True)
+        tb = body.timing(reset=True) if not args.no_tail else None
+        # the tail once more as ONE span (an event in front of its first kernel and one behind its last): every event record between two
+        # kernels costs a bubble of several microseconds on the stream, three of them sit inside the per-stage sum above
+        tail_span_ms = None
+        if not args.no_tail and args.stage_steps > 0:
+            body.enable_timing(2)
+            body.timing(reset=True)
+            for _ in range(args.stage_steps):
+                out = step()
+            torch.cuda.synchronize()
+            t2 = body.timing(reset=True)
+            tail_span_ms = t2["prep_ms"] / max(t2["passes"], 1)
+            body.enable_timing(False)
+        net.enable_timing(0)
+        del out
+        # fp16 storage: the range sentinel (deferred mode: nothing on the hot path) must be silent after everything timed above
+        range_ok = None
+        if args.precision == "f16":
+            net.range_status()                                   # raises airpose_amd._native.RangeError if any pass left the fp16 range
+            range_ok = True
+        cpu, sample, want = (None, None, None)
+        if rank == 0 and world == 1 and args.cpu_sample > 0:
+            cpu, sample, want = cpu_baseline(sd, md, args.cpu_sample)
+        parity = parity_block(args, sd, body, batch, net, sample, want, dev) if (rank == 0 and world == 1 and not args.no_tail) else None
+        timed_parity = None
+        if rank == 0 and world == 1 and not args.no_tail and cpu is not None and args.parity_pairs > 0:
+            timed_parity = timed_mode_parity(sd, md, pipe, dev, cpu["cores"], pairs_per_seed=max(1, args.parity_pairs // 2),
+                                             submit=bool(args.overlap_tail))
+        b64 = None
+        if rank == 0 and world == 1 and args.b64 and args.precision in ("bf16", "f16") and B != 64:
+            b64 = b64_block(args, sd, body, dev)
+        sweep = None
+        if rank == 0 and world == 1 and not args.no_tail and cpu is not None and args.parity_sweep:
+            sweep = parity_sweep(args, md, body, dev, cpu["cores"])
+        fitres = None
+        if rank == 0 and world == 1 and args.airpose_plus and not args.no_tail:
+            try:
+                fitres = airpose_plus_block(md, dev)
+            except Exception as e:                               # noqa: BLE001 (reported, not swallowed)
+                fitres = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
+        # the secondary measurement must never cost the primary one: an exception in the view-split block (it needs the pair
+        # communicators of a multi-GPU node, which no box of this round offered) is reported in the line instead of ending the run
+        vs = None
+        if world >= 2:
+            try:
+                vs = view_split_block(args, net, batch, dev, rank, world)
+            except Exception as e:                               # noqa: BLE001 (reported, not swallowed)
+                vs = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
 
     if rank == 0:
-        n_img = 2 * B
-        conv_flops_step = conv_stack_flops_per_image() * n_img
-        conv_ms_step = tm["conv_ms"] / max(tm["passes"], 1)
-        chunk = args.chunk or 512
-        # 52 convs: 4 downsample convs folded into conv3, layer1's 3 bottlenecks are one fused kernel each (bf16)
-        # two-view forwards of >= 64 pairs run the two views as two concurrent trunk passes (two internal streams):
-        # twice the launches at half the images each; conv_ms is then the span over both passes
-        dual = bool(args.dual_stream) and B >= 64 and chunk >= 128    # (views above chunk / 2 images: slices of chunk / 2 per pass stream)
-        half = args.precision in ("bf16", "f16")               # the throughput kernels (either 16-bit storage type)
-        launches = launches_timed                                # read back from the library behind the timed region: what it chose for this batch
-        # bf16x2 runs on the bf16 matrix pipe (3 MFMA products per algorithmic product): priced against the same peak
-        peak = PEAK_FP32_TFLOPS if args.precision == "fp32" else PEAK_BF16_DENSE_TFLOPS
-        achieved = conv_flops_step / (conv_ms_step * 1e-3) / 1e12
-        # SURVEY 8(d): roofline.achieved of the trunk + regressor line = pairs/s x 16.3916 GFLOP (trunk 2 x 8.174 incl. the stem +
-        # regressor 0.043) against the dense bf16 / fp16 MFMA peak -- the WHOLE step time in the denominator
-        path_flops_pair = (conv_stack_flops_per_image() + STEM_FLOPS_PER_IMAGE) * 2 + REG_FLOPS_PER_PAIR
         value = world * B * args.steps / elapsed
-        path_tf = value / world * path_flops_pair / 1e12
-        # the conv stack alone, as a span: the stream-ordered block (the two passes of a step run in lock step and the HIP events
-        # bracket both) when it was timed; in the serving form the passes of consecutive steps drift apart and only each pass's own
-        # duration exists (reported as conv_stack_own_ms: it shares the chip with the other pass's stem / pooling part of the time)
-        span_ms = other.get("conv_stack_ms") if (other is not None and args.overlap_tail) else (conv_ms_step if not args.overlap_tail else None)
+        chunk = args.chunk or 512
+        # two-view forwards of >= 64 pairs run the two views as two concurrent trunk passes (two internal streams)
+        dual = bool(args.dual_stream) and B >= 64 and chunk >= 128    # (views above chunk / 2 images: slices of chunk / 2 per pass stream)
         res = {
             "metric": "two-view frames/sec at batch %d (224x224)" % B,
             "value": value,
@@ -787,9 +819,29 @@ def main():
                                       "SMPL-X stage of step i on a second stream under them (at most 3 steps in flight); all K steps "
                                       "complete inside the timed region; outputs bit-identical to forward().  The figure with the "
                                       "REFERENCE's forward() semantics (every step complete in stream order before the next starts) is "
-                                      "`stream_ordered.pairs_per_s` of this line -- use that one to compare across rounds") if args.overlap_tail else
+                                      "`stream_ordered.pairs_per_s` of the --full line -- use that one to compare across rounds") if args.overlap_tail else
                                      "stream-ordered: every step complete on the caller's stream before the next starts (the reference's forward() semantics)",
                        "sharding": "whole pairs per GPU, no data-path collective"},
+        }
+    if rank == 0 and args.full:
+        n_img = 2 * B
+        conv_flops_step = conv_stack_flops_per_image() * n_img
+        conv_ms_step = tm["conv_ms"] / max(tm["passes"], 1)
+        # 52 convs: 4 downsample convs folded into conv3, layer1's 3 bottlenecks are one fused kernel each (bf16)
+        # two concurrent trunk passes: twice the launches at half the images each; conv_ms is then the span over both passes
+        launches = launches_timed                                # read back from the library behind the timed region: what it chose for this batch
+        # bf16x2 runs on the bf16 matrix pipe (3 MFMA products per algorithmic product): priced against the same peak
+        peak = PEAK_FP32_TFLOPS if args.precision == "fp32" else PEAK_BF16_DENSE_TFLOPS
+        achieved = conv_flops_step / (conv_ms_step * 1e-3) / 1e12
+        # SURVEY 8(d): roofline.achieved of the trunk + regressor line = pairs/s x 16.3916 GFLOP (trunk 2 x 8.174 incl. the stem +
+        # regressor 0.043) against the dense bf16 / fp16 MFMA peak -- the WHOLE step time in the denominator
+        path_flops_pair = (conv_stack_flops_per_image() + STEM_FLOPS_PER_IMAGE) * 2 + REG_FLOPS_PER_PAIR
+        path_tf = value / world * path_flops_pair / 1e12
+        # the conv stack alone, as a span: the stream-ordered block (the two passes of a step run in lock step and the HIP events
+        # bracket both) when it was timed; in the serving form the passes of consecutive steps drift apart and only each pass's own
+        # duration exists (reported as conv_stack_own_ms: it shares the chip with the other pass's stem / pooling part of the time)
+        span_ms = other.get("conv_stack_ms") if (other is not None and args.overlap_tail) else (conv_ms_step if not args.overlap_tail else None)
+        res.update({
             "roofline": {"bound": "mfma",
                          "kernel": "the 52 fused conv+BN(+residual)+ReLU layers of the trunk in %d launches per step; in the 16-bit modes, by share of "
                                    "the stack's time: blk_img_kernel (layer3's five identity bottlenecks, one image-resident kernel each), "
@@ -825,7 +877,7 @@ def main():
                                   "source": "conv_stack: HIP events inside the timed region; other stages: %d extra "
                                             "instrumented steps after it" % args.stage_steps},
             "path_tflops": path_tf,
-        }
+        })
         srt = sorted(blocks)
         res["repeat_blocks"] = {"n": len(blocks), "steps_each": rsteps, "median": srt[len(srt) // 2], "min": srt[0],
                                 "max": srt[-1], "unit": "pairs/s", "note": "block 0 is `value` (K = %d steps); the others run %d steps each" % (args.steps, rsteps)}
@@ -908,6 +960,7 @@ def main():
             # BASELINE.md publishes no throughput for this metric: vs_baseline stays null (the contract); the ratio to the CPU path
             # measured on this box is reported under its own name
             res["gpu_over_cpu_baseline"] = res["value"] / cpu["value"]
+    if rank == 0:
         res["n_ranks_seen"] = n_ranks_seen
         print(json.dumps(res))
     if use_dist:

@@ -92,9 +92,13 @@ def test_geometry_matches_reference(golden):
     out = geometry_ref.perspective_projection(pts, torch.eye(3).expand(3, 3, 3), torch.zeros(3, 3),
                                               [1475, 1475], torch.from_numpy(g["proj_center"]).unsqueeze(0))
     assert rel_err(out.numpy(), g["proj_out"]) < TOL
-    out = geometry_ref.perspective_projection(pts, torch.from_numpy(g["proj_rt_R"]),
-                                              torch.from_numpy(g["proj_rt_t"]) + torch.tensor([0, 0, 5.0]),
-                                              [1000.0, 1100.0], torch.from_numpy(g["proj_center"]))
+    # after this rigid transform some points sit at depth ~0.03 (5 - 4.97): there the float32 rounding of R p + t is amplified ~200x
+    # and depends on the summation order of the CPU's einsum kernel (1.9e-5 on another x86 host).  The oracle's formula is evaluated
+    # exactly (float64) against the reference's float32 output instead, under the same bar: 1.9e-6 on every host
+    f64 = lambda k: torch.from_numpy(g[k]).double()
+    out = geometry_ref.perspective_projection(f64("proj_points"), f64("proj_rt_R"),
+                                              f64("proj_rt_t") + torch.tensor([0, 0, 5.0], dtype=torch.float64),
+                                              [1000.0, 1100.0], f64("proj_center"))
     assert rel_err(out.numpy(), g["proj_rt_out"]) < TOL
     v, j = geometry_ref.transform_smpl(torch.from_numpy(g["tf_mat"]), torch.from_numpy(g["tf_verts"]),
                                        torch.from_numpy(g["tf_joints"]))

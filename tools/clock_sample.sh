@@ -3,7 +3,8 @@
 # guide's 2.4 GHz peak clock is what bench.py prices against: this shows what the chip actually holds under the trunk)
 cd ${GRAFT_REPO_ROOT:-/root/repo}; mkdir -p gpurun_out
 OUT=gpurun_out/clock_sample.txt; : > $OUT
-python bench.py --steps ${1:-4000} --warmup 20 --cpu-sample 0 --parity-steps 0 --b64 0 --repeat-blocks 0 --stage-steps 0 > gpurun_out/clock_bench.json 2> gpurun_out/clock_bench.err &
+D=$(dirname $OUT)                                    # the bench line and its log go beside the sample file
+python bench.py --full --steps ${1:-4000} --warmup 20 --cpu-sample 0 --parity-steps 0 --b64 0 --repeat-blocks 0 --stage-steps 0 > $D/clock_bench.json 2> $D/clock_bench.err &
 BP=$!
 t=0
 while kill -0 $BP 2>/dev/null; do

@@ -4,11 +4,11 @@
 # Counter passes are separate rocprofv3 runs with --pmc only (no tracing), as the MI355X guide prescribes.
 R=${GRAFT_REPO_ROOT:-/root/repo}; TAG=${1:-r01_x}; O=$R/gpurun_out; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
-python $R/bench.py --steps 20 --warmup 5 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
-python $R/bench.py --steps 20 --warmup 5 --batch 64 --no-tail --cpu-sample 0 --parity-steps 0 --repeat-steps 50 > $O/${TAG}_bench_b64.json 2>> $O/${TAG}_bench.err
-python $R/bench.py --steps 20 --warmup 5 --precision bf16 --cpu-sample 0 --parity-steps 0 --repeat-blocks 2 --repeat-steps 50 --b64 0 --airpose-plus 0 > $O/${TAG}_bench_bf16.json 2>> $O/${TAG}_bench.err
-python $R/bench.py --steps 10 --warmup 2 --precision bf16x2 --cpu-sample 0 --parity-steps 0 --repeat-blocks 1 --repeat-steps 10 --b64 0 --airpose-plus 0 > $O/${TAG}_bench_x2.json 2>> $O/${TAG}_bench.err
-python $R/bench.py --steps 5 --warmup 2 --precision fp32 --cpu-sample 0 --parity-steps 0 --repeat-blocks 0 --b64 0 --other-form 0 --airpose-plus 0 > $O/${TAG}_bench_fp32.json 2>> $O/${TAG}_bench.err
+python $R/bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python $R/bench.py --full --steps 20 --warmup 5 --batch 64 --no-tail --cpu-sample 0 --parity-steps 0 --repeat-steps 50 > $O/${TAG}_bench_b64.json 2>> $O/${TAG}_bench.err
+python $R/bench.py --full --steps 20 --warmup 5 --precision bf16 --cpu-sample 0 --parity-steps 0 --repeat-blocks 2 --repeat-steps 50 --b64 0 --airpose-plus 0 > $O/${TAG}_bench_bf16.json 2>> $O/${TAG}_bench.err
+python $R/bench.py --full --steps 10 --warmup 2 --precision bf16x2 --cpu-sample 0 --parity-steps 0 --repeat-blocks 1 --repeat-steps 10 --b64 0 --airpose-plus 0 > $O/${TAG}_bench_x2.json 2>> $O/${TAG}_bench.err
+python $R/bench.py --full --steps 5 --warmup 2 --precision fp32 --cpu-sample 0 --parity-steps 0 --repeat-blocks 0 --b64 0 --other-form 0 --airpose-plus 0 > $O/${TAG}_bench_fp32.json 2>> $O/${TAG}_bench.err
 rm -rf $O/${TAG}_trace $O/${TAG}_pmc_FETCH_SIZE $O/${TAG}_pmc_WRITE_SIZE
 # kernel trace of the single-pass trunk (--dual-stream 0): one kernel at a time, so the per-layer table is attributable;
 # the product's default (two concurrent passes) is what the bench lines and the counter passes below run

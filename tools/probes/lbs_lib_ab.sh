@@ -13,7 +13,7 @@ done
 if [ "$1" = "full" ]; then
  for rep in 1 2; do
   for L in libairpose_hip_base.so libairpose_hip.so; do
-   echo -n "$L bench r$rep: "; AIRPOSE_HIP_LIB=$PWD/airpose_amd/$L python bench.py --cpu-sample 0 --parity-steps 0 --b64 0 --repeat-blocks 4 2>/dev/null | python -c "
+   echo -n "$L bench r$rep: "; AIRPOSE_HIP_LIB=$PWD/airpose_amd/$L python bench.py --full --cpu-sample 0 --parity-steps 0 --b64 0 --repeat-blocks 4 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(round(d['value']), d['repeat_blocks']['median'], {k:(round(v,4) if isinstance(v,float) else v) for k,v in d['stage_ms_per_step'].items() if k!='source'}, round(d['smplx_tail_roofline']['frac'],4))"

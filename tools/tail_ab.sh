@@ -5,7 +5,7 @@ for rep in 1 2 3; do
 for v in "$@"; do
   export AIRPOSE_SMPLX_FUSED=$v
   echo -n "smplx_fused=$v: "
-  python bench.py --steps 10 --warmup 3 --stage-steps 30 --parity-sweep 0 --airpose-plus 0 --b64 0 --cpu-sample 0 --parity-steps 0 --repeat-blocks 0 --other-form 0 2>/dev/null | python -c "
+  python bench.py --full --steps 10 --warmup 3 --stage-steps 30 --parity-sweep 0 --airpose-plus 0 --b64 0 --cpu-sample 0 --parity-steps 0 --repeat-blocks 0 --other-form 0 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 s = d['stage_ms_per_step']
