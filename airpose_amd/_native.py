@@ -111,6 +111,7 @@ SIGNATURES = {
     "ap_smplx_destroy": (None, [_vp]),
     "ap_smplx_num_joints_out": (_i, [_vp]),
     "ap_smplx_fwd": (_i, [_vp, _i] + [_vp] * 8 + [_vp]),
+    "ap_smplx_bwd": (_i, [_vp, _i] + [_vp] * 14 + [_vp]),
     "ap_smplx_fwd_fused": (_i, [_vp, _i, _vp, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "ap_smplx_fwd_twoview": (_i, [_vp, _i, _vp, _i, _f, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ap_smplx_set_blend_precision": (_i, [_vp, _i]),
@@ -125,11 +126,12 @@ SIGNATURES = {
     "ap_rot6d_to_rotmat": (_i, [_vp, _i, _vp, _vp]),
     "ap_rotmat_to_angle_axis": (_i, [_vp, _i, _i, _vp, _vp]),
     "ap_batch_rodrigues": (_i, [_vp, _i, _i, _vp, _vp]),
+    "ap_batch_rodrigues_bwd": (_i, [_vp, _i, _vp, _vp, _vp]),
     "ap_transform_points": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "ap_perspective_projection": (_i, [_vp, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp]),
 }
 
-ABI_VERSION = 9          # include/airpose_hip.h: AP_ABI_VERSION
+ABI_VERSION = 10         # include/airpose_hip.h: AP_ABI_VERSION
 _lib = None
 _lib_lock = threading.Lock()
 

@@ -344,6 +344,11 @@ struct ap_smplx {
     DevBuf ws_coef, ws_A, ws_A22, ws_jposed, ws_post, ws_vposed, ws_cc;
     int n_out_joints = 0;
     Timing tm;
+    // backward (ap_smplx_bwd): its own tables and workspaces, allocated on the first backward -- never shared with a forward
+    bool bw_ready = false;
+    int bw_nr = 0;
+    DevBuf bw_bone_off, bw_bone_ent, bw_jv_off, bw_jv_ent;                  // bone-major skinning entries per vertex range; joint scatter
+    DevBuf bw_coef, bw_A, bw_jposed, bw_vposed, bw_gvp, bw_gA, bw_gt, bw_gcoef;
 };
 
 struct ap_fit {                   // AirPose+ fitting loop state (fitting.hip)
@@ -1410,7 +1415,7 @@ int regressor_run(ap_net* h, const RegInputs& in, int B, int iters, int two_view
 // ================================================================================== C ABI
 extern "C" {
 
-const char* ap_version(void) { return "airpose_hip 0.6 (gfx950; abi 9)"; }
+const char* ap_version(void) { return "airpose_hip 0.7 (gfx950; abi 10)"; }
 int ap_abi_version(void) { return AP_ABI_VERSION; }
 const char* ap_last_error(void) { return g_err.c_str(); }
 
@@ -2402,7 +2407,8 @@ void ap_smplx_destroy(ap_smplx* h) {
     (void)hipDeviceSynchronize();
     for (DevBuf* b : {&h->dirs.w, &h->dirs_split, &h->dirs.scale, &h->dirs.shift, &h->j_template, &h->j_shapedirs, &h->parents, &h->depth,
                       &h->skin_idx, &h->skin_w, &h->extra_verts, &h->lmk_tri, &h->lmk_bary, &h->ws_coef, &h->ws_A, &h->ws_A22, &h->dirs_frag, &h->jv_slot, &h->skin_idx8, &h->skin_w4, &h->skin_idx8b, &h->skin_w4b, &h->jt_pack, &h->ws_side,
-                      &h->ws_jposed, &h->ws_post, &h->ws_vposed, &h->ws_cc, &h->ws_cnt})
+                      &h->ws_jposed, &h->ws_post, &h->ws_vposed, &h->ws_cc, &h->ws_cnt, &h->bw_bone_off, &h->bw_bone_ent, &h->bw_jv_off,
+                      &h->bw_jv_ent, &h->bw_coef, &h->bw_A, &h->bw_jposed, &h->bw_vposed, &h->bw_gvp, &h->bw_gA, &h->bw_gt, &h->bw_gcoef})
         b->release();
     h->tm.destroy();
     delete h;
@@ -2537,6 +2543,150 @@ int ap_smplx_fwd_twoview(ap_smplx* h, int B, float* pred_pose, int pose_ld, floa
     return smplx_run(h, a, true, (hipStream_t)stream);
 }
 
+}  // extern "C"
+
+// ---- backward
+namespace {
+template <typename T> hipError_t download(std::vector<T>& dst, const DevBuf& src, size_t count) {
+    dst.resize(std::max<size_t>(count, 1));
+    return hipMemcpy(dst.data(), src.p, count * sizeof(T), hipMemcpyDeviceToHost);
+}
+
+// tables of the first backward, built from what the handle already holds on the device: the skinning entries bone-major
+// (ascending vertex, zero weights dropped) with each bone's start per vertex range, and per joint-vertex slot the output joints
+// it feeds (vertex picks: weight 1; landmarks: barycentric weight) in output-joint order
+hipError_t smplx_bwd_tables(ap_smplx* h) {
+    if (h->bw_ready) return hipSuccess;
+    const SmplxModelDev& m = h->m;
+    const int V = m.V, J = m.J, K = m.K, nr = (V + SMPLX_BWD_RV - 1) / SMPLX_BWD_RV;
+    std::vector<int> sidx, slot, ev, tri;
+    std::vector<float> sw, bary;
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = download(sidx, h->skin_idx, (size_t)V * K);
+    if (e == hipSuccess) e = download(sw, h->skin_w, (size_t)V * K);
+    if (e == hipSuccess) e = download(slot, h->jv_slot, V);
+    if (e == hipSuccess) e = download(ev, h->extra_verts, m.n_extra);
+    if (e == hipSuccess) e = download(tri, h->lmk_tri, (size_t)m.n_lmk * 3);
+    if (e == hipSuccess) e = download(bary, h->lmk_bary, (size_t)m.n_lmk * 3);
+    if (e != hipSuccess) return e;
+    std::vector<std::vector<int2>> per_bone(J);
+    for (int v = 0; v < V; ++v)
+        for (int k = 0; k < K; ++k) {
+            const float w = sw[(size_t)v * K + k];
+            if (w == 0.f) continue;
+            int wb;
+            memcpy(&wb, &w, 4);
+            per_bone[sidx[(size_t)v * K + k]].push_back(make_int2(v, wb));
+        }
+    std::vector<int2> ent;
+    std::vector<int> off((size_t)J * (nr + 1));
+    for (int j = 0; j < J; ++j) {
+        size_t i = 0;
+        for (int r = 0; r <= nr; ++r) {
+            while (i < per_bone[j].size() && per_bone[j][i].x < r * SMPLX_BWD_RV) ++i;
+            off[(size_t)j * (nr + 1) + r] = (int)(ent.size() + i);
+        }
+        ent.insert(ent.end(), per_bone[j].begin(), per_bone[j].end());
+    }
+    std::vector<std::vector<int2>> per_slot(m.n_jv);
+    auto add = [&](int v, int t, float w) {
+        int wb;
+        memcpy(&wb, &w, 4);
+        per_slot[slot[v]].push_back(make_int2(t, wb));
+    };
+    for (int t = 0; t < m.n_extra; ++t) add(ev[t], J + t, 1.f);
+    for (int l = 0; l < m.n_lmk; ++l)
+        for (int f = 0; f < 3; ++f) add(tri[l * 3 + f], J + m.n_extra + l, bary[l * 3 + f]);
+    std::vector<int2> jent;
+    std::vector<int> joff(m.n_jv + 1);
+    for (int s = 0; s < m.n_jv; ++s) {
+        joff[s] = (int)jent.size();
+        jent.insert(jent.end(), per_slot[s].begin(), per_slot[s].end());
+    }
+    joff[m.n_jv] = (int)jent.size();
+    if (ent.empty()) ent.push_back(make_int2(0, 0));
+    if (jent.empty()) jent.push_back(make_int2(0, 0));
+    e = upload(h->bw_bone_off, off.data(), off.size() * 4);
+    if (e == hipSuccess) e = upload(h->bw_bone_ent, ent.data(), ent.size() * sizeof(int2));
+    if (e == hipSuccess) e = upload(h->bw_jv_off, joff.data(), joff.size() * 4);
+    if (e == hipSuccess) e = upload(h->bw_jv_ent, jent.data(), jent.size() * sizeof(int2));
+    if (e != hipSuccess) return e;
+    h->bw_nr = nr;
+    h->bw_ready = true;
+    return hipSuccess;
+}
+}  // namespace
+
+extern "C" {
+
+int ap_smplx_bwd(ap_smplx* h, int n, const float* betas, const float* expression, const float* global_orient,
+                 const float* body_pose, const float* extra_pose, const float* transl, const float* grad_vertices,
+                 const float* grad_joints, float* grad_betas, float* grad_expression, float* grad_global_orient,
+                 float* grad_body_pose, float* grad_extra_pose, float* grad_transl, void* stream) {
+    (void)transl;                                            // the gradients do not depend on the translation
+    if (!h || n <= 0 || !betas || !body_pose) return fail(AP_EINVAL, "ap_smplx_bwd: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    const bool want_rest = grad_betas || grad_expression || grad_global_orient || grad_body_pose || grad_extra_pose;
+    if (!want_rest && !grad_transl) return AP_OK;
+    if (!grad_vertices && !grad_joints) {                    // zero upstream gradient
+        const std::pair<float*, size_t> outs[6] = {{grad_betas, 10}, {grad_expression, 10}, {grad_global_orient, 9},
+                                                   {grad_body_pose, 21 * 9}, {grad_extra_pose, (size_t)(h->m.J - 22) * 9}, {grad_transl, 3}};
+        for (const auto& o : outs)
+            if (o.first) HIP_TRY(hipMemsetAsync(o.first, 0, (size_t)n * o.second * 4, st));
+        return AP_OK;
+    }
+    HIP_TRY(smplx_bwd_tables(h));
+    SmplxModelDev m = h->m;                                  // (a copy: the forward's handle state is not touched)
+    m.coef_split = h->blend_split ? 1 : 0;
+    // hand / face poses (or their gradient): the K = 512 contraction; body-only: 224
+    const bool body_only = !extra_pose && !grad_extra_pose;
+    int K = body_only ? 20 + 21 * 9 : 20 + (m.J - 1) * 9;
+    K = ((K + 31) / 32) * 32;
+    const int rows16 = (3 * m.V + 15) & ~15;
+    const bool want_coef = grad_betas || grad_expression || grad_body_pose || grad_extra_pose;   // global_orient alone: no pose feature
+    const int nsplit = want_coef ? (rows16 + SMPLX_BWD_RC - 1) / SMPLX_BWD_RC : 0;
+    const int nr = h->bw_nr;
+    HIP_TRY(h->bw_coef.reserve((size_t)n * m.ncoef * 4));
+    HIP_TRY(h->bw_A.reserve((size_t)n * m.J * 12 * 4));
+    HIP_TRY(h->bw_jposed.reserve((size_t)n * m.J * 3 * 4));
+    HIP_TRY(h->bw_vposed.reserve((size_t)n * m.ldv * 4));
+    HIP_TRY(h->bw_gvp.reserve((size_t)n * m.ldv * 4));
+    HIP_TRY(h->bw_gA.reserve((size_t)n * nr * m.J * 12 * 4));
+    HIP_TRY(h->bw_gt.reserve((size_t)n * nr * 3 * 4));
+    if (nsplit) HIP_TRY(h->bw_gcoef.reserve((size_t)nsplit * n * K * 4));
+    // recompute: coefficient rows and bone transforms (smplx_prep_kernel), v_posed (the forward's two-kernel blend GEMM)
+    SmplxFwdArgs f{};
+    f.n = n; f.betas = betas; f.expression = expression; f.global_orient = global_orient; f.body_pose = body_pose;
+    f.extra_pose = extra_pose;
+    f.coef = h->bw_coef.as<float>(); f.A = h->bw_A.as<float>(); f.jposed = h->bw_jposed.as<float>();
+    HIP_TRY(ap_launch_smplx_prep(m, f, st));
+    {
+        ConvArgs g{};
+        g.x = f.coef; g.w = h->blend_split ? h->dirs_split.p : h->dirs.w.p;
+        g.scale = h->dirs.scale.as<float>(); g.shift = h->dirs.shift.as<float>();
+        g.out_f32 = 1;
+        g.res = nullptr; g.y = h->bw_vposed.p;
+        g.N = n; g.H = g.W = g.Ho = g.Wo = 1; g.Cin = K; g.Cout = h->dirs.cout; g.KH = g.KW = 1; g.stride = 1; g.pad = 0;
+        g.M = n; g.ldx = m.ncoef; g.ldy = m.ldv; g.ldr = 0; g.wld = h->dirs.wld; g.relu = 0;
+        HIP_TRY(dispatch_conv(g, h->blend_split ? AP_PREC_BF16X2 : AP_PREC_FP32, st));
+    }
+    SmplxBwdArgs a{};
+    a.n = n; a.betas = betas; a.expression = expression; a.global_orient = global_orient; a.body_pose = body_pose;
+    a.extra_pose = extra_pose; a.grad_vertices = grad_vertices; a.grad_joints = grad_joints;
+    a.grad_betas = grad_betas; a.grad_expression = grad_expression; a.grad_global_orient = grad_global_orient;
+    a.grad_body_pose = grad_body_pose; a.grad_extra_pose = grad_extra_pose; a.grad_transl = grad_transl;
+    a.A = f.A; a.vposed = h->bw_vposed.as<float>(); a.gvp = h->bw_gvp.as<float>(); a.gA = h->bw_gA.as<float>();
+    a.gt = h->bw_gt.as<float>(); a.gcoef = h->bw_gcoef.as<float>();
+    a.nr = nr; a.nsplit = nsplit; a.kp = K;
+    a.dirs = h->dirs.w.as<float>();
+    a.bone_off = h->bw_bone_off.as<int>(); a.bone_ent = h->bw_bone_ent.as<int2>();
+    a.jv_off = h->bw_jv_off.as<int>(); a.jv_ent = h->bw_jv_ent.as<int2>();
+    HIP_TRY(ap_launch_smplx_bwd_lbs(m, a, st));
+    if (nsplit) HIP_TRY(ap_launch_smplx_bwd_coef(m, a, st));
+    HIP_TRY(ap_launch_smplx_bwd_chain(m, a, st));
+    return AP_OK;
+}
+
 int ap_smplx_set_blend_precision(ap_smplx* h, int precision) {
     if (!h || (precision != AP_PREC_FP32 && precision != AP_PREC_BF16X2))
         return fail(AP_EINVAL, "ap_smplx_set_blend_precision: AP_PREC_FP32 or AP_PREC_BF16X2");
@@ -2585,6 +2735,12 @@ int ap_batch_rodrigues(const float* angle_axis, int n, int variant, float* rotma
     if (!angle_axis || !rotmat || n <= 0 || (variant != 0 && variant != 1))
         return fail(AP_EINVAL, "ap_batch_rodrigues: bad argument (variant 0 = smplx lbs, 1 = copenet geometry)");
     HIP_TRY(ap_launch_batch_rodrigues(angle_axis, n, variant, rotmat, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_batch_rodrigues_bwd(const float* angle_axis, int n, const float* grad_rotmat, float* grad_angle_axis, void* stream) {
+    if (!angle_axis || !grad_rotmat || !grad_angle_axis || n <= 0) return fail(AP_EINVAL, "ap_batch_rodrigues_bwd: bad argument");
+    HIP_TRY(ap_launch_batch_rodrigues_bwd(angle_axis, n, grad_rotmat, grad_angle_axis, (hipStream_t)stream));
     return AP_OK;
 }
 

@@ -263,6 +263,34 @@ bool ap_smplx_lbs_fused_supported(const SmplxModelDev& m);
 size_t ap_smplx_dirs_frag_bytes(int V);
 hipError_t ap_launch_smplx_lbs_fused(const SmplxModelDev& m, const SmplxFwdArgs& a, int n_cu, int merged, hipStream_t st);
 
+// ---- SMPL-X backward (smplx_bwd.hip): adjoint of ap_smplx_fwd.  A and vposed are the backward's own recompute of the forward's
+// bone transforms and v_posed (never the forward's workspaces)
+constexpr int SMPLX_BWD_RV = 1024;    // vertices per range of the LBS adjoint (its bone sums are per range, summed by the chain kernel)
+constexpr int SMPLX_BWD_RC = 1024;    // rows (of 3V) per reduction split of the blend-shape adjoint
+struct SmplxBwdArgs {
+    int n;
+    const float *betas, *expression, *global_orient, *body_pose, *extra_pose;   // as SmplxFwdArgs
+    const float* grad_vertices;   // [n][V][3] or NULL
+    const float* grad_joints;     // [n][J+21+51][3] or NULL
+    float *grad_betas, *grad_expression, *grad_global_orient, *grad_body_pose, *grad_extra_pose, *grad_transl;   // each or NULL
+    const float* A;               // [n][J][12]
+    const float* vposed;          // [n][ldv]
+    float* gvp;                   // [n][ldv]: g_vposed
+    float* gA;                    // [n][nr][J][12]: g_A per vertex range
+    float* gt;                    // [n][nr][3]: sum of grad_vertices per vertex range
+    float* gcoef;                 // [nsplit][n][kp]: g_coef per reduction split
+    int nr, nsplit, kp;           // vertex ranges, reduction splits (0: no shape / pose gradient wanted), coefficients (224 | 512)
+    const float* dirs;            // [ldv rows][ncoef] fp32 blend-shape directions (the forward's fp32 GEMM operand, read only)
+    const int* bone_off;          // [J][nr + 1]: bone j's skinning entries inside range r: [bone_off[j][r], bone_off[j][r + 1])
+    const int2* bone_ent;         // (vertex, weight bits), bone-major, ascending vertex
+    const int* jv_off;            // [n_jv + 1]: output joints fed by joint-vertex slot s: [jv_off[s], jv_off[s + 1])
+    const int2* jv_ent;           // (output joint, weight bits)
+};
+hipError_t ap_launch_smplx_bwd_lbs(const SmplxModelDev& m, const SmplxBwdArgs& a, hipStream_t st);
+hipError_t ap_launch_smplx_bwd_coef(const SmplxModelDev& m, const SmplxBwdArgs& a, hipStream_t st);
+hipError_t ap_launch_smplx_bwd_chain(const SmplxModelDev& m, const SmplxBwdArgs& a, hipStream_t st);
+hipError_t ap_launch_batch_rodrigues_bwd(const float* aa, int n, const float* gR, float* gaa, hipStream_t st);
+
 // ---- stand-alone geometry helpers (smplx.hip)
 hipError_t ap_launch_rot6d(const float* x6, int n, float* R, hipStream_t st);
 hipError_t ap_launch_rotmat_to_angle_axis(const float* R, int n, int ld, float* out, hipStream_t st);

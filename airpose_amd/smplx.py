@@ -3,7 +3,9 @@
 Mirrors ``smplx.SMPLX`` as the reference uses it (copenet/src/copenet/copenet_twoview.py:36-45 ctor,
 :237-241 ``forward(betas=, body_pose=, global_orient=, transl=, pose2rot=False)``, :64-65 ``.to()``,
 :69 ``.v_template``, :77 ``.faces``): the forward pass runs in libairpose_hip.so (pose prep + kinematic
-chain, blend-shape contraction in split-bf16 form on the bf16 matrix pipe fused with the sparse skinning, joint/landmark gather).  Semantics follow
+chain, blend-shape contraction in split-bf16 form on the bf16 matrix pipe fused with the sparse skinning, joint/landmark gather).
+``forward`` is differentiable (ap_smplx_bwd: the hand-written adjoint) when an input requires grad; ``forward_fused`` /
+``forward_twoview`` are inference-only.  Semantics follow
 upstream smplx 0.1.28 (the fork's source is absent from the reference checkout).
 """
 import ctypes
@@ -12,6 +14,7 @@ import threading
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from . import _native as N
 from . import smplx_model as SM
@@ -24,6 +27,26 @@ class ModelOutput(object):
         self.vertices = self.joints = self.full_pose = self.betas = self.global_orient = None
         self.body_pose = self.expression = self.transl = None
         self.__dict__.update(kw)
+
+
+class _SmplxFunction(torch.autograd.Function):
+    """SMPLX.forward under autograd: ap_smplx_fwd forward (bit-identical to the no-grad call), ap_smplx_bwd backward.
+    Inputs are the converted fp32 contiguous tensors (betas, expression, global_orient, body_pose, extra_pose, transl)."""
+
+    @staticmethod
+    def forward(ctx, model, betas, expression, go, body, extra, transl):
+        inputs = (betas, expression, go, body, extra, transl)
+        ctx.model, ctx.B = model, betas.shape[0]
+        ctx.save_for_backward(*inputs)
+        ctx.set_materialize_grads(False)                 # an unused output's gradient arrives as None -> NULL
+        return model._fwd_native(betas.device, ctx.B, *inputs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_verts, g_joints):
+        inputs = ctx.saved_tensors
+        grads = ctx.model._bwd_native(inputs[0].device, ctx.B, inputs, g_verts, g_joints, ctx.needs_input_grad[1:])
+        return (None, *grads)
 
 
 class SMPLX(nn.Module):
@@ -182,6 +205,17 @@ class SMPLX(nn.Module):
             raise RuntimeError("expression must be (B, %d), got %s" % (self.num_expression_coeffs, tuple(expression.shape)))
         if transl is not None and tuple(transl.shape) != (B, 3):
             raise RuntimeError("transl must be (B, 3), got %s" % (tuple(transl.shape),))
+        inputs = (betas, expression, go, body, extra, transl)
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in inputs):
+            # differentiable call: the same ap_smplx_fwd, its adjoint ap_smplx_bwd in backward (the conversions above are
+            # autograd-transparent, so the gradients reach the caller's tensors in their own shapes and dtypes)
+            verts, joints = _SmplxFunction.apply(self, *inputs)
+        else:
+            verts, joints = self._fwd_native(dev, B, *inputs)
+        return ModelOutput(vertices=verts if return_verts else None, joints=joints, betas=betas, expression=expression,
+                           global_orient=global_orient, body_pose=body_pose, transl=transl)
+
+    def _fwd_native(self, dev, B, betas, expression, go, body, extra, transl):
         verts = torch.empty(B, self.num_verts, 3, device=dev, dtype=torch.float32)
         with self._lock, torch.cuda.device(dev):
             h = self._native(dev)
@@ -189,13 +223,30 @@ class SMPLX(nn.Module):
             N.check(N.lib().ap_smplx_fwd(h, B, N.dptr(betas), N.dptr(expression), N.dptr(go), N.dptr(body),
                                          N.dptr(extra), N.dptr(transl), N.dptr(verts), N.dptr(joints),
                                          N.stream_ptr(dev)), "ap_smplx_fwd")
-        return ModelOutput(vertices=verts if return_verts else None, joints=joints, betas=betas, expression=expression,
-                           global_orient=global_orient, body_pose=body_pose, transl=transl)
+        return verts, joints
+
+    def _bwd_native(self, dev, B, inputs, g_verts, g_joints, want):
+        """ap_smplx_bwd on the current stream: gradients of the inputs flagged in `want` (None elsewhere)."""
+        betas, expression, go, body, extra, transl = inputs
+        shapes = ((B, 10), (B, self.num_expression_coeffs), (B, 1, 3, 3), (B, 21, 3, 3), (B, 33, 3, 3), (B, 3))
+        grads = [torch.empty(sh, device=dev, dtype=torch.float32) if w and t is not None else None
+                 for t, sh, w in zip(inputs, shapes, want)]
+        if all(g is None for g in grads):
+            return grads
+        g_verts = N.f32c(g_verts, dev)
+        g_joints = N.f32c(g_joints, dev)
+        with self._lock, torch.cuda.device(dev):
+            h = self._native(dev)
+            N.check(N.lib().ap_smplx_bwd(h, B, N.dptr(betas), N.dptr(expression), N.dptr(go), N.dptr(body), N.dptr(extra),
+                                         N.dptr(transl), N.dptr(g_verts), N.dptr(g_joints), *[N.dptr(g) for g in grads],
+                                         N.stream_ptr(dev)), "ap_smplx_bwd")
+        return grads
 
     def forward_fused(self, pred_pose, pred_betas, cam_center=None, focal_length=(1475.0, 1475.0), want_rotmat=True):
         """rot6d -> SMPL-X (global_orient = I, transl = 0) -> transform_smpl([R_root | trans]) -> projection for
         one view in three launches + one GEMM (copenet_twoview.py:222-223, 237-246, 307-311).
-        pred_pose (n,135) with the translation already un-scaled.  Returns dict."""
+        pred_pose (n,135) with the translation already un-scaled.  Returns dict.  Not differentiable: the outputs carry no
+        gradient (inference path; SMPLX.forward is the differentiable entry)."""
         if not pred_pose.is_cuda:
             raise RuntimeError("airpose_amd.SMPLX: inputs must be CUDA (ROCm) tensors; there is no CPU path")
         dev = pred_pose.device
@@ -221,7 +272,7 @@ class SMPLX(nn.Module):
         237-279, 307-317).  pred_pose (2,B,135) / pred_betas (2,B,10): view 0 first, contiguous; with trans_scale > 0
         the translation columns of pred_pose are un-scaled IN PLACE (the reference's ``pred_smpltrans /= trans_scale``
         on a view of pred_pose).  in_smpltrans (2,B,3): also emit the test-mode input meshes (betas = 0, identity
-        root).  Returns dict of (2,B,...) tensors."""
+        root).  Returns dict of (2,B,...) tensors.  Not differentiable, like forward_fused."""
         if not pred_pose.is_cuda:
             raise RuntimeError("airpose_amd.SMPLX: inputs must be CUDA (ROCm) tensors; there is no CPU path")
         dev = pred_pose.device

@@ -50,10 +50,11 @@ typedef struct ap_net ap_net;     /* ResNet-50 trunk + IEF regressor */
 typedef struct ap_smplx ap_smplx; /* SMPL-X body model */
 
 /* ABI number of this header: bumped whenever an exported signature changes or an entry point is added or removed
- * (8: round 6 -- ap_net_parity_probe, ap_net_range_peek / _mark_next / _slot, ap_regressor_feat_part / _step_local / _step_finish;
+ * (10: ap_smplx_bwd, ap_batch_rodrigues_bwd -- the adjoints of ap_smplx_fwd and of lbs.batch_rodrigues;
+ *  8: round 6 -- ap_net_parity_probe, ap_net_range_peek / _mark_next / _slot, ap_regressor_feat_part / _step_local / _step_finish;
  *  7: ap_conv_pw_*, ap_block_img_*; 6: ap_set_pair_groups removed).  A binding built against another number must refuse to load
  * the library (airpose_amd/_native.py does). */
-#define AP_ABI_VERSION 9
+#define AP_ABI_VERSION 10
 const char* ap_version(void);
 int ap_abi_version(void);
 const char* ap_last_error(void);
@@ -460,6 +461,19 @@ int ap_smplx_fwd(ap_smplx* h, int n, const float* betas, const float* expression
                  const float* body_pose, const float* extra_pose, const float* transl, float* vertices,
                  float* joints, void* stream);
 
+/* Adjoint of ap_smplx_fwd for the same inputs (plain autograd through upstream smplx 0.1.28 lbs: gradients with respect to
+ * the rotation matrices are the unconstrained 3x3 Jacobians).  grad_vertices [n][V][3] / grad_joints [n][127][3]: either may
+ * be NULL (zero).  Outputs grad_betas / grad_expression [n][10], grad_global_orient [n][3][3], grad_body_pose [n][21][3][3],
+ * grad_extra_pose [n][33][3][3], grad_transl [n][3] are written, not accumulated; each may be NULL (not wanted; the blend-shape
+ * contraction is skipped when neither a shape nor a pose-feature gradient is wanted).  The bone transforms and v_posed are
+ * recomputed from the inputs into the handle's own backward workspaces (allocated on the first backward; no forward workspace
+ * is touched).  Deterministic: no floating-point atomics, and a body's gradients do not depend on n or its place in the batch. */
+int ap_smplx_bwd(ap_smplx* h, int n, const float* betas, const float* expression, const float* global_orient,
+                 const float* body_pose, const float* extra_pose, const float* transl,
+                 const float* grad_vertices, const float* grad_joints,
+                 float* grad_betas, float* grad_expression, float* grad_global_orient, float* grad_body_pose,
+                 float* grad_extra_pose, float* grad_transl, void* stream);
+
 /* Fused caller slice for one view: rot6d_to_rotmat -> SMPLX.forward(global_orient = I, transl = 0) ->
  * transform_smpl([R_root | trans]) -> perspective_projection(R = I, t = 0)
  * (copenet_twoview.py:222-223, 237-246, 307-311).  pred_pose [n][pose_ld]: trans3 (already un-scaled) |
@@ -550,6 +564,9 @@ int ap_rotmat_to_angle_axis(const float* rotmat, int n, int cols, float* angle_a
  * (copenet/dsets/aerialpeople.py:177) and SMPLX.forward(pose2rot=True) applies to its pose inputs; variant 1:
  * copenet/utils/geometry.py:9-45 batch_rodrigues (through a unit quaternion). */
 int ap_batch_rodrigues(const float* angle_axis, int n, int variant, float* rotmat, void* stream);
+/* Adjoint of ap_batch_rodrigues variant 0 (lbs.batch_rodrigues, epsilon = 1e-8): angle_axis [n][3], grad_rotmat [n][3][3]
+ * -> grad_angle_axis [n][3] (written). */
+int ap_batch_rodrigues_bwd(const float* angle_axis, int n, const float* grad_rotmat, float* grad_angle_axis, void* stream);
 int ap_transform_points(const float* rt, const float* pts, int B, int P, float* out, void* stream); /* rt [B][3][4] */
 int ap_perspective_projection(const float* pts, int B, int P, const float* rotation, const float* translation,
                               float fx, float fy, const float* center, float* out, void* stream);
