@@ -1,0 +1,82 @@
+"""ctypes binding of libairpose_grad.so (the C ABI in include/airpose_grad.h): the gradient entry points.
+
+Same pattern as _native.py: PyTorch is used for device memory and streams only, the library is loaded lazily and checked
+against the header's ABI number, and there is NO fallback: if the library is missing or a call fails, a RuntimeError is raised.
+"""
+import ctypes
+import os
+import threading
+
+import torch  # noqa: F401  (must be imported first so that libamdhip64 is the one torch loaded)
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.environ.get("AIRPOSE_GRAD_LIB", os.path.join(_HERE, "libairpose_grad.so"))
+
+_c = ctypes
+_vp, _i, _f, _i64, _u64 = _c.c_void_p, _c.c_int, _c.c_float, _c.c_int64, _c.c_uint64
+_vpp, _ip = _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_int)
+
+# name -> (restype, argtypes); mirrors include/airpose_grad.h one to one
+SIGNATURES = {
+    "apg_version": (_c.c_char_p, []),
+    "apg_abi_version": (_i, []),
+    "apg_last_error": (_c.c_char_p, []),
+    "apg_dropout_mask": (_i, [_u64, _i, _i, _i, _f, _vp, _vp]),
+    "apg_head_fwd": (_i, [_i, _vp, _vp, _vpp, _ip] + [_vp] * 8 + [_u64, _f, _f] + [_vp] * 3 + [_vpp, _vpp, _vp]),
+    "apg_head_bwd_workspace_bytes": (_i64, [_i, _i]),
+    "apg_head_bwd": (_i, [_i] + [_vp] * 7 + [_u64, _f, _f, _vpp, _vpp, _vpp, _vp, _i64, _vp]),
+    "apg_rot6d_to_rotmat_bwd": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "apg_perspective_projection_bwd": (_i, [_vp, _i, _i, _vp, _vp, _f, _f] + [_vp] * 5 + [_vp]),
+    "apg_transform_points_bwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+}
+
+ABI_VERSION = 1          # include/airpose_grad.h: APG_ABI_VERSION
+_lib = None
+_lib_lock = threading.Lock()
+
+
+def lib():
+    """Load (once) and return the gradient library; raises if it has not been built."""
+    global _lib
+    if _lib is None:
+        with _lib_lock:
+            if _lib is None:
+                if not os.path.isfile(LIB_PATH):
+                    raise RuntimeError(
+                        "airpose_amd: %s is missing -- build it with `python -c 'import __graft_entry__ as g; "
+                        "g.build()'` (hipcc, gfx950).  There is no CPU fallback." % LIB_PATH)
+                L = ctypes.CDLL(LIB_PATH)
+                abi = getattr(L, "apg_abi_version", None)
+                if abi is None or abi() != ABI_VERSION:
+                    raise RuntimeError("airpose_amd: %s exports ABI %s, this binding is written against ABI %d (include/airpose_grad.h: "
+                                       "APG_ABI_VERSION) -- rebuild the library" % (LIB_PATH, "?" if abi is None else abi(), ABI_VERSION))
+                for name, (res, args) in SIGNATURES.items():
+                    fn = getattr(L, name)
+                    fn.restype, fn.argtypes = res, args
+                _lib = L
+    return _lib
+
+
+def check(rc, what):
+    if rc != 0:
+        msg = lib().apg_last_error().decode("utf-8", "replace")
+        raise RuntimeError("airpose_grad %s failed (status %d): %s" % (what, rc, msg))
+
+
+def ptrs(tensors):
+    """HOST array of device pointers (None -> NULL) for the entry points that take one."""
+    arr = (_c.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+    return arr
+
+
+def ints(values):
+    return (_c.c_int * len(values))(*values)
+
+
+def dropout_mask(seed, layer, rows, cols, p, device):
+    """(rows, cols) uint8 on `device`: exactly the keep mask of (seed, layer) the head kernels apply (1 = kept)."""
+    out = torch.empty(rows, cols, device=device, dtype=torch.uint8)
+    with torch.cuda.device(device):
+        check(lib().apg_dropout_mask(int(seed), int(layer), int(rows), int(cols), float(p), _c.c_void_p(out.data_ptr()),
+                                     _c.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "apg_dropout_mask")
+    return out

@@ -7,7 +7,8 @@ same outputs, same sub-module / buffer names, hence the same 331 ``state_dict`` 
 ``copenet_twoview`` (copenet/src/copenet/copenet_twoview.py:60,79-80) and Lightning checkpoints
 work unchanged.  The nn.Conv2d / nn.BatchNorm2d / nn.Linear children are parameter containers
 only: all compute goes through the C ABI of libairpose_hip.so (hand-written gfx950 kernels).
-Inference (eval) only; there is no CPU or eager fallback.
+Inference (eval) only, except the two-view IEF head: forward_ief / forward_reg are differentiable in train mode or with
+inputs that require grad (head_grad.py, libairpose_grad.so).  There is no CPU or eager fallback.
 """
 import ctypes
 import threading
@@ -17,6 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as N
+from . import head_grad
 
 
 class Bottleneck(nn.Module):
@@ -206,6 +208,15 @@ class copenet(nn.Module):
             raise RuntimeError("airpose_amd.copenet implements the inference path only: call .eval() "
                                "(training through the HIP kernels is out of scope)")
 
+    def _head_trains(self, *inputs):
+        """forward_ief / forward_reg of the two-view head take the differentiable path (head_grad.py, libairpose_grad.so: fp32 on
+        the live fc1 / fc2 / decpose / decshape parameters, drop1 / drop2 active in their training mode) in train mode, or when
+        grad is enabled and an input requires grad.  Otherwise the inference path runs unchanged."""
+        if self.variant != 0:
+            return False
+        return self.training or (torch.is_grad_enabled() and
+                                 any(isinstance(t, torch.Tensor) and t.requires_grad for t in inputs))
+
     @staticmethod
     def _dev(x):
         if not x.is_cuda:
@@ -303,7 +314,11 @@ class copenet(nn.Module):
 
     def forward_ief(self, xf0, xf1, bb0, bb1, init_position0, init_position1, init_theta0=None, init_theta1=None,
                     init_shape0=None, init_shape1=None, iters=3):
-        """The IEF loop of forward() from pre-computed trunk features (model_copenet.py:144-157)."""
+        """The IEF loop of forward() from pre-computed trunk features (model_copenet.py:144-157).  Differentiable in train mode
+        or when an input requires grad (two-view head): see _head_trains."""
+        if self._head_trains(xf0, xf1, bb0, bb1, init_position0, init_position1, init_theta0, init_theta1, init_shape0, init_shape1):
+            return head_grad.forward_ief(self, xf0, xf1, bb0, bb1, init_position0, init_position1, init_theta0, init_theta1,
+                                         init_shape0, init_shape1, iters)
         self._check_eval()
         dev = self._dev(xf0)
         if xf0.dim() != 2 or xf0.shape[1] != 2048 or xf1.shape != xf0.shape:
@@ -313,7 +328,12 @@ class copenet(nn.Module):
 
     def forward_reg(self, xf0, xf1, bb0, bb1, pred_position0, pred_position1, pred_orient0, pred_orient1,
                     pred_art_pose0, pred_art_pose1, pred_shape0, pred_shape1):
-        """One regressor evaluation for both views [model_copenet.py:178-204]."""
+        """One regressor evaluation for both views [model_copenet.py:178-204].  Differentiable in train mode or when an input
+        requires grad (two-view head): see _head_trains."""
+        if self._head_trains(xf0, xf1, bb0, bb1, pred_position0, pred_position1, pred_orient0, pred_orient1, pred_art_pose0,
+                             pred_art_pose1, pred_shape0, pred_shape1):
+            return head_grad.forward_reg(self, xf0, xf1, bb0, bb1, pred_position0, pred_position1, pred_orient0, pred_orient1,
+                                         pred_art_pose0, pred_art_pose1, pred_shape0, pred_shape1)
         th0 = torch.cat([pred_orient0, pred_art_pose0], 1)
         th1 = torch.cat([pred_orient1, pred_art_pose1], 1)
         return self.forward_ief(xf0, xf1, bb0, bb1, pred_position0, pred_position1, th0, th1,

@@ -1,9 +1,12 @@
 """GPU versions of the reference's geometry helpers on the hot path
 (copenet/src/copenet/utils/geometry.py:47-61 rot6d_to_rotmat, :63-91 perspective_projection).
-Each is one launch of a hand-written HIP kernel through the C ABI; no CPU path."""
+Each is one launch of a hand-written HIP kernel through the C ABI; no CPU path.  rot6d_to_rotmat and perspective_projection are
+differentiable when an input requires grad: the forward is the same kernel, the backward a kernel of libairpose_grad.so."""
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _native as N
+from . import _native_grad as G
 
 
 def _cuda(t, name):
@@ -12,14 +15,45 @@ def _cuda(t, name):
     return t.device
 
 
-def rot6d_to_rotmat(x):
-    """(B,6k) 6-D rotations -> (B*k,3,3)   [geometry.py:47-61]"""
-    dev = _cuda(x, "rot6d_to_rotmat")
-    x = N.f32c(x).reshape(-1, 6)
+def _grad_wanted(*ts):
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts)
+
+
+def _rot6d_fwd(x):
+    dev = x.device
     out = torch.empty(x.shape[0], 3, 3, device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
         N.check(N.lib().ap_rot6d_to_rotmat(N.dptr(x), x.shape[0], N.dptr(out), N.stream_ptr(dev)), "ap_rot6d_to_rotmat")
     return out
+
+
+class _Rot6d(torch.autograd.Function):
+    """Forward: ap_rot6d_to_rotmat (the no-grad kernel, same bits); backward: apg_rot6d_to_rotmat_bwd."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        return _rot6d_fwd(x)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, = ctx.saved_tensors
+        dev = x.device
+        g = N.f32c(g)
+        gx = torch.empty_like(x)
+        with torch.cuda.device(dev):
+            G.check(G.lib().apg_rot6d_to_rotmat_bwd(N.dptr(x), x.shape[0], N.dptr(g), N.dptr(gx), N.stream_ptr(dev)),
+                    "apg_rot6d_to_rotmat_bwd")
+        return gx
+
+
+def rot6d_to_rotmat(x):
+    """(B,6k) 6-D rotations -> (B*k,3,3)   [geometry.py:47-61]; differentiable when x requires grad."""
+    _cuda(x, "rot6d_to_rotmat")
+    if _grad_wanted(x):
+        return _Rot6d.apply(N.f32c(x).reshape(-1, 6))
+    return _rot6d_fwd(N.f32c(x).reshape(-1, 6))
 
 
 def _rodrigues(theta, variant, name):
@@ -53,19 +87,57 @@ def rotation_matrix_to_angle_axis(rotation_matrix):
     return out
 
 
-def perspective_projection(points, rotation, translation, focal_length, camera_center):
-    """(bs,N,3) -> (bs,N,2)   [geometry.py:63-91]; camera_center (bs,2) or the caller's (1,bs,2)."""
-    dev = _cuda(points, "perspective_projection")
+def _projection_fwd(points, rotation, translation, fx, fy, cc):
+    dev = points.device
     B, P = points.shape[0], points.shape[1]
+    out = torch.empty(B, P, 2, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        N.check(N.lib().ap_perspective_projection(N.dptr(points), B, P, N.dptr(rotation), N.dptr(translation), fx, fy,
+                                                  N.dptr(cc), N.dptr(out), N.stream_ptr(dev)), "ap_perspective_projection")
+    return out
+
+
+class _Projection(torch.autograd.Function):
+    """Forward: ap_perspective_projection (the no-grad kernel, same bits); backward: apg_perspective_projection_bwd."""
+
+    @staticmethod
+    def forward(ctx, points, rotation, translation, cc, fx, fy):
+        ctx.fxy = (fx, fy)
+        ctx.save_for_backward(points, rotation, translation)
+        return _projection_fwd(points, rotation, translation, fx, fy, cc)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        points, rotation, translation = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dev = points.device
+        B = points.shape[0]
+        g = N.f32c(g)
+        mk = lambda flag, *shape: torch.empty(*shape, device=dev, dtype=torch.float32) if flag else None
+        gp, gr, gt, gc = mk(need[0], *points.shape), mk(need[1], B, 3, 3), mk(need[2], B, 3), mk(need[3], B, 2)
+        with torch.cuda.device(dev):
+            G.check(G.lib().apg_perspective_projection_bwd(N.dptr(points), B, points.shape[1], N.dptr(rotation),
+                                                           N.dptr(translation), ctx.fxy[0], ctx.fxy[1], N.dptr(g), N.dptr(gp),
+                                                           N.dptr(gr), N.dptr(gt), N.dptr(gc), N.stream_ptr(dev)),
+                    "apg_perspective_projection_bwd")
+        return gp, gr, gt, gc, None, None
+
+
+def perspective_projection(points, rotation, translation, focal_length, camera_center):
+    """(bs,N,3) -> (bs,N,2)   [geometry.py:63-91]; camera_center (bs,2) or the caller's (1,bs,2).  Differentiable in points,
+    rotation, translation and camera_center when one of them requires grad; focal_length is not differentiable."""
+    dev = _cuda(points, "perspective_projection")
+    B = points.shape[0]
+    if isinstance(focal_length, torch.Tensor) and focal_length.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("perspective_projection: focal_length is not differentiable (pass it detached)")
     points = N.f32c(points)
     rotation = N.f32c(rotation, dev)
     translation = N.f32c(translation, dev)
     cc = N.f32c(camera_center, dev).reshape(-1, 2)
     if cc.shape[0] != B:
         cc = cc.expand(B, 2).contiguous()
-    out = torch.empty(B, P, 2, device=dev, dtype=torch.float32)
-    with torch.cuda.device(dev):
-        N.check(N.lib().ap_perspective_projection(N.dptr(points), B, P, N.dptr(rotation), N.dptr(translation),
-                                                  float(focal_length[0]), float(focal_length[1]), N.dptr(cc),
-                                                  N.dptr(out), N.stream_ptr(dev)), "ap_perspective_projection")
-    return out
+    fx, fy = float(focal_length[0]), float(focal_length[1])
+    if _grad_wanted(points, rotation, translation, cc):
+        return _Projection.apply(points, rotation, translation, cc, fx, fy)
+    return _projection_fwd(points, rotation, translation, fx, fy, cc)

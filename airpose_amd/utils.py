@@ -2,11 +2,13 @@
 import ctypes
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _native as N
+from . import _native_grad as G
 
 
-def _apply(rt, pts):
+def _apply_fwd(rt, pts):
     dev = pts.device
     out = torch.empty_like(pts, dtype=torch.float32)
     with torch.cuda.device(dev):
@@ -15,8 +17,37 @@ def _apply(rt, pts):
     return out
 
 
+class _Transform(torch.autograd.Function):
+    """Forward: ap_transform_points (the no-grad kernel, same bits); backward: apg_transform_points_bwd."""
+
+    @staticmethod
+    def forward(ctx, rt, pts):
+        ctx.save_for_backward(rt, pts)
+        return _apply_fwd(rt, pts)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        rt, pts = ctx.saved_tensors
+        dev = pts.device
+        g = N.f32c(g)
+        grt = torch.empty_like(rt) if ctx.needs_input_grad[0] else None
+        gpts = torch.empty_like(pts) if ctx.needs_input_grad[1] else None
+        with torch.cuda.device(dev):
+            G.check(G.lib().apg_transform_points_bwd(N.dptr(rt), N.dptr(pts), pts.shape[0], pts.shape[1], N.dptr(g),
+                                                     N.dptr(grt), N.dptr(gpts), N.stream_ptr(dev)), "apg_transform_points_bwd")
+        return grt, gpts
+
+
+def _apply(rt, pts):
+    if torch.is_grad_enabled() and (rt.requires_grad or pts.requires_grad):
+        return _Transform.apply(rt, pts)
+    return _apply_fwd(rt, pts)
+
+
 def transform_smpl(trans_mat, smplvertices=None, smpljoints=None, orientation=None, smpltrans=None):
-    """Returns (verts, joints, orient, trans) like the reference; trans_mat (B,3,4) or (B,4,4)."""
+    """Returns (verts, joints, orient, trans) like the reference; trans_mat (B,3,4) or (B,4,4).  Differentiable in trans_mat
+    and every leg when one of them requires grad (same forward kernel, backward in libairpose_grad.so)."""
     if not trans_mat.is_cuda:
         raise RuntimeError("airpose_amd.utils.transform_smpl: CUDA (ROCm) tensors only; there is no CPU path")
     rt = N.f32c(trans_mat[:, :3, :4])

@@ -1,0 +1,101 @@
+/* airpose_grad.h -- C ABI of libairpose_grad.so (gfx950 / MI355X): the gradient entry points.
+ *
+ * The training-side companion of libairpose_hip.so.  It holds the forward / backward of the IEF regressor head
+ * (copenet.forward_reg, copenet/src/copenet/models/model_copenet.py:178-204) on live weights, and the adjoints of the
+ * geometry helpers of the reference's training loss (copenet_twoview.py:205-317).  A library of its own, so that the
+ * inference library's ABI, exports and binary stay as they are.
+ *
+ * Conventions
+ *   - stateless: no handle.  Every data pointer is a DEVICE pointer owned by the caller (PyTorch's caching allocator);
+ *     weights are read straight from the caller's fp32 row-major [out][in] storage on every call (no packing);
+ *   - `stream` is a hipStream_t passed as void*; all work is enqueued on it, nothing synchronises;
+ *   - return value: 0 = ok, negative = APG_E* argument error, positive = hipError_t; apg_last_error() returns a
+ *     thread-local description;
+ *   - no floating-point atomics: every reduction runs in a fixed order, so results are bit-reproducible run to run;
+ *   - all tensors are dense row-major float32 unless stated.
+ */
+#ifndef AIRPOSE_GRAD_H
+#define AIRPOSE_GRAD_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define APG_OK 0
+#define APG_EINVAL (-1) /* bad argument */
+#define APG_ENOMEM (-4) /* workspace smaller than the query asked for */
+
+/* ABI number of this header: bumped whenever an exported signature changes or an entry point is added or removed.
+ * A binding built against another number must refuse to load the library (airpose_amd/_native_grad.py does). */
+#define APG_ABI_VERSION 1
+const char* apg_version(void);
+int apg_abi_version(void);
+const char* apg_last_error(void);
+
+/* ---------------------------------------------------------------------------------------------
+ * Dropout.  keep(seed, layer, row, col) <=> u >= p, u = 24-bit uniform of a counter-based hash of (seed, layer, row, col);
+ * kept values are scaled by 1 / (1 - p).  layer 1 = drop1 (after fc1), 2 = drop2 (after fc2); row = view * B + sample.
+ * p <= 0: every entry kept (the eval-mode identity).  Writes out[row][col] = keep ? 1 : 0 (uint8, rows x cols): exactly
+ * the mask the head kernels apply. */
+int apg_dropout_mask(uint64_t seed, int layer, int rows, int cols, float p, uint8_t* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * IEF regressor head, both views, R = 2B rows (view 0, then view 1).  fc1 input row (2332 columns):
+ *   xc = [xf (2048) | bb (3) | pos (3) | orient (6) | art (126) | shape (10) | partner art (126) | partner shape (10)]
+ * h1d = drop1(xc W1^T + b1), h2d = drop2(h1d W2^T + b2), delta = h2d [Wpose; Wshape]^T + [bpose; bshape],
+ * pose = [pos | orient | art] + delta[:, :135], betas = shape + delta[:, 135:].
+ *
+ * apg_head_fwd
+ *   state / state_ld: HOST arrays of 10 entries -- bb, pos, orient, art, shape of view 0, then of view 1: a device pointer
+ *     and its row stride in floats (columns contiguous; stride 0 broadcasts one row to the B samples).
+ *   xc (R x 2332), h1d (R x 1024), h2d (R x 1024): written; what apg_head_bwd reads (xc holds the snapshot of the state
+ *     columns taken here, so the caller may change its inputs in place afterwards).
+ *   pose_out / betas_out: HOST arrays of 2 device pointers (view 0, view 1), (B x 135) and (B x 10).
+ *   p1, p2: dropout probabilities of drop1 / drop2 (0 when the module is not in training mode).
+ * Matrix products on v_mfma_f32_16x16x4_f32 (exact fp32).  A sample's outputs depend only on its own row. */
+int apg_head_fwd(int B, const float* xf0, const float* xf1, const void* const* state, const int* state_ld,
+                 const float* W1, const float* b1, const float* W2, const float* b2, const float* Wpose, const float* bpose,
+                 const float* Wshape, const float* bshape, uint64_t seed, float p1, float p2,
+                 float* xc, float* h1d, float* h2d, void* const* pose_out, void* const* betas_out, void* stream);
+
+/* Workspace of apg_head_bwd in bytes; need_gxf = 1 when the gradient of xf0 / xf1 is asked for. */
+int64_t apg_head_bwd_workspace_bytes(int B, int need_gxf);
+
+/* apg_head_bwd
+ *   xc, h1d, h2d: what apg_head_fwd wrote; seed, p1, p2: the values it was given (the masks are regenerated).
+ *   g_out: HOST array of 4 device pointers -- g_pose0 (B x 135), g_betas0 (B x 10), g_pose1, g_betas1; NULL = zero.
+ *   g_param: HOST array of 8 device pointers -- gW1, gb1, gW2, gb2, gWpose, gbpose, gWshape, gbshape (each written, not
+ *     accumulated; NULL = not needed).  Every entry is reduced over the R rows in a fixed order.
+ *   g_in: HOST array of 12 device pointers -- g_xf, g_bb, g_pos, g_orient, g_art, g_shape of view 0, then of view 1,
+ *     contiguous (B x width), written; NULL = not needed.  Each collects its own view's fc1 columns, the partner's
+ *     art / shape columns (the fusion) and the identity of the residual, in that order.
+ *   workspace: at least apg_head_bwd_workspace_bytes(B, g_xf0 || g_xf1) bytes. */
+int apg_head_bwd(int B, const float* xc, const float* h1d, const float* h2d, const float* W1, const float* W2,
+                 const float* Wpose, const float* Wshape, uint64_t seed, float p1, float p2, const void* const* g_out,
+                 void* const* g_param, void* const* g_in, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Geometry adjoints (one workgroup per body for the per-body reductions, fixed order).
+ *
+ * rot6d_to_rotmat (copenet/src/copenet/utils/geometry.py:47-61, ap_rot6d_to_rotmat): x6 (n x 6), g_rotmat (n x 3 x 3)
+ *   -> g_x6 (n x 6); the clamp_min(1e-12) of F.normalize included (below it the norm is a constant). */
+int apg_rot6d_to_rotmat_bwd(const float* x6, int n, const float* g_rotmat, float* g_x6, void* stream);
+
+/* perspective_projection (geometry.py:63-91, ap_perspective_projection): pts (B x P x 3), rotation (B x 3 x 3) or NULL
+ * (identity), translation (B x 3) or NULL (zero), g_out (B x P x 2) -> g_pts (B x P x 3), g_rotation (B x 3 x 3),
+ * g_translation (B x 3), g_center (B x 2); each output NULL = not needed. */
+int apg_perspective_projection_bwd(const float* pts, int B, int P, const float* rotation, const float* translation, float fx,
+                                   float fy, const float* g_out, float* g_pts, float* g_rotation, float* g_translation,
+                                   float* g_center, void* stream);
+
+/* transform_points (ap_transform_points, X' = R X + t): rt (B x 3 x 4), pts (B x P x 3), g_out (B x P x 3)
+ *   -> g_rt (B x 3 x 4), g_pts (B x P x 3); each output NULL = not needed. */
+int apg_transform_points_bwd(const float* rt, const float* pts, int B, int P, const float* g_out, float* g_rt, float* g_pts,
+                             void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
