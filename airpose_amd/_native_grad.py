@@ -28,9 +28,22 @@ SIGNATURES = {
     "apg_rot6d_to_rotmat_bwd": (_i, [_vp, _i, _vp, _vp, _vp]),
     "apg_perspective_projection_bwd": (_i, [_vp, _i, _i, _vp, _vp, _f, _f] + [_vp] * 5 + [_vp]),
     "apg_transform_points_bwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "apg_conv_fwd": (_i, [_vp] + [_i] * 4 + [_vp] + [_i] * 5 + [_vp, _vp]),
+    "apg_conv_bwd_workspace_bytes": (_i64, [_i] * 9),
+    "apg_conv_bwd": (_i, [_vp] + [_i] * 4 + [_vp] + [_i] * 5 + [_vp] * 4 + [_i64, _vp]),
+    "apg_bn_workspace_bytes": (_i64, [_i, _i]),
+    "apg_bn_fwd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "apg_bn_bwd": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "apg_maxpool_fwd": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "apg_maxpool_bwd": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "apg_avgpool_fwd": (_i, [_vp, _i, _i, _vp, _vp]),
+    "apg_avgpool_bwd": (_i, [_vp, _i, _i, _vp, _vp]),
+    "apg_trunk_workspace_bytes": (_i64, [_i, _i]),
+    "apg_trunk_fwd": (_i, [_i, _vp, _vpp, _i, _f, _f, _vp, _i, _vp, _i64, _vp]),
+    "apg_trunk_bwd": (_i, [_i, _vpp, _i, _vp, _vpp, _vp, _vp, _i64, _vp]),
 }
 
-ABI_VERSION = 1          # include/airpose_grad.h: APG_ABI_VERSION
+ABI_VERSION = 2          # include/airpose_grad.h: APG_ABI_VERSION
 _lib = None
 _lib_lock = threading.Lock()
 

@@ -8,7 +8,8 @@ same outputs, same sub-module / buffer names, hence the same 331 ``state_dict`` 
 work unchanged.  The nn.Conv2d / nn.BatchNorm2d / nn.Linear children are parameter containers
 only: all compute goes through the C ABI of libairpose_hip.so (hand-written gfx950 kernels).
 Inference (eval) only, except the two-view IEF head: forward_ief / forward_reg are differentiable in train mode or with
-inputs that require grad (head_grad.py, libairpose_grad.so).  There is no CPU or eager fallback.
+inputs that require grad (head_grad.py, libairpose_grad.so), and, after set_trunk_trainable(True), the ResNet-50 trunk:
+forward_feat_ext and forward (trunk_grad.py).  There is no CPU or eager fallback.
 """
 import ctypes
 import threading
@@ -18,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as N
-from . import head_grad
+from . import head_grad, trunk_grad
 
 
 class Bottleneck(nn.Module):
@@ -217,6 +218,25 @@ class copenet(nn.Module):
         return self.training or (torch.is_grad_enabled() and
                                  any(isinstance(t, torch.Tensor) and t.requires_grad for t in inputs))
 
+    def set_trunk_trainable(self, on=True):
+        """Opt in (default off) to the trainable trunk (trunk_grad.py, libairpose_grad.so).  When on, forward_feat_ext and forward
+        take it in train mode (batch-statistics BatchNorm, running statistics updated as nn.BatchNorm2d does; the graph is recorded
+        when grad is enabled), and in eval mode when grad is enabled and the crops or a trunk parameter require grad (BatchNorm on
+        the running statistics).  Eval mode under no_grad keeps the inference path.  When off, nothing changes."""
+        if self.variant != 0:
+            raise RuntimeError("set_trunk_trainable: the trainable trunk serves the two-view copenet head only")
+        self._trunk_trainable = bool(on)
+        return self
+
+    def _trunk_trains(self, *xs):
+        if self.variant != 0 or not getattr(self, "_trunk_trainable", False):
+            return False
+        if self.training:
+            return True
+        return torch.is_grad_enabled() and (any(isinstance(x, torch.Tensor) and x.requires_grad for x in xs) or
+                                            any(p.requires_grad for conv, bn in trunk_grad.conv_bn_pairs(self)
+                                                for p in (conv.weight, bn.weight, bn.bias)))
+
     @staticmethod
     def _dev(x):
         if not x.is_cuda:
@@ -225,7 +245,9 @@ class copenet(nn.Module):
 
     # ------------------------------------------------------------------ reference API
     def forward_feat_ext(self, x):
-        """(n,3,224,224) -> (n,2048)   [model_copenet.py:161-176]"""
+        """(n,3,224,224) -> (n,2048)   [model_copenet.py:161-176].  Trainable after set_trunk_trainable(True): see there."""
+        if self._trunk_trains(x):
+            return trunk_grad.forward_feat_ext(self, x)
         self._check_eval()
         dev = self._dev(x)
         if x.dim() != 4 or x.shape[1:] != (3, 224, 224):
@@ -303,7 +325,15 @@ class copenet(nn.Module):
 
     def forward(self, x0, x1, bb0, bb1, init_position0, init_position1, init_theta0=None, init_theta1=None,
                 init_shape0=None, init_shape1=None, iters=3):
-        """[model_copenet.py:112-159] -> (pred_pose0 (B,135), pred_betas0 (B,10), pred_pose1, pred_betas1)."""
+        """[model_copenet.py:112-159] -> (pred_pose0 (B,135), pred_betas0 (B,10), pred_pose1, pred_betas1).  After
+        set_trunk_trainable(True), in train mode (or eval mode with grad, see there) it runs as the reference does: the trunk on
+        view 0, then on view 1 (per-view BatchNorm statistics and running-stat updates in that order), then the differentiable
+        head."""
+        if self._trunk_trains(x0, x1):
+            xf0 = self.forward_feat_ext(x0)
+            xf1 = self.forward_feat_ext(x1)
+            return head_grad.forward_ief(self, xf0, xf1, bb0, bb1, init_position0, init_position1, init_theta0, init_theta1,
+                                         init_shape0, init_shape1, iters)
         self._check_eval()
         dev = self._dev(x0)
         B = x0.shape[0]

@@ -163,7 +163,7 @@ int apg_fail(int code, const std::string& msg) {
 
 extern "C" {
 
-const char* apg_version(void) { return "airpose_grad 0.1 (gfx950; abi 1)"; }
+const char* apg_version(void) { return "airpose_grad 0.2 (gfx950; abi 2)"; }
 int apg_abi_version(void) { return APG_ABI_VERSION; }
 const char* apg_last_error(void) { return g_err.c_str(); }
 

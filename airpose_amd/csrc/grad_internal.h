@@ -1,4 +1,4 @@
-// Internal helpers shared by the sources of libairpose_grad.so (head_grad.hip, geom_grad.hip).
+// Internal helpers shared by the sources of libairpose_grad.so (head_grad.hip, geom_grad.hip, trunk_grad.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

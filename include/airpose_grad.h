@@ -1,7 +1,8 @@
 /* airpose_grad.h -- C ABI of libairpose_grad.so (gfx950 / MI355X): the gradient entry points.
  *
  * The training-side companion of libairpose_hip.so.  It holds the forward / backward of the IEF regressor head
- * (copenet.forward_reg, copenet/src/copenet/models/model_copenet.py:178-204) on live weights, and the adjoints of the
+ * (copenet.forward_reg, copenet/src/copenet/models/model_copenet.py:178-204) and of the ResNet-50 trunk
+ * (copenet.forward_feat_ext, model_copenet.py:161-176, train- or eval-mode BatchNorm) on live weights, and the adjoints of the
  * geometry helpers of the reference's training loss (copenet_twoview.py:205-317).  A library of its own, so that the
  * inference library's ABI, exports and binary stay as they are.
  *
@@ -29,7 +30,7 @@ extern "C" {
 
 /* ABI number of this header: bumped whenever an exported signature changes or an entry point is added or removed.
  * A binding built against another number must refuse to load the library (airpose_amd/_native_grad.py does). */
-#define APG_ABI_VERSION 1
+#define APG_ABI_VERSION 2
 const char* apg_version(void);
 int apg_abi_version(void);
 const char* apg_last_error(void);
@@ -94,6 +95,73 @@ int apg_perspective_projection_bwd(const float* pts, int B, int P, const float* 
  *   -> g_rt (B x 3 x 4), g_pts (B x P x 3); each output NULL = not needed. */
 int apg_transform_points_bwd(const float* rt, const float* pts, int B, int P, const float* g_out, float* g_rt, float* g_pts,
                              void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ResNet-50 trunk primitives (trunk_grad.hip), one layer per call.  Activations are NHWC fp32 (n, H, W, C); conv weights are the
+ * live OIHW fp32 parameters (K = C_out, C, R, S).  Products on v_mfma_f32_16x16x4_f32 (exact fp32), reductions in a fixed order.
+ *
+ * apg_conv_fwd: y (n, Ho, Wo, K) = conv(x, w), Ho = (H + 2 pad - R) / stride + 1 (likewise Wo). */
+int apg_conv_fwd(const float* x, int n, int H, int W, int C, const float* w, int K, int R, int S, int stride, int pad, float* y,
+                 void* stream);
+
+/* Workspace of apg_conv_bwd in bytes (the split-K partials of the weight gradient); negative for a bad geometry. */
+int64_t apg_conv_bwd_workspace_bytes(int n, int H, int W, int C, int K, int R, int S, int stride, int pad);
+
+/* apg_conv_bwd: gy (n, Ho, Wo, K), 16-byte aligned, K a multiple of 16 -> gx (n, H, W, C) and / or gw (K, C, R, S, written in OIHW);
+ * each output NULL = not needed (at least one).  gx needs w, gw needs x and the workspace. */
+int apg_conv_bwd(const float* x, int n, int H, int W, int C, const float* w, int K, int R, int S, int stride, int pad, const float* gy,
+                 float* gx, float* gw, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Workspace of apg_bn_fwd (train) / apg_bn_bwd over M = n H W rows of C channels, in bytes. */
+int64_t apg_bn_workspace_bytes(int M, int C);
+
+/* apg_bn_fwd: y = (x - mean) * invstd * gamma + beta (+ res) (ReLU when relu != 0) over x (M, C); y may alias x or res.
+ *   train != 0: mean and the biased variance of the batch (per-tile centred partials combined by Chan's formula); when
+ *     running_mean / running_var are given they are updated as nn.BatchNorm2d does: r = (1 - momentum) r + momentum * stat, with
+ *     the unbiased variance (num_batches_tracked is the caller's).  Needs the workspace.
+ *   train == 0: mean / var are running_mean / running_var (required, read only); no workspace.
+ *   save_mean, save_invstd (C): written, what apg_bn_bwd reads (invstd = 1 / sqrt(var + eps)). */
+int apg_bn_fwd(const float* x, int M, int C, const float* gamma, const float* beta, float* running_mean, float* running_var, int train,
+               float momentum, float eps, const float* res, int relu, float* y, float* save_mean, float* save_invstd, void* workspace,
+               int64_t workspace_bytes, void* stream);
+
+/* apg_bn_bwd: gy (M, C) is the gradient of apg_bn_fwd's y; y (its output) gives the ReLU mask (NULL: no ReLU); x is its input.
+ *   g = gy * (y > 0); gx = gamma invstd (g - mean(g) - xhat mean(g xhat)) (train) or gamma invstd g (eval); g_res = g (the residual's
+ *   gradient; NULL = not needed); g_gamma = sum g xhat, g_beta = sum g (NULL = not needed).  gx may alias gy.  Needs the workspace. */
+int apg_bn_bwd(const float* gy, const float* y, const float* x, int M, int C, const float* gamma, const float* save_mean,
+               const float* save_invstd, int train, float* gx, float* g_res, float* g_gamma, float* g_beta, void* workspace,
+               int64_t workspace_bytes, void* stream);
+
+/* Max-pool 3 x 3 / s2 / p1 (padding = -inf): x (n, H, W, C) -> y (n, (H-1)/2+1, (W-1)/2+1, C).  Backward: each window's gradient goes to
+ * its first maximum in row-major window order (torch's choice among ties); gx is written, not accumulated. */
+int apg_maxpool_fwd(const float* x, int n, int H, int W, int C, float* y, void* stream);
+int apg_maxpool_bwd(const float* x, int n, int H, int W, int C, const float* gy, float* gx, void* stream);
+
+/* Avg-pool 7 x 7 of a (n, 7, 7, C) map -> (n, C), and its backward gx (n, 7, 7, C) = gy / 49. */
+int apg_avgpool_fwd(const float* x, int n, int C, float* y, void* stream);
+int apg_avgpool_bwd(const float* gy, int n, int C, float* gx, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The trunk walker: the whole fixed [3, 4, 6, 3] graph, (n, 3, 224, 224) NCHW crops -> (n, 2048) features, in one call.
+ *   params: HOST table of 53 x 5 device pointers, for each conv + BN pair in state_dict order (conv1 / bn1, then per bottleneck
+ *     conv1 / bn1, conv2 / bn2, conv3 / bn3, downsample.0 / downsample.1): conv weight (OIHW), gamma, beta, running_mean, running_var.
+ *   g_params: HOST table of 53 x 3 device pointers in the same order: gW (OIHW), g_gamma, g_beta; written, not accumulated; NULL =
+ *     not needed.
+ *
+ * Workspace in bytes; save = 1: what apg_trunk_bwd reads (every conv output and BN output, per-channel mean and invstd, and the
+ * backward's own buffers): 7.0 GB at n = 64 (about 110 MB per image); save = 0: forward only (five rotating activation buffers). */
+int64_t apg_trunk_workspace_bytes(int n, int save);
+
+/* apg_trunk_fwd: train != 0: BatchNorm on batch statistics, running_mean / running_var updated in place through the table (the
+ * caller adds 1 to num_batches_tracked); train == 0: BatchNorm on the running statistics.  xf (n, 2048) written.  save = 1 keeps
+ * what apg_trunk_bwd needs in the workspace.  1 <= n <= 2048. */
+int apg_trunk_fwd(int n, const float* x, const void* const* params, int train, float momentum, float eps, float* xf, int save,
+                  void* workspace, int64_t workspace_bytes, void* stream);
+
+/* apg_trunk_bwd: after apg_trunk_fwd(save = 1) on the same workspace, n, train and parameters: g_xf (n, 2048) -> g_params and, when
+ * g_x is not NULL, the gradient of the crops g_x (n, 3, 224, 224) NCHW. */
+int apg_trunk_bwd(int n, const void* const* params, int train, const float* g_xf, void* const* g_params, float* g_x, void* workspace,
+                  int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
