@@ -474,6 +474,9 @@ struct Geom {
 
 bool geom_ok(const Geom& g) {
     if (g.n <= 0 || g.H <= 0 || g.W <= 0 || g.C <= 0 || g.K <= 0 || g.R <= 0 || g.S <= 0 || g.st <= 0 || g.pad < 0) return false;
+    // the kernel must fit the padded input: make_geom's division truncates toward zero, so at stride >= 2 a too-large kernel
+    // would otherwise come out as Ho = 1
+    if ((long long)g.H + 2LL * g.pad < g.R || (long long)g.W + 2LL * g.pad < g.S) return false;
     if (g.Ho <= 0 || g.Wo <= 0) return false;
     return (long long)g.n * g.H * g.W * g.C < (1LL << 31) && (long long)g.n * g.Ho * g.Wo * g.K < (1LL << 31) &&
            (long long)g.n * g.Ho * g.Wo < (1LL << 31);

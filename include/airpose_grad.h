@@ -100,7 +100,9 @@ int apg_transform_points_bwd(const float* rt, const float* pts, int B, int P, co
  * ResNet-50 trunk primitives (trunk_grad.hip), one layer per call.  Activations are NHWC fp32 (n, H, W, C); conv weights are the
  * live OIHW fp32 parameters (K = C_out, C, R, S).  Products on v_mfma_f32_16x16x4_f32 (exact fp32), reductions in a fixed order.
  *
- * apg_conv_fwd: y (n, Ho, Wo, K) = conv(x, w), Ho = (H + 2 pad - R) / stride + 1 (likewise Wo). */
+ * apg_conv_fwd: y (n, Ho, Wo, K) = conv(x, w), Ho = (H + 2 pad - R) / stride + 1 (likewise Wo).  The kernel must fit the
+ * padded input, H + 2 pad >= R and W + 2 pad >= S, at every stride; otherwise every conv entry point returns APG_EINVAL and the
+ * workspace query a negative size. */
 int apg_conv_fwd(const float* x, int n, int H, int W, int C, const float* w, int K, int R, int S, int stride, int pad, float* y,
                  void* stream);
 

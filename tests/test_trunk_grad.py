@@ -231,13 +231,16 @@ def test_pools_match_torch_with_exact_ties(dev):
 
 
 # ------------------------------------------------------------------------------------------------ 2. / 3. the whole trunk
-@pytest.mark.parametrize("train", [True, False], ids=["train", "eval"])
-def test_whole_trunk_matches_fp64(copenet_sd, dev, monkeypatch, train):
+# n = 1: every layer4 GEMM and BatchNorm below one tile (M = 49); n = 6: the stem's BatchNorm in the capped-tile regime (M = 75 264
+# rows > 65 536: 296-row tiles, 255 of them, the last ragged) and layer1's above 64 tiles
+@pytest.mark.parametrize("train,n", [pytest.param(True, 4, id="train"), pytest.param(False, 4, id="eval"),
+                                     pytest.param(True, 1, id="train-n1"), pytest.param(True, 6, id="train-n6")])
+def test_whole_trunk_matches_fp64(copenet_sd, dev, monkeypatch, train, n):
     from oracle import copenet_ref
     net = _net(copenet_sd, dev).train(train)
     _, bns = _trunk_keys(net)
-    x = _images(4, 21)
-    Wt = torch.randn(4, 2048, generator=torch.Generator().manual_seed(22))
+    x = _images(n, 21)
+    Wt = torch.randn(n, 2048, generator=torch.Generator().manual_seed(22))
     before = {k: v.detach().clone() for k, v in net.state_dict().items() if "running" in k or "num_batches" in k}
     xf64, sd64, x64 = _ref_trunk(monkeypatch, net, x.double(), Wt, torch.float64, train, True)
     runs32 = [_ref_trunk(monkeypatch, net, x.float(), Wt, torch.float32, train, True, cl) for cl in (False, True)]
@@ -257,14 +260,23 @@ def test_whole_trunk_matches_fp64(copenet_sd, dev, monkeypatch, train):
     # zero relative to their maximum -- inside fp32's accumulated forward error, so whether a ReLU mask entry flips against fp64
     # is chance for any fp32 order: flips in layer4.1 moved its conv1 / bn1 / bn3 gradients by 5e-5 / 1.2e-4 / 6.5e-4 while every
     # tensor before them stayed under 1e-4.  The floor is 1e-3 there; the layer primitives hold 1e-5 in eval mode on their own.
-    _check_trunk_grads(net, xg, sd64, x64, [r[1] for r in runs32], [r[2] for r in runs32], "trunk train=%s" % train,
+    _check_trunk_grads(net, xg, sd64, x64, [r[1] for r in runs32], [r[2] for r in runs32], "trunk train=%s n=%d" % (train, n),
                        1e-5 if train else 1e-3)
     after = net.state_dict()
     for p in bns:
         if train:
             for b in ("running_mean", "running_var"):
-                e = rel_err(after[p + "." + b].cpu().numpy(), sd64[p + "." + b].numpy())
-                assert e <= 1e-5, (p, b, e)
+                k = p + "." + b
+                e = rel_err(after[k].cpu().numpy(), sd64[k].numpy())
+                # n = 1: a layer4 statistic over 49 rows averages away little of the fp32 error that the 50 layers before it
+                # carry, and a correct fp32 evaluation misses 1e-5 there: torch's own fp32 CPU restatements of this batch land at
+                # 1.0e-5 (NCHW) and 1.3e-5 (the worse of the two) on layer4.2.bn1.running_var, this kernel at 1.1e-5, while the
+                # BatchNorm primitive at M = 49 holds 1e-7 on its own (test_trunk_grad_shapes.py).  At n = 1 the bar is therefore
+                # the gradients' rule, max(4 x fp32-CPU, 1e-5) (5.3e-5 on that buffer); at n = 4 and 6 the fixed 1e-5 holds.
+                bar = 1e-5 if n > 1 else max(1e-5, 4 * max(rel_err(r[1][k].detach().numpy(), sd64[k].numpy()) for r in runs32))
+                if e > 1e-5:
+                    print("%s: %.3e against the bar %.3e" % (k, e, bar))
+                assert e <= bar, (p, b, e, bar)
             assert int(after[p + ".num_batches_tracked"]) == int(before[p + ".num_batches_tracked"]) + 1
         else:
             for b in ("running_mean", "running_var", "num_batches_tracked"):

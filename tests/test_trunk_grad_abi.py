@@ -91,3 +91,32 @@ def test_workspace_queries_are_positive_and_grow_with_n():
     assert L.apg_conv_bwd_workspace_bytes(1, 8, 8, 16, 16, 3, 3, 0, 1) < 0
     b = [L.apg_bn_workspace_bytes(m, 64) for m in (49, 3136, 802816)]
     assert b[0] > 0 and b == sorted(b) and L.apg_bn_workspace_bytes(0, 64) < 0
+
+
+def test_conv_refuses_a_kernel_larger_than_the_padded_input():
+    """(H + 2 pad - R) / stride truncates toward zero, so a kernel wider than the padded input would pass as a 1 x 1 output at
+    stride >= 2 (F.conv2d refuses it).  Every conv entry point must refuse it at every stride; H + 2 pad == R stays valid."""
+    L = _lib()
+    fake = ctypes.c_void_p(4096)
+    bad = [  # (n, H, W, C, K, R, S, stride, pad)
+        (1, 2, 2, 16, 16, 3, 3, 2, 0),
+        (1, 2, 2, 16, 16, 3, 3, 1, 0),
+        (1, 4, 4, 16, 16, 7, 7, 2, 1),
+        (1, 4, 4, 16, 16, 7, 7, 3, 1),
+        (1, 8, 2, 16, 16, 3, 3, 2, 0),           # only the width is too small
+        (1, 2, 8, 16, 16, 3, 3, 2, 0),           # only the height
+        (1, 8, 2, 16, 16, 1, 5, 2, 1),           # R != S: W + 2 pad = 4 < S = 5
+    ]
+    for n, H, W, C, K, R, S, st, pad in bad:
+        geom = (n, H, W, C, K, R, S, st, pad)
+        assert L.apg_conv_bwd_workspace_bytes(*geom) < 0, geom       # first: the calls below must never reach a launch
+        assert L.apg_conv_fwd(fake, n, H, W, C, fake, K, R, S, st, pad, fake, None) == EINVAL, geom
+        assert "apg_conv_fwd" in _err(L)
+        assert L.apg_conv_bwd(fake, n, H, W, C, fake, K, R, S, st, pad, fake, fake, fake, fake, 1 << 30, None) == EINVAL, geom
+        assert "apg_conv_bwd" in _err(L)
+    # the boundary: the kernel exactly covers the padded input -> Ho = Wo = 1, valid at stride 1 and 2
+    for geom in [(1, 1, 1, 16, 16, 3, 3, 2, 1), (1, 3, 3, 16, 16, 3, 3, 2, 0), (1, 4, 4, 16, 16, 6, 6, 2, 1),
+                 (1, 3, 3, 16, 16, 3, 3, 1, 0), (2, 2, 6, 16, 16, 4, 8, 2, 1)]:
+        n, H, W, C, K, R, S, st, pad = geom
+        nb = L.apg_conv_bwd_workspace_bytes(*geom)
+        assert nb > 0 and nb % (4 * K * C * R * S) == 0, geom                # accepted: whole split-K chunks of gw
