@@ -41,7 +41,24 @@ SIGNATURES = {
     "apg_trunk_workspace_bytes": (_i64, [_i, _i]),
     "apg_trunk_fwd": (_i, [_i, _vp, _vpp, _i, _f, _f, _vp, _i, _vp, _i64, _vp]),
     "apg_trunk_bwd": (_i, [_i, _vpp, _i, _vp, _vpp, _vp, _vp, _i64, _vp]),
+    # the bf16 training mode (trunk_grad_bf16.hip)
+    "apg_trunk_precisions": (_i, []),
+    "apg_pack_weights_bf16": (_i, [_vp] + [_i] * 5 + [_vp, _vp, _vp]),
+    "apg_conv_fwd_bf16": (_i, [_vp] + [_i] * 4 + [_vp] + [_i] * 5 + [_vp, _vp]),
+    "apg_conv_bwd_bf16_workspace_bytes": (_i64, [_i] * 9),
+    "apg_conv_bwd_bf16": (_i, [_vp] + [_i] * 4 + [_vp] + [_i] * 5 + [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i64, _vp]),
+    "apg_bn_bf16_workspace_bytes": (_i64, [_i, _i]),
+    "apg_bn_fwd_bf16": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "apg_bn_bwd_bf16": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "apg_maxpool_fwd_bf16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "apg_maxpool_bwd_bf16": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "apg_avgpool_fwd_bf16": (_i, [_vp, _i, _i, _vp, _vp]),
+    "apg_avgpool_bwd_bf16": (_i, [_vp, _i, _i, _vp, _vp]),
+    "apg_trunk_workspace_bytes_p": (_i64, [_i, _i, _i]),
+    "apg_trunk_fwd_p": (_i, [_i, _i, _vp, _vpp, _i, _f, _f, _vp, _i, _vp, _i64, _vp]),
+    "apg_trunk_bwd_p": (_i, [_i, _i, _vpp, _i, _vp, _vpp, _vp, _vp, _i64, _vp]),
 }
+PRECISIONS = {"fp32": 0, "bf16": 1}          # include/airpose_grad.h: APG_PREC_*
 
 ABI_VERSION = 2          # include/airpose_grad.h: APG_ABI_VERSION
 _lib = None

@@ -218,15 +218,25 @@ class copenet(nn.Module):
         return self.training or (torch.is_grad_enabled() and
                                  any(isinstance(t, torch.Tensor) and t.requires_grad for t in inputs))
 
-    def set_trunk_trainable(self, on=True):
+    def set_trunk_trainable(self, on=True, precision="fp32"):
         """Opt in (default off) to the trainable trunk (trunk_grad.py, libairpose_grad.so).  When on, forward_feat_ext and forward
         take it in train mode (batch-statistics BatchNorm, running statistics updated as nn.BatchNorm2d does; the graph is recorded
         when grad is enabled), and in eval mode when grad is enabled and the crops or a trunk parameter require grad (BatchNorm on
-        the running statistics).  Eval mode under no_grad keeps the inference path.  When off, nothing changes."""
+        the running statistics).  Eval mode under no_grad keeps the inference path.  When off, nothing changes.
+        precision: "fp32" (the default: fp32 storage and products) or "bf16" (mixed precision: bf16 activations and products,
+        fp32 accumulation, statistics, master weights and gradients; trunk_grad.py).  A runtime switch, not part of state_dict."""
         if self.variant != 0:
             raise RuntimeError("set_trunk_trainable: the trainable trunk serves the two-view copenet head only")
+        if precision not in ("fp32", "bf16"):
+            raise RuntimeError("set_trunk_trainable: precision is \"fp32\" or \"bf16\", got %r" % (precision,))
         self._trunk_trainable = bool(on)
+        self._trunk_precision = precision
         return self
+
+    @property
+    def trunk_precision(self):
+        """The arithmetic of the trainable trunk: "fp32" or "bf16" (set_trunk_trainable)."""
+        return getattr(self, "_trunk_precision", "fp32")
 
     def _trunk_trains(self, *xs):
         if self.variant != 0 or not getattr(self, "_trunk_trainable", False):
@@ -247,7 +257,9 @@ class copenet(nn.Module):
     def forward_feat_ext(self, x):
         """(n,3,224,224) -> (n,2048)   [model_copenet.py:161-176].  Trainable after set_trunk_trainable(True): see there."""
         if self._trunk_trains(x):
-            return trunk_grad.forward_feat_ext(self, x)
+            if self.trunk_precision == "fp32":
+                return trunk_grad.forward_feat_ext(self, x)
+            return trunk_grad.forward_feat_ext(self, x, self.trunk_precision)
         self._check_eval()
         dev = self._dev(x)
         if x.dim() != 4 or x.shape[1:] != (3, 224, 224):

@@ -1,0 +1,943 @@
+// Mixed-precision (bf16) training mode of the ResNet-50 trunk for gfx950 (libairpose_grad.so): the graph of trunk_grad.hip with bf16
+// NHWC activations and activation gradients, bf16 x bf16 products accumulated in fp32 on v_mfma_f32_16x16x32_bf16, fp32 master
+// weights (a bf16 copy is packed into the workspace on every forward call), fp32 BatchNorm statistics, fp32 parameter gradients.
+// The storage and rounding rules are the table of DESIGN 4.3.4; every rounding is one round-to-nearest-even at a store.
+//   convolution:  bconv_kernel<MODE, BM, BN>, an implicit GEMM with both operands k-contiguous in LDS (row pitch 72 bf16, so the
+//                 ds_read_b128 fragment reads of 16 rows fall on 16 distinct 16-byte bank slots), K in stages of 64 (two 16x16x32
+//                 steps per fragment pair), two LDS stages: the next stage's 16-byte global loads are issued before the current
+//                 stage's MFMAs and land in LDS after them, one barrier per stage.  256 threads = 2 x 2 waves; tiles 128 x 128
+//                 (16 accumulator fragments per wave, 32 MFMAs between barriers) and 64 x 64.
+//                   CV_FWD    M = n Ho Wo, N = C_out, K = (r, s, c_in):  A = x NHWC, B = weights packed [co][r][s][c]
+//                   CV_DGRAD  M = n H W,   N = C_in,  K = (r, s, c_out): A = gy NHWC gathered with the per-tap validity test,
+//                             B = weights packed [c][r][s][co]
+//                   CV_WGRAD  M = C_out,   N = (r, s, c_in), K = n Ho Wo in fixed split-K chunks: neither operand is k-contiguous
+//                             in NHWC, so both are transposed on the way into LDS: a thread loads 8 channels of two consecutive
+//                             pixels (two 16-byte loads) and writes 8 dwords, each one channel's pixel pair
+//   BatchNorm:    the kernels of trunk_grad.hip on bf16 storage: same tiles (bn_tile_rows / bn_tiles), same per-channel order and
+//                 trees, fp32 math; the element-wise passes move 8 bf16 (16 bytes) per thread
+//   pools, layout: bf16 storage, 8 channels per thread; the crops are cast into an 8-channel NHWC image (channels 3 .. 7 zero)
+// No floating-point atomics: every reduction runs in a fixed order, so results are bit-reproducible run to run.
+#include "ap_common.h"
+#include "grad_internal.h"
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+namespace {
+
+enum { CV_FWD = 0, CV_DGRAD = 1, CV_WGRAD = 2 };
+constexpr int LP = 72;                   // LDS row pitch in bf16: 64 k + 8 (144 bytes)
+
+struct BArgs {
+    const bf16_t* a;                     // CV_FWD: x (n, H, W, C); CV_DGRAD / CV_WGRAD: gy (n, Ho, Wo, K)
+    const bf16_t* b;                     // CV_FWD: wf [K][R S C]; CV_DGRAD: wd [C][R S K]; CV_WGRAD: x (n, H, W, C)
+    void* out;                           // CV_FWD: y bf16; CV_DGRAD: gx bf16 (or fp32 when out_f32); CV_WGRAD: fp32 chunk partials
+    const void* add;                     // CV_DGRAD: out = acc + add (same index, fp32 add, one rounding; bf16, may alias out;
+                                         // fp32 when add_f32)
+    int n, H, W, C, K, R, S, st, pad, Ho, Wo;
+    int M, N, KK;
+    int kchunk;                          // CV_WGRAD: pixels per chunk (a multiple of 64)
+    int out_f32, add_f32;
+};
+
+__device__ __forceinline__ uint32_t half_of(const u32x4& v, int j) { return (v[j >> 1] >> (16 * (j & 1))) & 0xffffu; }
+
+template <int MODE, int BM, int BN>
+__global__ void __launch_bounds__(256) bconv_kernel(const BArgs a) {
+    __shared__ __attribute__((aligned(16))) bf16_t As[2][BM * LP];
+    __shared__ __attribute__((aligned(16))) bf16_t Bs[2][BN * LP];
+    constexpr int VA = BM / 32, VB = BN / 32;                   // 16-byte global loads per thread and stage
+    constexpr int MI = BM / 32, NI = BN / 32;                   // 16 x 16 fragments per wave
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;       // M tiles on x: n H W / 64 can pass 65535
+    const int wm = (wv >> 1) * (BM / 2), wn = (wv & 1) * (BN / 2);
+    const int i16 = lane & 15, q = lane >> 4;
+    int kbeg = 0, kend = a.KK;
+    if (MODE == CV_WGRAD) {
+        kbeg = blockIdx.z * a.kchunk;
+        kend = min(kbeg + a.kchunk, a.KK);
+    }
+    // CV_FWD / CV_DGRAD: thread t stages rows t / 8 + 32 i of both tiles, 8 k at 8 (t % 8); the rows' pixels are fixed
+    // CV_WGRAD: thread t stages the pixel pair t % 32 of the channel groups (8 channels) t / 32 + 8 i
+    const int kv = t & 7, lr = t >> 3, pp = t & 31, cg = t >> 5;
+    int pb[VA], ph[VA], pw[VA];                                 // CV_FWD / CV_DGRAD: image (-1: row outside M), h / w base
+    int br[VB], bs[VB], bc[VB];                                 // CV_WGRAD: tap and first channel of the B column group (br -1: outside N)
+    if (MODE == CV_FWD || MODE == CV_DGRAD) {
+        const int hw = MODE == CV_FWD ? a.Ho * a.Wo : a.H * a.W, wd = MODE == CV_FWD ? a.Wo : a.W;
+#pragma unroll
+        for (int i = 0; i < VA; ++i) {
+            const int m = m0 + lr + 32 * i;
+            pb[i] = -1; ph[i] = 0; pw[i] = 0;
+            if (m < a.M) {
+                const int b = m / hw, rem = m - b * hw, y = rem / wd, x = rem - y * wd;
+                pb[i] = b;
+                ph[i] = MODE == CV_FWD ? y * a.st - a.pad : y + a.pad;
+                pw[i] = MODE == CV_FWD ? x * a.st - a.pad : x + a.pad;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < VB / 2; ++i) {
+            const int col = n0 + (cg + 8 * i) * 8;
+            br[i] = -1; bs[i] = 0; bc[i] = 0;
+            if (col < a.N) {
+                const int tap = col / a.C;
+                bc[i] = col - tap * a.C;
+                br[i] = tap / a.S;
+                bs[i] = tap - br[i] * a.S;
+            }
+        }
+    }
+    u32x4 ra[VA], rb[VB];
+    const u32x4 zero4 = {0u, 0u, 0u, 0u};
+
+    auto load = [&](int k0) {
+        if (MODE == CV_FWD || MODE == CV_DGRAD) {
+            const int gk = k0 + kv * 8;
+            const bool kok = gk < kend;
+            int r = 0, s = 0, c = 0;
+            if (kok) {
+                const int ch = MODE == CV_FWD ? a.C : a.K, tap = gk / ch;
+                c = gk - tap * ch;
+                r = tap / a.S;
+                s = tap - r * a.S;
+            }
+#pragma unroll
+            for (int i = 0; i < VA; ++i) {
+                ra[i] = zero4;
+                if (!kok || pb[i] < 0) continue;
+                if (MODE == CV_FWD) {
+                    const int h = ph[i] + r, w = pw[i] + s;
+                    if (h >= 0 && h < a.H && w >= 0 && w < a.W)
+                        ra[i] = *(const u32x4*)(a.a + (((long long)pb[i] * a.H + h) * a.W + w) * a.C + c);
+                } else {
+                    const int th = ph[i] - r, tw = pw[i] - s;
+                    if (th >= 0 && tw >= 0 && th % a.st == 0 && tw % a.st == 0) {
+                        const int ho = th / a.st, wo = tw / a.st;
+                        if (ho < a.Ho && wo < a.Wo)
+                            ra[i] = *(const u32x4*)(a.a + (((long long)pb[i] * a.Ho + ho) * a.Wo + wo) * a.K + c);
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < VB; ++i) {
+                const int nr = n0 + lr + 32 * i;
+                rb[i] = zero4;
+                if (kok && nr < a.N) rb[i] = *(const u32x4*)(a.b + (long long)nr * a.KK + gk);
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int pix = k0 + 2 * pp + e;
+                const bool ok = pix < kend;
+                int b = 0, h0 = 0, w0 = 0;
+                if (ok) {
+                    const int hw = a.Ho * a.Wo;
+                    b = pix / hw;
+                    const int rem = pix - b * hw, ho = rem / a.Wo, wo = rem - ho * a.Wo;
+                    h0 = ho * a.st - a.pad;
+                    w0 = wo * a.st - a.pad;
+                }
+#pragma unroll
+                for (int i = 0; i < VA / 2; ++i) {               // A(co, pix) = gy[pix][co]
+                    const int co = m0 + (cg + 8 * i) * 8;
+                    ra[2 * i + e] = zero4;
+                    if (ok && co < a.M) ra[2 * i + e] = *(const u32x4*)(a.a + (long long)pix * a.K + co);
+                }
+#pragma unroll
+                for (int i = 0; i < VB / 2; ++i) {               // B((r, s, c), pix) = x[b][ho st - pad + r][wo st - pad + s][c]
+                    rb[2 * i + e] = zero4;
+                    if (!ok || br[i] < 0) continue;
+                    const int h = h0 + br[i], w = w0 + bs[i];
+                    if (h >= 0 && h < a.H && w >= 0 && w < a.W)
+                        rb[2 * i + e] = *(const u32x4*)(a.b + (((long long)b * a.H + h) * a.W + w) * a.C + bc[i]);
+                }
+            }
+        }
+    };
+    auto store = [&](int buf) {
+        if (MODE == CV_FWD || MODE == CV_DGRAD) {
+#pragma unroll
+            for (int i = 0; i < VA; ++i) *(u32x4*)&As[buf][(lr + 32 * i) * LP + kv * 8] = ra[i];
+#pragma unroll
+            for (int i = 0; i < VB; ++i) *(u32x4*)&Bs[buf][(lr + 32 * i) * LP + kv * 8] = rb[i];
+        } else {                                                 // the transpose: row = channel, two consecutive pixels per dword
+#pragma unroll
+            for (int i = 0; i < VA / 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    *(uint32_t*)&As[buf][((cg + 8 * i) * 8 + j) * LP + 2 * pp] = half_of(ra[2 * i], j) | (half_of(ra[2 * i + 1], j) << 16);
+#pragma unroll
+            for (int i = 0; i < VB / 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    *(uint32_t*)&Bs[buf][((cg + 8 * i) * 8 + j) * LP + 2 * pp] = half_of(rb[2 * i], j) | (half_of(rb[2 * i + 1], j) << 16);
+        }
+    };
+
+    f32x4 acc[MI][NI];
+#pragma unroll
+    for (int x = 0; x < MI; ++x)
+#pragma unroll
+        for (int y = 0; y < NI; ++y) acc[x][y] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (kbeg < kend) {
+        load(kbeg);
+        store(0);
+    }
+    __syncthreads();
+    int buf = 0;
+    for (int k0 = kbeg; k0 < kend; k0 += 64, buf ^= 1) {
+        const bool more = k0 + 64 < kend;
+        if (more) load(k0 + 64);                                 // in flight under this stage's MFMAs
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            // 16x16x32 operand maps: A[row l & 15][k = 8 (l >> 4) + j], B[k = 8 (l >> 4) + j][col l & 15]
+            bf16x8 fa[MI], fb[NI];
+#pragma unroll
+            for (int x = 0; x < MI; ++x) fa[x] = *(const bf16x8*)&As[buf][(wm + 16 * x + i16) * LP + ks * 32 + 8 * q];
+#pragma unroll
+            for (int y = 0; y < NI; ++y) fb[y] = *(const bf16x8*)&Bs[buf][(wn + 16 * y + i16) * LP + ks * 32 + 8 * q];
+#pragma unroll
+            for (int x = 0; x < MI; ++x)
+#pragma unroll
+                for (int y = 0; y < NI; ++y) acc[x][y] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[x], fb[y], acc[x][y], 0, 0, 0);
+        }
+        if (more) store(buf ^ 1);                                // the other stage: last read before the previous barrier
+        __syncthreads();
+    }
+    // C/D map: col = l & 15, row = 4 (l >> 4) + reg
+#pragma unroll
+    for (int x = 0; x < MI; ++x)
+#pragma unroll
+        for (int y = 0; y < NI; ++y)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int row = m0 + wm + 16 * x + 4 * q + e, col = n0 + wn + 16 * y + i16;
+                if (row >= a.M || col >= a.N) continue;
+                const long long o = (long long)row * a.N + col;
+                float v = acc[x][y][e];
+                if (MODE == CV_WGRAD) {
+                    ((float*)a.out)[(long long)blockIdx.z * a.M * a.N + o] = v;
+                } else {
+                    if (MODE == CV_DGRAD && a.add) v = (a.add_f32 ? ((const float*)a.add)[o] : bf16_to_f32(((const bf16_t*)a.add)[o])) + v;
+                    if (MODE == CV_DGRAD && a.out_f32) ((float*)a.out)[o] = v;
+                    else ((bf16_t*)a.out)[o] = f32_to_bf16(v);
+                }
+            }
+}
+
+// gW[co][c][r][s] (c < C) = sum over the chunks, in chunk order, of part[chunk][co][(r S + s) Cp + c]
+__global__ void __launch_bounds__(256) bwgrad_combine_kernel(const float* __restrict__ part, int nch, int K, int C, int Cp, int R, int S,
+                                                             float* __restrict__ gw) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, per = (long long)C * R * S, perp = (long long)Cp * R * S;
+    if (idx >= (long long)K * per) return;
+    const int co = (int)(idx / per), rem = (int)(idx - co * per);
+    const int c = rem / (R * S), rs = rem - c * R * S;
+    const long long src = (long long)co * perp + (long long)rs * Cp + c, stride = (long long)K * perp;
+    float s = 0.f;
+    for (int ch = 0; ch < nch; ++ch) s += part[ch * stride + src];
+    gw[idx] = s;
+}
+
+// fp32 OIHW master weights -> bf16 (RNE), channels padded with zeros to Cp: wf[co][r][s][c] and / or wd[c][r][s][co]
+__global__ void __launch_bounds__(256) pack_weights_kernel(const float* __restrict__ w, int K, int C, int Cp, int R, int S,
+                                                           bf16_t* __restrict__ wf, bf16_t* __restrict__ wd) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)K * R * S * Cp) return;
+    const int c = (int)(idx % Cp);
+    const long long p = idx / Cp;
+    const int rs = (int)(p % (R * S)), co = (int)(p / (R * S));
+    const bf16_t v = c < C ? f32_to_bf16(w[((long long)co * C + c) * R * S + rs]) : (bf16_t)0;
+    if (wf) wf[idx] = v;
+    if (wd) wd[((long long)c * R * S + rs) * K + co] = v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- 8 bf16 at a time
+struct F8 {
+    float v[8];
+};
+__device__ __forceinline__ F8 ld8(const bf16_t* p) {
+    const u32x4 u = *(const u32x4*)p;
+    F8 f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) unpack_bf16x2(u[j], f.v[2 * j], f.v[2 * j + 1]);
+    return f;
+}
+__device__ __forceinline__ void st8(bf16_t* p, const F8& f) {
+    u32x4 u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) u[j] = pack_bf16x2(f.v[2 * j], f.v[2 * j + 1]);
+    *(u32x4*)p = u;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- BatchNorm
+// The tiling and the per-channel order of trunk_grad.hip: rows in tiles of `tr` (tr % 4 == 0, at most 256 tiles), a workgroup takes
+// 64 channels x one tile, its 4 waves a quarter of the tile each.
+#include "bn_common.inc"
+
+__global__ void __launch_bounds__(256) bbn_stats_part_kernel(const bf16_t* __restrict__ x, int M, int C, int tr, float* __restrict__ part) {
+    __shared__ float sh[4][64];
+    __shared__ float smean[64];
+    const int t = threadIdx.x, cl = t & 63, g = t >> 6, c = blockIdx.x * 64 + cl, tile = blockIdx.y;
+    const int t0 = tile * tr, tcnt = min(tr, M - t0), r0 = t0 + g * (tr / 4), r1 = min(r0 + tr / 4, M);
+    float s = 0.f;
+    if (c < C)
+        for (int r = r0; r < r1; ++r) s += bf16_to_f32(x[(long long)r * C + c]);
+    sh[g][cl] = s;
+    __syncthreads();
+    if (g == 0) smean[cl] = (((sh[0][cl] + sh[1][cl]) + sh[2][cl]) + sh[3][cl]) / (float)tcnt;
+    __syncthreads();
+    const float mean = smean[cl];
+    float m2 = 0.f;
+    if (c < C)
+        for (int r = r0; r < r1; ++r) {
+            const float d = bf16_to_f32(x[(long long)r * C + c]) - mean;
+            m2 += d * d;
+        }
+    sh[g][cl] = m2;
+    __syncthreads();
+    if (g == 0 && c < C) {
+        part[((long long)tile * 3 + 0) * C + c] = (float)tcnt;
+        part[((long long)tile * 3 + 1) * C + c] = mean;
+        part[((long long)tile * 3 + 2) * C + c] = ((sh[0][cl] + sh[1][cl]) + sh[2][cl]) + sh[3][cl];
+    }
+}
+
+// y = (x - mean) invstd gamma + beta (+ res) (ReLU) on 8 channels per thread (C % 8 == 0); y may alias x or res
+__global__ void __launch_bounds__(256) bbn_apply_kernel(const bf16_t* x, long long groups, int C, const float* __restrict__ mean,
+                                                        const float* __restrict__ invstd, const float* __restrict__ gamma,
+                                                        const float* __restrict__ beta, const bf16_t* res, int relu, bf16_t* y) {
+    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gi >= groups) return;
+    const long long idx = gi * 8;
+    const int c = (int)(idx % C);
+    F8 v = ld8(x + idx), r;
+    if (res) r = ld8(res + idx);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float f = (v.v[j] - mean[c + j]) * invstd[c + j] * gamma[c + j] + beta[c + j];
+        if (res) f += r.v[j];
+        if (relu) f = fmaxf(f, 0.f);
+        v.v[j] = f;
+    }
+    st8(y + idx, v);
+}
+
+__global__ void __launch_bounds__(256) bbn_bwd_part_kernel(const bf16_t* __restrict__ gy, const bf16_t* __restrict__ y,
+                                                           const bf16_t* __restrict__ x, int M, int C, int tr, const float* __restrict__ mean,
+                                                           const float* __restrict__ invstd, float* __restrict__ part) {
+    __shared__ float s1[4][64], s2[4][64];
+    const int t = threadIdx.x, cl = t & 63, g = t >> 6, c = blockIdx.x * 64 + cl, tile = blockIdx.y;
+    const int r0 = tile * tr + g * (tr / 4), r1 = min(r0 + tr / 4, M);
+    float a = 0.f, b = 0.f;
+    if (c < C) {
+        const float mu = mean[c], is = invstd[c];
+        for (int r = r0; r < r1; ++r) {
+            const long long o = (long long)r * C + c;
+            float gv = bf16_to_f32(gy[o]);
+            if (y && !(bf16_to_f32(y[o]) > 0.f)) gv = 0.f;
+            a += gv;
+            b += gv * ((bf16_to_f32(x[o]) - mu) * is);
+        }
+    }
+    s1[g][cl] = a;
+    s2[g][cl] = b;
+    __syncthreads();
+    if (g == 0 && c < C) {
+        part[((long long)tile * 2 + 0) * C + c] = ((s1[0][cl] + s1[1][cl]) + s1[2][cl]) + s1[3][cl];
+        part[((long long)tile * 2 + 1) * C + c] = ((s2[0][cl] + s2[1][cl]) + s2[2][cl]) + s2[3][cl];
+    }
+}
+
+// gx = gamma invstd (g - sum g / M - xhat sum(g xhat) / M) (train) or gamma invstd g (eval); g_res = g.  gx may alias gy.
+__global__ void __launch_bounds__(256) bbn_bwd_apply_kernel(const bf16_t* gy, const bf16_t* __restrict__ y, const bf16_t* __restrict__ x,
+                                                            long long groups, int C, float inv_m, int train, const float* __restrict__ mean,
+                                                            const float* __restrict__ invstd, const float* __restrict__ gamma,
+                                                            const float* __restrict__ sums, bf16_t* gx, bf16_t* g_res) {
+    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gi >= groups) return;
+    const long long idx = gi * 8;
+    const int c = (int)(idx % C);
+    F8 g = ld8(gy + idx), xv = ld8(x + idx), o;
+    if (y) {
+        const F8 yv = ld8(y + idx);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (!(yv.v[j] > 0.f)) g.v[j] = 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float k = gamma[c + j] * invstd[c + j];
+        if (train) {
+            const float xhat = (xv.v[j] - mean[c + j]) * invstd[c + j];
+            o.v[j] = k * ((g.v[j] - sums[c + j] * inv_m) - xhat * (sums[C + c + j] * inv_m));
+        } else {
+            o.v[j] = k * g.v[j];
+        }
+    }
+    if (g_res) st8(g_res + idx, g);                              // exact: g is gy or 0
+    st8(gx + idx, o);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- pools, layout
+// max-pool 3 x 3 / s2 / p1 on 8 channels per thread: padding is -inf; the first maximum in row-major window order is the argmax
+__device__ __forceinline__ void maxpool_arg8(const bf16_t* __restrict__ x, int b, int ho, int wo, int c, int H, int W, int C, float* best,
+                                             int* arg) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { best[j] = -INFINITY; arg[j] = -1; }
+    for (int r = 0; r < 3; ++r) {
+        const int h = ho * 2 - 1 + r;
+        if (h < 0 || h >= H) continue;
+        for (int s = 0; s < 3; ++s) {
+            const int w = wo * 2 - 1 + s;
+            if (w < 0 || w >= W) continue;
+            const F8 v = ld8(x + (((long long)b * H + h) * W + w) * C + c);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (arg[j] < 0 || v.v[j] > best[j] || v.v[j] != v.v[j]) { best[j] = v.v[j]; arg[j] = h * W + w; }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) bmaxpool_fwd_kernel(const bf16_t* __restrict__ x, int n, int H, int W, int C, int Ho, int Wo,
+                                                           bf16_t* __restrict__ y) {
+    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x, idx = gi * 8;
+    if (idx >= (long long)n * Ho * Wo * C) return;
+    const int c = (int)(idx % C);
+    const long long p = idx / C;
+    const int wo = (int)(p % Wo), ho = (int)((p / Wo) % Ho), b = (int)(p / ((long long)Wo * Ho));
+    F8 m;
+    int arg[8];
+    maxpool_arg8(x, b, ho, wo, c, H, W, C, m.v, arg);
+    st8(y + idx, m);                                             // a selection: exact
+}
+
+__global__ void __launch_bounds__(256) bmaxpool_bwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ gy, int n, int H, int W,
+                                                           int C, int Ho, int Wo, bf16_t* __restrict__ gx) {
+    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x, idx = gi * 8;
+    if (idx >= (long long)n * H * W * C) return;
+    const int c = (int)(idx % C);
+    const long long p = idx / C;
+    const int w = (int)(p % W), h = (int)((p / W) % H), b = (int)(p / ((long long)W * H));
+    F8 s;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s.v[j] = 0.f;
+    const int me = h * W + w;
+    for (int ho = max(0, h / 2 - 1); ho <= min(Ho - 1, (h + 1) / 2); ++ho) {
+        if (h < ho * 2 - 1 || h > ho * 2 + 1) continue;
+        for (int wo = max(0, w / 2 - 1); wo <= min(Wo - 1, (w + 1) / 2); ++wo) {
+            if (w < wo * 2 - 1 || w > wo * 2 + 1) continue;
+            float m[8];
+            int arg[8];
+            maxpool_arg8(x, b, ho, wo, c, H, W, C, m, arg);
+            const F8 g = ld8(gy + (((long long)b * Ho + ho) * Wo + wo) * C + c);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (arg[j] == me) s.v[j] += g.v[j];
+        }
+    }
+    st8(gx + idx, s);
+}
+
+// avg-pool 7 x 7 over a bf16 (n, 7, 7, C) map -> fp32 (n, C): the 49 pixels summed in row-major order in fp32, / 49
+__global__ void __launch_bounds__(256) bavgpool_fwd_kernel(const bf16_t* __restrict__ x, int n, int C, float* __restrict__ y) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)n * C) return;
+    const int c = (int)(idx % C), b = (int)(idx / C);
+    float s = 0.f;
+    for (int p = 0; p < 49; ++p) s += bf16_to_f32(x[((long long)b * 49 + p) * C + c]);
+    y[idx] = s / 49.f;
+}
+
+__global__ void __launch_bounds__(256) bavgpool_bwd_kernel(const float* __restrict__ gy, int n, int C, bf16_t* __restrict__ gx) {
+    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x, idx = gi * 8;
+    if (idx >= (long long)n * 49 * C) return;
+    const int c = (int)(idx % C), b = (int)(idx / (49LL * C));
+    F8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o.v[j] = gy[(long long)b * C + c + j] / 49.f;
+    st8(gx + idx, o);
+}
+
+// fp32 NCHW (n, C, HW) -> bf16 NHWC with 8 channels per pixel (C <= 8; channels C .. 7 zero), RNE
+__global__ void __launch_bounds__(256) nchw_to_nhwc8_kernel(const float* __restrict__ x, int n, int C, int HW, bf16_t* __restrict__ y) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)n * HW) return;
+    const int hw = (int)(idx % HW), b = (int)(idx / HW);
+    F8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o.v[j] = j < C ? x[((long long)b * C + j) * HW + hw] : 0.f;
+    st8(y + idx * 8, o);
+}
+
+// fp32 NHWC with 8 channels per pixel -> fp32 NCHW (n, C, HW), the first C channels
+__global__ void __launch_bounds__(256) nhwc8_to_nchw_kernel(const float* __restrict__ x, int n, int C, int HW, float* __restrict__ y) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)n * C * HW) return;
+    const int hw = (int)(idx % HW);
+    const long long p = idx / HW;
+    const int c = (int)(p % C), b = (int)(p / C);
+    y[idx] = x[((long long)b * HW + hw) * 8 + c];
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host side
+size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+unsigned nblk(long long total) { return (unsigned)((total + 255) / 256); }
+bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+struct Geom {
+    int n, H, W, C, K, R, S, st, pad, Ho, Wo;                   // C: the channel count of x as stored (a multiple of 8)
+};
+
+bool geom_ok(const Geom& g) {
+    if (g.n <= 0 || g.H <= 0 || g.W <= 0 || g.C <= 0 || g.K <= 0 || g.R <= 0 || g.S <= 0 || g.st <= 0 || g.pad < 0) return false;
+    if ((long long)g.H + 2LL * g.pad < g.R || (long long)g.W + 2LL * g.pad < g.S) return false;
+    if (g.Ho <= 0 || g.Wo <= 0) return false;
+    if (g.C % 8 != 0 || g.K % 8 != 0) return false;             // a 16-byte load holds 8 channels of one pixel / tap
+    return (long long)g.n * g.H * g.W * g.C < (1LL << 31) && (long long)g.n * g.Ho * g.Wo * g.K < (1LL << 31) &&
+           (long long)g.n * g.Ho * g.Wo < (1LL << 31) && (long long)g.R * g.S * g.C * g.K < (1LL << 31);
+}
+
+Geom make_geom(int n, int H, int W, int C, int K, int R, int S, int st, int pad) {
+    Geom g{n, H, W, C, K, R, S, st, pad, 0, 0};
+    if (st > 0) {
+        g.Ho = (H + 2 * pad - R) / st + 1;
+        g.Wo = (W + 2 * pad - S) / st + 1;
+    }
+    return g;
+}
+
+BArgs conv_args(const Geom& g) {
+    BArgs a = {};
+    a.n = g.n; a.H = g.H; a.W = g.W; a.C = g.C; a.K = g.K; a.R = g.R; a.S = g.S; a.st = g.st; a.pad = g.pad; a.Ho = g.Ho; a.Wo = g.Wo;
+    return a;
+}
+
+// the 128 x 128 tile where it fills the part (256 CUs) and both sides reach it, else 64 x 64
+bool big_tile(int M, int N) { return N >= 128 && M >= 128 && (long long)((M + 127) / 128) * ((N + 127) / 128) >= 256; }
+bool wgrad_big(const Geom& g) { return g.K >= 128 && g.R * g.S * g.C >= 128; }
+
+// split-K of the weight gradient: enough chunks for ~1024 workgroups of 64 x 64 (512 of 128 x 128), chunks of at least 512 pixels
+// (a multiple of 64, one K stage)
+void wgrad_split(const Geom& g, int* nch, int* chunk) {
+    const int M = g.K, N = g.R * g.S * g.C, KK = g.n * g.Ho * g.Wo, T = wgrad_big(g) ? 128 : 64;
+    const int tiles = ((M + T - 1) / T) * ((N + T - 1) / T), want = T == 128 ? 512 : 1024;
+    const int s = std::max(1, std::min((want + tiles - 1) / tiles, (KK + 511) / 512));
+    int ch = (KK + s - 1) / s;
+    ch = (ch + 63) & ~63;
+    *chunk = ch;
+    *nch = (KK + ch - 1) / ch;
+}
+
+size_t wgrad_floats(const Geom& g) {
+    int nch, chunk;
+    wgrad_split(g, &nch, &chunk);
+    return (size_t)nch * g.K * g.R * g.S * g.C;
+}
+
+template <int MODE>
+void launch_conv(const BArgs& a, int nz, bool big, hipStream_t st) {
+    if (big) hipLaunchKernelGGL((bconv_kernel<MODE, 128, 128>), dim3((a.M + 127) / 128, (a.N + 127) / 128, nz), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((bconv_kernel<MODE, 64, 64>), dim3((a.M + 63) / 64, (a.N + 63) / 64, nz), dim3(256), 0, st, a);
+}
+
+hipError_t conv_fwd(const Geom& g, const bf16_t* x, const bf16_t* wf, bf16_t* y, hipStream_t st) {
+    BArgs a = conv_args(g);
+    a.a = x; a.b = wf; a.out = y;
+    a.M = g.n * g.Ho * g.Wo; a.N = g.K; a.KK = g.R * g.S * g.C;
+    launch_conv<CV_FWD>(a, 1, big_tile(a.M, a.N), st);
+    return hipGetLastError();
+}
+
+hipError_t conv_dgrad(const Geom& g, const bf16_t* gy, const bf16_t* wd, const void* add, int add_f32, void* gx, int out_f32,
+                      hipStream_t st) {
+    BArgs a = conv_args(g);
+    a.a = gy; a.b = wd; a.out = gx; a.add = add; a.add_f32 = add_f32; a.out_f32 = out_f32;
+    a.M = g.n * g.H * g.W; a.N = g.C; a.KK = g.R * g.S * g.K;
+    launch_conv<CV_DGRAD>(a, 1, big_tile(a.M, a.N), st);
+    return hipGetLastError();
+}
+
+// gw (OIHW fp32, c_real <= C input channels) through `part` (wgrad_floats(g) floats)
+hipError_t conv_wgrad(const Geom& g, const bf16_t* x, const bf16_t* gy, float* part, float* gw, int c_real, hipStream_t st) {
+    BArgs a = conv_args(g);
+    a.a = gy; a.b = x; a.out = part;
+    a.M = g.K; a.N = g.R * g.S * g.C; a.KK = g.n * g.Ho * g.Wo;
+    int nch;
+    wgrad_split(g, &nch, &a.kchunk);
+    launch_conv<CV_WGRAD>(a, nch, wgrad_big(g), st);
+    const long long tot = (long long)g.K * c_real * g.R * g.S;
+    hipLaunchKernelGGL(bwgrad_combine_kernel, dim3(nblk(tot)), dim3(256), 0, st, part, nch, g.K, c_real, g.C, g.R, g.S, gw);
+    return hipGetLastError();
+}
+
+void pack_weights(const float* w, int K, int C, int Cp, int R, int S, bf16_t* wf, bf16_t* wd, hipStream_t st) {
+    hipLaunchKernelGGL(pack_weights_kernel, dim3(nblk((long long)K * R * S * Cp)), dim3(256), 0, st, w, K, C, Cp, R, S, wf, wd);
+}
+
+size_t bn_part_floats(int M, int C) { return (size_t)bn_tiles(M) * 3 * C + 2 * (size_t)C; }
+
+hipError_t bn_fwd(const bf16_t* x, int M, int C, const float* gamma, const float* beta, float* rm, float* rv, int train, float momentum,
+                  float eps, const bf16_t* res, int relu, bf16_t* y, float* mean, float* invstd, float* part, hipStream_t st) {
+    if (train) {
+        const int tr = bn_tile_rows(M), nt = bn_tiles(M);
+        hipLaunchKernelGGL(bbn_stats_part_kernel, dim3((C + 63) / 64, nt), dim3(256), 0, st, x, M, C, tr, part);
+        hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C), dim3(64), 0, st, part, nt, C, momentum, eps, rm, rv, mean, invstd);
+    } else {
+        hipLaunchKernelGGL(bn_eval_stats_kernel, dim3((C + 255) / 256), dim3(256), 0, st, rm, rv, C, eps, mean, invstd);
+    }
+    const long long groups = (long long)M * C / 8;
+    hipLaunchKernelGGL(bbn_apply_kernel, dim3(nblk(groups)), dim3(256), 0, st, x, groups, C, mean, invstd, gamma, beta, res, relu, y);
+    return hipGetLastError();
+}
+
+hipError_t bn_bwd(const bf16_t* gy, const bf16_t* y, const bf16_t* x, int M, int C, const float* gamma, const float* mean,
+                  const float* invstd, int train, bf16_t* gx, bf16_t* g_res, float* g_gamma, float* g_beta, float* part, hipStream_t st) {
+    const int tr = bn_tile_rows(M), nt = bn_tiles(M);
+    float* sums = part + (size_t)nt * 2 * C;
+    hipLaunchKernelGGL(bbn_bwd_part_kernel, dim3((C + 63) / 64, nt), dim3(256), 0, st, gy, y, x, M, C, tr, mean, invstd, part);
+    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C), dim3(64), 0, st, part, nt, C, sums, g_gamma, g_beta);
+    const long long groups = (long long)M * C / 8;
+    hipLaunchKernelGGL(bbn_bwd_apply_kernel, dim3(nblk(groups)), dim3(256), 0, st, gy, y, x, groups, C, 1.f / (float)M, train, mean,
+                       invstd, gamma, sums, gx, g_res);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the trunk plan
+constexpr int NLAYER = 53;
+constexpr int IMG = 224;
+
+struct Layer {
+    int idx, c_real;                     // position in state_dict order; input channels of the fp32 weight (3 for the stem)
+    Geom g;
+    bf16_t *in, *z, *a;                  // conv input, conv output (pre-BN), BN output
+    bf16_t *wf, *wd;                     // this call's packed bf16 weights
+    float *mean, *invstd;
+};
+
+struct Block {
+    Layer c1, c2, c3, ds;
+    bool has_ds;
+};
+
+struct Plan {
+    Layer stem;
+    bf16_t *ximg, *pool;                 // 8-channel NHWC bf16 copy of the crops; max-pool output
+    Block blk[16];
+    bf16_t* G[6];                        // backward: gradient buffers of the largest activation
+    float* part;                         // split-K / BN partials
+    size_t total;                        // bytes
+};
+
+// The walk of trunk_grad.hip's make_plan with bf16 activations.  base == nullptr: sizes only.  Every buffer starts on a 256-byte
+// boundary.  Order: packed weights (wf, and wd when save = 1, per layer), then activations / statistics as the fp32 plan lists them,
+// the six gradient
+// buffers (save = 1), the fp32 partials.
+Plan make_plan(int n, int save, char* base) {
+    Plan P;
+    size_t off = 0;
+    auto take = [&](size_t bytes) -> char* {
+        char* p = base ? base + off : nullptr;
+        off += align256(bytes);
+        return p;
+    };
+    const size_t big = (size_t)n * 112 * 112 * 64 * 2;      // the largest activation in bytes (= the fp32 8-channel crop gradient)
+    bf16_t* slot[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t part = 0;
+    std::vector<Layer*> order;
+    auto mk = [&](Layer& L, int idx, bf16_t* in, int H, int C, int K, int R, int st, int pad, bf16_t* zs) {
+        L.idx = idx;
+        L.c_real = C;
+        const int Cp = (C + 7) & ~7;
+        L.g = make_geom(n, H, H, Cp, K, R, R, st, pad);
+        L.in = in;
+        L.wf = (bf16_t*)take((size_t)K * R * R * Cp * 2);
+        L.wd = save ? (bf16_t*)take((size_t)K * R * R * Cp * 2) : nullptr;    // the data gradient's packing: backward only
+        const size_t sz = (size_t)n * L.g.Ho * L.g.Wo * K * 2;
+        L.z = save ? (bf16_t*)take(sz) : zs;
+        L.a = save ? (bf16_t*)take(sz) : zs;
+        L.mean = (float*)take((size_t)K * 4);
+        L.invstd = (float*)take((size_t)K * 4);
+        part = std::max(part, wgrad_floats(L.g));
+        part = std::max(part, bn_part_floats(n * L.g.Ho * L.g.Wo, K));
+    };
+    if (!save)
+        for (int k = 0; k < 5; ++k) slot[k] = (bf16_t*)take(big);
+    P.ximg = save ? (bf16_t*)take((size_t)n * IMG * IMG * 8 * 2) : slot[0];
+    mk(P.stem, 0, P.ximg, IMG, 3, 64, 7, 2, 3, slot[1]);
+    P.pool = save ? (bf16_t*)take((size_t)n * 56 * 56 * 64 * 2) : slot[2];
+    bf16_t* x = P.pool;
+    int H = 56, C = 64, idx = 1, bi = 0;
+    int free_slots[3] = {0, 1, 3};
+    int in_slot = 2, ds_slot = 4;
+    const int layers[4] = {3, 4, 6, 3}, planes[4] = {64, 128, 256, 512};
+    for (int li = 0; li < 4; ++li)
+        for (int b = 0; b < layers[li]; ++b, ++bi) {
+            const int p = planes[li], st = (b == 0 && li > 0) ? 2 : 1;
+            Block& B = P.blk[bi];
+            B.has_ds = b == 0;
+            bf16_t *s1 = nullptr, *s2 = nullptr, *s3 = nullptr;
+            if (!save) { s1 = slot[free_slots[0]]; s2 = slot[free_slots[1]]; s3 = slot[free_slots[2]]; }
+            mk(B.c1, idx++, x, H, C, p, 1, 1, 0, s1);
+            mk(B.c2, idx++, B.c1.a, H, p, p, 3, st, 1, s2);
+            const int Ho = B.c2.g.Ho;
+            mk(B.c3, idx++, B.c2.a, Ho, p, 4 * p, 1, 1, 0, s3);
+            if (B.has_ds) mk(B.ds, idx++, x, H, C, 4 * p, 1, st, 0, save ? nullptr : slot[ds_slot]);
+            x = B.c3.a;
+            H = Ho;
+            C = 4 * p;
+            if (!save) {
+                const int o = free_slots[2];
+                free_slots[2] = in_slot;
+                in_slot = o;
+            }
+        }
+    for (int k = 0; k < 6; ++k) P.G[k] = save ? (bf16_t*)take(big) : nullptr;
+    P.part = (float*)take(part * 4);
+    P.total = off;
+    return P;
+}
+
+const float* prm(const void* const* t, int layer, int k) { return (const float*)t[layer * 5 + k]; }
+
+int check_table(const void* const* params, const char* what) {
+    if (!params) return apg_fail(APG_EINVAL, std::string(what) + ": parameter table missing");
+    for (int k = 0; k < NLAYER * 5; ++k)
+        if (!params[k]) return apg_fail(APG_EINVAL, std::string(what) + ": parameter table entry " + std::to_string(k) + " is NULL");
+    return APG_OK;
+}
+
+int64_t bf16_trunk_bytes(int n, int save) {
+    if (n <= 0 || n > 2048) return -1;
+    return (int64_t)make_plan(n, save ? 1 : 0, nullptr).total;
+}
+
+}  // namespace
+
+#define APG_TRY(expr)                                                                               \
+    do {                                                                                            \
+        hipError_t _e = (expr);                                                                     \
+        if (_e != hipSuccess) return apg_fail((int)_e, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+    } while (0)
+
+extern "C" {
+
+int apg_trunk_precisions(void) { return (1 << APG_PREC_FP32) | (1 << APG_PREC_BF16); }
+
+// ------------------------------------------------------------------------------------------------ primitives
+int apg_pack_weights_bf16(const float* w, int K, int C, int Cp, int R, int S, void* wf, void* wd, void* stream) {
+    if (!w || (!wf && !wd) || K <= 0 || C <= 0 || R <= 0 || S <= 0 || Cp < C || Cp % 8 != 0 || K % 8 != 0 || !al16(wf) || !al16(wd) ||
+        (long long)K * R * S * Cp >= (1LL << 31))
+        return apg_fail(APG_EINVAL, "apg_pack_weights_bf16: bad argument (Cp >= C and C_out multiples of 8, wf / wd 16-byte aligned)");
+    pack_weights(w, K, C, Cp, R, S, (bf16_t*)wf, (bf16_t*)wd, (hipStream_t)stream);
+    APG_TRY(hipGetLastError());
+    return APG_OK;
+}
+
+int apg_conv_fwd_bf16(const void* x, int n, int H, int W, int C, const void* wf, int K, int R, int S, int stride, int pad, void* y,
+                      void* stream) {
+    const Geom g = make_geom(n, H, W, C, K, R, S, stride, pad);
+    if (!x || !wf || !y || !geom_ok(g) || !al16(x) || !al16(wf) || !al16(y))
+        return apg_fail(APG_EINVAL, "apg_conv_fwd_bf16: bad argument (C and C_out multiples of 8, pointers 16-byte aligned)");
+    APG_TRY(conv_fwd(g, (const bf16_t*)x, (const bf16_t*)wf, (bf16_t*)y, (hipStream_t)stream));
+    return APG_OK;
+}
+
+int64_t apg_conv_bwd_bf16_workspace_bytes(int n, int H, int W, int C, int K, int R, int S, int stride, int pad) {
+    const Geom g = make_geom(n, H, W, C, K, R, S, stride, pad);
+    if (!geom_ok(g)) return -1;
+    return (int64_t)(wgrad_floats(g) * sizeof(float));
+}
+
+int apg_conv_bwd_bf16(const void* x, int n, int H, int W, int C, const void* wd, int K, int R, int S, int stride, int pad, const void* gy,
+                      const void* add, int add_fp32, void* gx, int gx_fp32, float* gw, int gw_channels, void* workspace, int64_t workspace_bytes,
+                      void* stream) {
+    const Geom g = make_geom(n, H, W, C, K, R, S, stride, pad);
+    if (!gy || !geom_ok(g) || (!gx && !gw) || (gx && !wd) || (gw && !x) || !al16(gy) || !al16(x) || !al16(wd) || !al16(gx) || !al16(add) ||
+        (add && (!gx || gx_fp32)) || (add && add_fp32 && add == gx) || (gw && (gw_channels <= 0 || gw_channels > C)))
+        return apg_fail(APG_EINVAL, "apg_conv_bwd_bf16: bad argument (C and C_out multiples of 8, pointers 16-byte aligned, "
+                                    "1 <= gw_channels <= C)");
+    if (gw && (!workspace || workspace_bytes < (int64_t)(wgrad_floats(g) * sizeof(float))))
+        return apg_fail(APG_ENOMEM, "apg_conv_bwd_bf16: workspace of " + std::to_string(workspace_bytes) + " bytes, " +
+                                        std::to_string(wgrad_floats(g) * sizeof(float)) + " needed");
+    hipStream_t st = (hipStream_t)stream;
+    if (gx) APG_TRY(conv_dgrad(g, (const bf16_t*)gy, (const bf16_t*)wd, add, add_fp32 ? 1 : 0, gx, gx_fp32 ? 1 : 0, st));
+    if (gw) APG_TRY(conv_wgrad(g, (const bf16_t*)x, (const bf16_t*)gy, (float*)workspace, gw, gw_channels, st));
+    return APG_OK;
+}
+
+int64_t apg_bn_bf16_workspace_bytes(int M, int C) {
+    if (M <= 0 || C <= 0 || C % 8 != 0) return -1;
+    return (int64_t)(bn_part_floats(M, C) * sizeof(float));
+}
+
+int apg_bn_fwd_bf16(const void* x, int M, int C, const float* gamma, const float* beta, float* running_mean, float* running_var, int train,
+                    float momentum, float eps, const void* res, int relu, void* y, float* save_mean, float* save_invstd, void* workspace,
+                    int64_t workspace_bytes, void* stream) {
+    if (!x || M <= 0 || C <= 0 || C % 8 != 0 || !gamma || !beta || !y || !save_mean || !save_invstd || !(eps >= 0.f) ||
+        (!train && (!running_mean || !running_var)) || (!running_mean != !running_var) || !al16(x) || !al16(y) || !al16(res))
+        return apg_fail(APG_EINVAL, "apg_bn_fwd_bf16: bad argument (C a multiple of 8, x / y / res 16-byte aligned)");
+    if (train && (!workspace || workspace_bytes < apg_bn_bf16_workspace_bytes(M, C)))
+        return apg_fail(APG_ENOMEM, "apg_bn_fwd_bf16: workspace too small");
+    APG_TRY(bn_fwd((const bf16_t*)x, M, C, gamma, beta, running_mean, running_var, train, momentum, eps, (const bf16_t*)res, relu,
+                   (bf16_t*)y, save_mean, save_invstd, (float*)workspace, (hipStream_t)stream));
+    return APG_OK;
+}
+
+int apg_bn_bwd_bf16(const void* gy, const void* y, const void* x, int M, int C, const float* gamma, const float* save_mean,
+                    const float* save_invstd, int train, void* gx, void* g_res, float* g_gamma, float* g_beta, void* workspace,
+                    int64_t workspace_bytes, void* stream) {
+    if (!gy || !x || M <= 0 || C <= 0 || C % 8 != 0 || !gamma || !save_mean || !save_invstd || !gx || !al16(gy) || !al16(y) || !al16(x) ||
+        !al16(gx) || !al16(g_res))
+        return apg_fail(APG_EINVAL, "apg_bn_bwd_bf16: bad argument (C a multiple of 8, activation pointers 16-byte aligned)");
+    if (!workspace || workspace_bytes < apg_bn_bf16_workspace_bytes(M, C))
+        return apg_fail(APG_ENOMEM, "apg_bn_bwd_bf16: workspace too small");
+    APG_TRY(bn_bwd((const bf16_t*)gy, (const bf16_t*)y, (const bf16_t*)x, M, C, gamma, save_mean, save_invstd, train, (bf16_t*)gx,
+                   (bf16_t*)g_res, g_gamma, g_beta, (float*)workspace, (hipStream_t)stream));
+    return APG_OK;
+}
+
+int apg_maxpool_fwd_bf16(const void* x, int n, int H, int W, int C, void* y, void* stream) {
+    if (!x || !y || n <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 != 0 || !al16(x) || !al16(y) ||
+        (long long)n * H * W * C >= (1LL << 31))
+        return apg_fail(APG_EINVAL, "apg_maxpool_fwd_bf16: bad argument (C a multiple of 8, pointers 16-byte aligned)");
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    hipLaunchKernelGGL(bmaxpool_fwd_kernel, dim3(nblk((long long)n * Ho * Wo * C / 8)), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16_t*)x, n, H, W, C, Ho, Wo, (bf16_t*)y);
+    APG_TRY(hipGetLastError());
+    return APG_OK;
+}
+
+int apg_maxpool_bwd_bf16(const void* x, int n, int H, int W, int C, const void* gy, void* gx, void* stream) {
+    if (!x || !gy || !gx || n <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 != 0 || !al16(x) || !al16(gy) || !al16(gx) ||
+        (long long)n * H * W * C >= (1LL << 31))
+        return apg_fail(APG_EINVAL, "apg_maxpool_bwd_bf16: bad argument (C a multiple of 8, pointers 16-byte aligned)");
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    hipLaunchKernelGGL(bmaxpool_bwd_kernel, dim3(nblk((long long)n * H * W * C / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
+                       (const bf16_t*)gy, n, H, W, C, Ho, Wo, (bf16_t*)gx);
+    APG_TRY(hipGetLastError());
+    return APG_OK;
+}
+
+int apg_avgpool_fwd_bf16(const void* x, int n, int C, float* y, void* stream) {
+    if (!x || !y || n <= 0 || C <= 0) return apg_fail(APG_EINVAL, "apg_avgpool_fwd_bf16: bad argument");
+    hipLaunchKernelGGL(bavgpool_fwd_kernel, dim3(nblk((long long)n * C)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, n, C, y);
+    APG_TRY(hipGetLastError());
+    return APG_OK;
+}
+
+int apg_avgpool_bwd_bf16(const float* gy, int n, int C, void* gx, void* stream) {
+    if (!gy || !gx || n <= 0 || C <= 0 || C % 8 != 0 || !al16(gx))
+        return apg_fail(APG_EINVAL, "apg_avgpool_bwd_bf16: bad argument (C a multiple of 8, gx 16-byte aligned)");
+    hipLaunchKernelGGL(bavgpool_bwd_kernel, dim3(nblk((long long)n * 49 * C / 8)), dim3(256), 0, (hipStream_t)stream, gy, n, C,
+                       (bf16_t*)gx);
+    APG_TRY(hipGetLastError());
+    return APG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the trunk walker
+int64_t apg_trunk_workspace_bytes_p(int n, int save, int precision) {
+    if (precision == APG_PREC_FP32) return apg_trunk_workspace_bytes(n, save);
+    if (precision != APG_PREC_BF16) return -1;
+    return bf16_trunk_bytes(n, save);
+}
+
+int apg_trunk_fwd_p(int precision, int n, const float* x, const void* const* params, int train, float momentum, float eps, float* xf,
+                    int save, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (precision == APG_PREC_FP32) return apg_trunk_fwd(n, x, params, train, momentum, eps, xf, save, workspace, workspace_bytes, stream);
+    if (precision != APG_PREC_BF16) return apg_fail(APG_EINVAL, "apg_trunk_fwd_p: unknown precision " + std::to_string(precision));
+    if (n <= 0 || n > 2048 || !x || !xf || !workspace || !(eps >= 0.f) || (train && !(momentum >= 0.f && momentum <= 1.f)))
+        return apg_fail(APG_EINVAL, "apg_trunk_fwd_p: bad argument");
+    if (((uintptr_t)workspace & 255) != 0) return apg_fail(APG_EINVAL, "apg_trunk_fwd_p: the workspace must be 256-byte aligned");
+    if (int rc = check_table(params, "apg_trunk_fwd_p")) return rc;
+    if (workspace_bytes < bf16_trunk_bytes(n, save))
+        return apg_fail(APG_ENOMEM, "apg_trunk_fwd_p: workspace of " + std::to_string(workspace_bytes) + " bytes, " +
+                                        std::to_string(bf16_trunk_bytes(n, save)) + " needed");
+    hipStream_t st = (hipStream_t)stream;
+    const Plan P = make_plan(n, save ? 1 : 0, (char*)workspace);
+    auto run = [&](const Layer& L, const bf16_t* res, int relu) -> hipError_t {
+        pack_weights(prm(params, L.idx, 0), L.g.K, L.c_real, L.g.C, L.g.R, L.g.S, L.wf, L.wd, st);
+        hipError_t e = conv_fwd(L.g, L.in, L.wf, L.z, st);
+        if (e != hipSuccess) return e;
+        return bn_fwd(L.z, n * L.g.Ho * L.g.Wo, L.g.K, prm(params, L.idx, 1), prm(params, L.idx, 2), (float*)prm(params, L.idx, 3),
+                      (float*)prm(params, L.idx, 4), train, momentum, eps, res, relu, L.a, L.mean, L.invstd, P.part, st);
+    };
+    hipLaunchKernelGGL(nchw_to_nhwc8_kernel, dim3(nblk((long long)n * IMG * IMG)), dim3(256), 0, st, x, n, 3, IMG * IMG, P.ximg);
+    APG_TRY(run(P.stem, nullptr, 1));
+    hipLaunchKernelGGL(bmaxpool_fwd_kernel, dim3(nblk((long long)n * 56 * 56 * 64 / 8)), dim3(256), 0, st, P.stem.a, n, 112, 112, 64, 56,
+                       56, P.pool);
+    APG_TRY(hipGetLastError());
+    for (int b = 0; b < 16; ++b) {
+        const Block& B = P.blk[b];
+        APG_TRY(run(B.c1, nullptr, 1));
+        APG_TRY(run(B.c2, nullptr, 1));
+        if (B.has_ds) APG_TRY(run(B.ds, nullptr, 0));
+        APG_TRY(run(B.c3, B.has_ds ? B.ds.a : B.c1.in, 1));
+    }
+    hipLaunchKernelGGL(bavgpool_fwd_kernel, dim3(nblk((long long)n * 2048)), dim3(256), 0, st, P.blk[15].c3.a, n, 2048, xf);
+    APG_TRY(hipGetLastError());
+    return APG_OK;
+}
+
+int apg_trunk_bwd_p(int precision, int n, const void* const* params, int train, const float* g_xf, void* const* g_params, float* g_x,
+                    void* workspace, int64_t workspace_bytes, void* stream) {
+    if (precision == APG_PREC_FP32) return apg_trunk_bwd(n, params, train, g_xf, g_params, g_x, workspace, workspace_bytes, stream);
+    if (precision != APG_PREC_BF16) return apg_fail(APG_EINVAL, "apg_trunk_bwd_p: unknown precision " + std::to_string(precision));
+    if (n <= 0 || n > 2048 || !g_xf || !g_params || !workspace) return apg_fail(APG_EINVAL, "apg_trunk_bwd_p: bad argument");
+    if (((uintptr_t)workspace & 255) != 0) return apg_fail(APG_EINVAL, "apg_trunk_bwd_p: the workspace must be 256-byte aligned");
+    if (int rc = check_table(params, "apg_trunk_bwd_p")) return rc;
+    if (workspace_bytes < bf16_trunk_bytes(n, 1))
+        return apg_fail(APG_ENOMEM, "apg_trunk_bwd_p: workspace of " + std::to_string(workspace_bytes) + " bytes, " +
+                                        std::to_string(bf16_trunk_bytes(n, 1)) + " needed (the one apg_trunk_fwd_p filled, save = 1)");
+    hipStream_t st = (hipStream_t)stream;
+    const Plan P = make_plan(n, 1, (char*)workspace);
+    bf16_t *gcur = P.G[0], *gnext = P.G[1], *g3 = P.G[2], *g2 = P.G[3], *g1 = P.G[4], *gres = P.G[5];
+    auto gp = [&](const Layer& L, int k) { return (float*)g_params[L.idx * 3 + k]; };
+    auto bnb = [&](const Layer& L, const bf16_t* gy, int relu, bf16_t* gx, bf16_t* g_res) -> hipError_t {
+        return bn_bwd(gy, relu ? L.a : nullptr, L.z, n * L.g.Ho * L.g.Wo, L.g.K, prm(params, L.idx, 1), L.mean, L.invstd, train, gx,
+                      g_res, gp(L, 1), gp(L, 2), P.part, st);
+    };
+    auto wg = [&](const Layer& L, const bf16_t* gz) -> hipError_t {
+        if (!gp(L, 0)) return hipSuccess;
+        return conv_wgrad(L.g, L.in, gz, P.part, gp(L, 0), L.c_real, st);
+    };
+    hipLaunchKernelGGL(bavgpool_bwd_kernel, dim3(nblk((long long)n * 49 * 2048 / 8)), dim3(256), 0, st, g_xf, n, 2048, gcur);
+    APG_TRY(hipGetLastError());
+    for (int b = 15; b >= 0; --b) {
+        const Block& B = P.blk[b];
+        APG_TRY(bnb(B.c3, gcur, 1, g3, gres));
+        APG_TRY(wg(B.c3, g3));
+        APG_TRY(conv_dgrad(B.c3.g, g3, B.c3.wd, nullptr, 0, g2, 0, st));
+        APG_TRY(bnb(B.c2, g2, 1, g2, nullptr));
+        APG_TRY(wg(B.c2, g2));
+        APG_TRY(conv_dgrad(B.c2.g, g2, B.c2.wd, nullptr, 0, g1, 0, st));
+        APG_TRY(bnb(B.c1, g1, 1, g1, nullptr));
+        APG_TRY(wg(B.c1, g1));
+        if (B.has_ds) {
+            APG_TRY(bnb(B.ds, gres, 0, gres, nullptr));
+            APG_TRY(wg(B.ds, gres));
+            // the downsample's data gradient stays fp32 (g3 and g2 are free here and adjacent: 2 x big bytes hold the block
+            // input in fp32) and conv1's data gradient adds it before the one rounding
+            APG_TRY(conv_dgrad(B.ds.g, gres, B.ds.wd, nullptr, 0, g3, 1, st));
+            APG_TRY(conv_dgrad(B.c1.g, g1, B.c1.wd, g3, 1, gnext, 0, st));
+        } else {
+            APG_TRY(conv_dgrad(B.c1.g, g1, B.c1.wd, gres, 0, gnext, 0, st));
+        }
+        std::swap(gcur, gnext);
+    }
+    hipLaunchKernelGGL(bmaxpool_bwd_kernel, dim3(nblk((long long)n * 112 * 112 * 64 / 8)), dim3(256), 0, st, P.stem.a, gcur, n, 112, 112,
+                       64, 56, 56, g1);
+    APG_TRY(hipGetLastError());
+    APG_TRY(bnb(P.stem, g1, 1, g1, nullptr));
+    APG_TRY(wg(P.stem, g1));
+    if (g_x) {                                                   // fp32 crop gradient: 8 channels per pixel in g2, then NCHW
+        APG_TRY(conv_dgrad(P.stem.g, g1, P.stem.wd, nullptr, 0, g2, 1, st));
+        hipLaunchKernelGGL(nhwc8_to_nchw_kernel, dim3(nblk((long long)n * 3 * IMG * IMG)), dim3(256), 0, st, (const float*)g2, n, 3,
+                           IMG * IMG, g_x);
+        APG_TRY(hipGetLastError());
+    }
+    return APG_OK;
+}
+
+}  // extern "C"

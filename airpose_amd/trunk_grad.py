@@ -11,6 +11,11 @@ BatchNorm follows the module's mode, as nn.BatchNorm2d does:
   - eval mode: the running statistics (the "frozen BN" fine-tune), left unchanged.
 The activations backward needs live in one workspace the forward fills (apg_trunk_workspace_bytes(n, 1), kept by the autograd
 graph until backward); without grad the forward runs on a smaller one and records nothing.
+
+precision="bf16" (copenet.set_trunk_trainable(True, precision="bf16")) runs the same graph through trunk_grad_bf16.hip: bf16 NHWC
+activations and activation gradients inside the workspace, bf16 x bf16 products accumulated in fp32, fp32 BatchNorm statistics.
+The parameters, their .grad, the running buffers, xf and the crop gradient stay fp32 tensors; the bf16 copy of the conv weights is
+packed into the call's workspace on every forward call, so nothing is cached across calls either.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -74,8 +79,16 @@ def _table_ptrs(params, bufs):
     return G.ptrs(t)
 
 
-def _run_fwd(n, x, params, bufs, train, momentum, eps, save, dev):
+def _prec(precision):
+    if precision not in G.PRECISIONS:
+        raise RuntimeError("airpose_amd.copenet: the trainable trunk's precision is one of %s, got %r" % (sorted(G.PRECISIONS), precision))
+    return G.PRECISIONS[precision]
+
+
+def _run_fwd(n, x, params, bufs, train, momentum, eps, save, dev, precision="fp32"):
     L = G.lib()
+    if precision != "fp32":
+        return _run_fwd_p(L, _prec(precision), n, x, params, bufs, train, momentum, eps, save, dev)
     nbytes = L.apg_trunk_workspace_bytes(n, int(save))
     if nbytes <= 0:
         raise RuntimeError("airpose_amd.copenet: the trainable trunk takes 1 <= n <= 2048 crops per call, got %d" % n)
@@ -87,11 +100,23 @@ def _run_fwd(n, x, params, bufs, train, momentum, eps, save, dev):
     return xf, ws
 
 
+def _run_fwd_p(L, prec, n, x, params, bufs, train, momentum, eps, save, dev):
+    nbytes = L.apg_trunk_workspace_bytes_p(n, int(save), prec)
+    if nbytes <= 0:
+        raise RuntimeError("airpose_amd.copenet: the trainable trunk takes 1 <= n <= 2048 crops per call, got %d" % n)
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)     # the caching allocator hands out 512-byte aligned blocks
+    xf = torch.empty(n, 2048, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        G.check(L.apg_trunk_fwd_p(prec, n, N.dptr(x, "x"), _table_ptrs(params, bufs), int(train), momentum, eps, N.dptr(xf), int(save),
+                                  ws.data_ptr(), nbytes, N.stream_ptr(dev)), "apg_trunk_fwd_p")
+    return xf, ws
+
+
 class _Trunk(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg, x, *params):
-        n, train, momentum, eps, bufs, dev = cfg
-        xf, ws = _run_fwd(n, x, params, bufs, train, momentum, eps, True, dev)
+        n, train, momentum, eps, bufs, dev, precision = cfg
+        xf, ws = _run_fwd(n, x, params, bufs, train, momentum, eps, True, dev, precision)
         ctx.cfg = cfg
         ctx.ws = ws                                              # saved activations: the library's own buffer
         ctx.save_for_backward(*params)                           # version check: the parameters must not change before backward
@@ -100,7 +125,7 @@ class _Trunk(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g_xf):
-        n, train, momentum, eps, bufs, dev = ctx.cfg
+        n, train, momentum, eps, bufs, dev, precision = ctx.cfg
         params = ctx.saved_tensors
         need = ctx.needs_input_grad
         g_xf = N.f32c(g_xf, dev)
@@ -108,14 +133,21 @@ class _Trunk(torch.autograd.Function):
         g_x = torch.empty(n, 3, 224, 224, device=dev, dtype=torch.float32) if need[1] else None
         ws, ctx.ws = ctx.ws, None
         with torch.cuda.device(dev):
-            G.check(G.lib().apg_trunk_bwd(n, _table_ptrs(list(params), bufs), int(train), N.dptr(g_xf), G.ptrs(g_params),
-                                          N.dptr(g_x), ws.data_ptr(), ws.numel(), N.stream_ptr(dev)), "apg_trunk_bwd")
+            if precision == "fp32":
+                G.check(G.lib().apg_trunk_bwd(n, _table_ptrs(list(params), bufs), int(train), N.dptr(g_xf), G.ptrs(g_params),
+                                              N.dptr(g_x), ws.data_ptr(), ws.numel(), N.stream_ptr(dev)), "apg_trunk_bwd")
+            else:
+                G.check(G.lib().apg_trunk_bwd_p(_prec(precision), n, _table_ptrs(list(params), bufs), int(train), N.dptr(g_xf),
+                                                G.ptrs(g_params), N.dptr(g_x), ws.data_ptr(), ws.numel(), N.stream_ptr(dev)),
+                        "apg_trunk_bwd_p")
         return (None, g_x) + tuple(g_params)
 
 
-def forward_feat_ext(net, x):
+def forward_feat_ext(net, x, precision="fp32"):
     """(n, 3, 224, 224) NCHW crops -> (n, 2048) features on the trainable path; BatchNorm in the module's mode (see the module
-    docstring).  Records the autograd graph when grad is enabled and x or a trunk parameter requires grad."""
+    docstring).  Records the autograd graph when grad is enabled and x or a trunk parameter requires grad.  precision: "fp32"
+    or "bf16" (see the module docstring)."""
+    _prec(precision)
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise RuntimeError("airpose_amd.copenet: inputs must be CUDA (ROCm) tensors; there is no CPU path")
     dev = x.device
@@ -128,9 +160,9 @@ def forward_feat_ext(net, x):
     x = N.f32c(x)
     n = x.shape[0]
     if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
-        xf = _Trunk.apply((n, train, momentum, eps, bufs, dev), x, *params)
+        xf = _Trunk.apply((n, train, momentum, eps, bufs, dev, precision), x, *params)
     else:
-        xf, _ = _run_fwd(n, x, params, bufs, train, momentum, eps, False, dev)
+        xf, _ = _run_fwd(n, x, params, bufs, train, momentum, eps, False, dev, precision)
     if train:
         with torch.no_grad():
             torch._foreach_add_([bn.num_batches_tracked for _, bn in pairs], 1)

@@ -165,6 +165,74 @@ int apg_trunk_fwd(int n, const float* x, const void* const* params, int train, f
 int apg_trunk_bwd(int n, const void* const* params, int train, const float* g_xf, void* const* g_params, float* g_x, void* workspace,
                   int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mixed-precision (bf16) training mode of the trunk (trunk_grad_bf16.hip).  Additive under ABI 2: a binding tells a library that
+ * has these entry points from one that has not by looking up apg_trunk_precisions.
+ *
+ * Storage: activations and activation gradients are bf16 NHWC (passed as void*), every one 16-byte aligned with a channel count
+ * that is a multiple of 8; parameters, parameter gradients, BatchNorm statistics, xf and the crop gradient are fp32.  Products are
+ * bf16 x bf16 accumulated in fp32 (v_mfma_f32_16x16x32_bf16); each stored bf16 value is ONE round-to-nearest-even of an fp32 result.
+ * Reductions run in a fixed order: results are bit-reproducible run to run.  A misaligned bf16 pointer or a channel count that is
+ * not a multiple of 8 is APG_EINVAL, as are the geometry refusals of the fp32 entry points; a workspace smaller than its query
+ * asks for is APG_ENOMEM, as in the fp32 entry points.  fp32 outputs (gw, an fp32 gx, statistics, xf) are written one float at a
+ * time and need only their natural 4-byte alignment. */
+#define APG_PREC_FP32 0
+#define APG_PREC_BF16 1
+
+/* Bit mask of the precisions the trunk walker takes: bit APG_PREC_FP32 | bit APG_PREC_BF16. */
+int apg_trunk_precisions(void);
+
+/* fp32 OIHW weights w (K, C, R, S) -> bf16 (RNE) in the two layouts the kernels read, input channels padded with zeros to Cp
+ * (Cp >= C, a multiple of 8; K a multiple of 8): wf [K][R][S][Cp] (forward) and wd [Cp][R][S][K] (data gradient); either may be
+ * NULL. */
+int apg_pack_weights_bf16(const float* w, int K, int C, int Cp, int R, int S, void* wf, void* wd, void* stream);
+
+/* y (n, Ho, Wo, K) bf16 = RNE(conv(x, w)): x (n, H, W, C) bf16, wf from apg_pack_weights_bf16 with Cp = C. */
+int apg_conv_fwd_bf16(const void* x, int n, int H, int W, int C, const void* wf, int K, int R, int S, int stride, int pad, void* y,
+                      void* stream);
+
+/* Workspace of apg_conv_bwd_bf16 in bytes (the fp32 split-K partials, C padded channels wide); negative for a bad geometry. */
+int64_t apg_conv_bwd_bf16_workspace_bytes(int n, int H, int W, int C, int K, int R, int S, int stride, int pad);
+
+/* gy (n, Ho, Wo, K) bf16 -> gx (n, H, W, C) and / or gw; each output NULL = not needed (at least one).
+ *   gx = RNE(dgrad(gy, wd) + add): wd from apg_pack_weights_bf16; add (same shape as gx, NULL = none; bf16, may alias gx, or with
+ *     add_fp32 != 0 fp32, must not alias gx) is added in fp32 before the one rounding; gx_fp32 != 0: gx is written as fp32 instead
+ *     (no add).  The walker keeps a downsample branch's data gradient in fp32 and hands it to conv1's data gradient as the fp32
+ *     addend, so a block input's gradient is rounded once.
+ *   gw (K, gw_channels, R, S) fp32 OIHW = the first gw_channels <= C input channels of wgrad(x, gy): fixed split-K chunks of fp32
+ *     partials combined in chunk order; needs x and the workspace. */
+int apg_conv_bwd_bf16(const void* x, int n, int H, int W, int C, const void* wd, int K, int R, int S, int stride, int pad, const void* gy,
+                      const void* add, int add_fp32, void* gx, int gx_fp32, float* gw, int gw_channels, void* workspace, int64_t workspace_bytes,
+                      void* stream);
+
+/* BatchNorm on bf16 x / y / res / gy / gx / g_res; everything per channel is fp32.  Statistics are taken in fp32 from the stored
+ * bf16 x with the tiles, partials and trees of apg_bn_fwd; arguments as apg_bn_fwd / apg_bn_bwd.  g_res is exact (gy or 0). */
+int64_t apg_bn_bf16_workspace_bytes(int M, int C);
+int apg_bn_fwd_bf16(const void* x, int M, int C, const float* gamma, const float* beta, float* running_mean, float* running_var, int train,
+                    float momentum, float eps, const void* res, int relu, void* y, float* save_mean, float* save_invstd, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+int apg_bn_bwd_bf16(const void* gy, const void* y, const void* x, int M, int C, const float* gamma, const float* save_mean,
+                    const float* save_invstd, int train, void* gx, void* g_res, float* g_gamma, float* g_beta, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+
+/* The pools on bf16 maps.  Max-pool is a selection (exact); its backward sums a pixel's windows in fp32 and rounds once.
+ * Avg-pool: bf16 (n, 7, 7, C) -> fp32 (n, C) summed in fp32 in row-major order; backward fp32 gy (n, C) -> bf16 gx = RNE(gy / 49). */
+int apg_maxpool_fwd_bf16(const void* x, int n, int H, int W, int C, void* y, void* stream);
+int apg_maxpool_bwd_bf16(const void* x, int n, int H, int W, int C, const void* gy, void* gx, void* stream);
+int apg_avgpool_fwd_bf16(const void* x, int n, int C, float* y, void* stream);
+int apg_avgpool_bwd_bf16(const float* gy, int n, int C, void* gx, void* stream);
+
+/* The trunk walker with a precision argument.  APG_PREC_FP32 is apg_trunk_workspace_bytes / apg_trunk_fwd / apg_trunk_bwd, same
+ * bits.  APG_PREC_BF16: x, params, g_params, xf, g_xf, g_x as there (all fp32); the crops are cast to bf16 (8 channels per pixel,
+ * the last 5 zero), every conv weight is packed to bf16 into the workspace on every apg_trunk_fwd_p call (nothing is cached across
+ * calls; the data gradient's packing only with save = 1) and apg_trunk_bwd_p reads that copy.  The workspace must be 256-byte aligned; save = 1: 3.7 GB at n = 64 (about 56 MB per
+ * image and 94 MB of packed weights).  Any other precision: a negative size / APG_EINVAL. */
+int64_t apg_trunk_workspace_bytes_p(int n, int save, int precision);
+int apg_trunk_fwd_p(int precision, int n, const float* x, const void* const* params, int train, float momentum, float eps, float* xf,
+                    int save, void* workspace, int64_t workspace_bytes, void* stream);
+int apg_trunk_bwd_p(int precision, int n, const void* const* params, int train, const float* g_xf, void* const* g_params, float* g_x,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

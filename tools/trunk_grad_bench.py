@@ -14,7 +14,12 @@ way the reference's training_step runs them:
 HIP events around windows of --reps calls after --warmup calls; the median of --windows windows is reported per call.  One JSON line
 per batch size; --out also writes them to a file.
 
-    python tools/trunk_grad_bench.py [--sizes 8,32,64] [--reps 3] [--windows 3] [--out profiles/x.json]
+--precision {fp32,bf16} times the trunk in that mode (set_trunk_trainable(True, precision=...)) and, in the same process with the
+windows of all candidates interleaved round-robin (so clocks and neighbours drift over all alike), the fp32 path of the same build
+(fp32_fwd_ms / fp32_fwdbwd_ms), torch eager fp32 and torch eager under autocast(bfloat16) (autocast_fwd_ms / autocast_fwdbwd_ms);
+the peak fraction is then against the 2.5 PF bf16 matrix peak for bf16.  Without the flag the output is what it always was.
+
+    python tools/trunk_grad_bench.py [--sizes 8,32,64] [--reps 3] [--windows 3] [--precision bf16] [--out profiles/x.json]
 """
 import argparse
 import json
@@ -67,6 +72,27 @@ def timed(fn, warmup, reps, windows):
     return statistics.median(out)
 
 
+def timed_interleaved(fns, warmup, reps, windows, between):
+    """{name: median ms per call}: one window of every candidate per round, `windows` rounds"""
+    for fn in fns.values():
+        for _ in range(warmup):
+            fn()
+        between()
+    torch.cuda.synchronize()
+    out = {k: [] for k in fns}
+    for _ in range(windows):
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                fn()
+            b.record()
+            b.synchronize()
+            out[k].append(a.elapsed_time(b) / reps)
+            between()
+    return {k: round(statistics.median(v), 3) for k, v in out.items()}
+
+
 def eager_trunk(net, x):
     """forward_feat_ext in torch eager fp32 with train-mode BatchNorm (the module's own running buffers updated)."""
     def cbr(x, conv, bn, relu=True, res=None):
@@ -91,6 +117,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--precision", choices=("fp32", "bf16"), default=None)
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     net = copenet_model.getcopenet(MEAN, precision="fp32")
@@ -137,6 +164,40 @@ def main():
                 loss = loss + ((pj[:, :22] - j2d) ** 2).mean() * 1e-4 + ((jc[:, :22] - j3d) ** 2).mean() + (betas ** 2).mean()
             loss.backward()
 
+        if args.precision is not None:
+            def mode(precision, fn):
+                def run():
+                    net.set_trunk_trainable(True, precision=precision)
+                    fn()
+                return run
+
+            def autocast(fn):
+                def run():
+                    with torch.autocast("cuda", dtype=torch.bfloat16):
+                        fn()
+                return run
+            res = timed_interleaved({"fwd_ms": mode(args.precision, fwd), "fwdbwd_ms": mode(args.precision, fwdbwd),
+                                     "fp32_fwd_ms": mode("fp32", fwd), "fp32_fwdbwd_ms": mode("fp32", fwdbwd),
+                                     "eager_fwd_ms": eager_fwd, "eager_fwdbwd_ms": eager_fwdbwd,
+                                     "autocast_fwd_ms": autocast(eager_fwd), "autocast_fwdbwd_ms": autocast(eager_fwdbwd),
+                                     "step_ms": mode(args.precision, step)}, args.warmup, args.reps, args.windows,
+                                    lambda: net.zero_grad(set_to_none=True))
+            f, b = conv_flops(2 * B)
+            peak = 2.5e15 if args.precision == "bf16" else PEAK
+            L = __import__("airpose_amd._native_grad", fromlist=["lib"]).lib()
+            rec = {"tool": "trunk_grad_bench", "precision": args.precision, "pairs": B, "images": 2 * B, **res,
+                   "fwdbwd_vs_fp32_path": round(res["fp32_fwdbwd_ms"] / res["fwdbwd_ms"], 2),
+                   "fwdbwd_vs_eager": round(res["eager_fwdbwd_ms"] / res["fwdbwd_ms"], 2),
+                   "fwdbwd_vs_autocast": round(res["autocast_fwdbwd_ms"] / res["fwdbwd_ms"], 2),
+                   "fwd_vs_eager": round(res["eager_fwd_ms"] / res["fwd_ms"], 2),
+                   "fwdbwd_tflop": round((f + b) / 1e12, 3), "fwdbwd_tflops": round((f + b) / res["fwdbwd_ms"] / 1e9, 2),
+                   "fwdbwd_peak_frac": round((f + b) / res["fwdbwd_ms"] / 1e9 / (peak / 1e12), 4), "peak_tflops": peak / 1e12,
+                   "save_workspace_bytes_per_call": int(L.apg_trunk_workspace_bytes_p(B, 1, 1 if args.precision == "bf16" else 0)),
+                   "save_workspace_bytes_n64": {"bf16": int(L.apg_trunk_workspace_bytes_p(64, 1, 1)),
+                                                "fp32": int(L.apg_trunk_workspace_bytes_p(64, 1, 0))}}
+            print(json.dumps(rec), flush=True)
+            lines.append(rec)
+            continue
         res = {}
         for name, fn in (("fwd_ms", fwd), ("fwdbwd_ms", fwdbwd), ("eager_fwd_ms", eager_fwd), ("eager_fwdbwd_ms", eager_fwdbwd),
                          ("step_ms", step)):
