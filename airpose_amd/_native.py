@@ -93,6 +93,11 @@ SIGNATURES = {
     "ap_conv_img3_stream_bytes": (_c.c_int64, []),
     "ap_conv_img3_pack": (_i, [_i, _vp, _vp, _vp]),
     "ap_conv_img3_nhwc": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "ap_stem_pack_bytes": (_c.c_int64, [_i]),
+    "ap_stem_pack": (_i, [_i, _vp, _vp, _vp]),
+    "ap_stem_nhwc": (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "ap_maxpool_nhwc": (_i, [_i, _vp, _vp, _i, _vp]),
+    "ap_avgpool_nhwc": (_i, [_i, _vp, _vp, _i, _i, _vp]),
     "ap_conv_s2p_stream_bytes": (_c.c_int64, []),
     "ap_conv_s2p_pack": (_i, [_i, _vp, _vp, _vp]),
     "ap_conv_s2p_nhwc": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
@@ -131,7 +136,7 @@ SIGNATURES = {
     "ap_perspective_projection": (_i, [_vp, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp]),
 }
 
-ABI_VERSION = 10         # include/airpose_hip.h: AP_ABI_VERSION
+ABI_VERSION = 11         # include/airpose_hip.h: AP_ABI_VERSION
 _lib = None
 _lib_lock = threading.Lock()
 

@@ -634,38 +634,46 @@ void release_blocks(ap_net* h) {
     h->blocks.clear();
 }
 
-int finalize_trunk(ap_net* h) {
-    // stem: [64][3][7][7] -> [k = (r,s,c)][64] fp32 for the direct kernel
-    const HostTensor* w = find(h, "conv1.weight");
-    if (!w) return fail(AP_ESTATE, "missing tensor conv1.weight");
-    if (w->numel() != 64 * 3 * 49) return fail(AP_ESHAPE, "shape mismatch for conv1.weight");
-    std::vector<float> sw(147 * 64);
+// The stem's weight operands, packed on the host from conv1.weight [64][3][7][7] fp32 -- ONE packing for the trunk (finalize_trunk)
+// and for the stand-alone operator (ap_stem_pack), so a test of the operator is a test of the packing the trunk runs on:
+//   direct  [k = (r,s,c)][64] fp32 for the direct kernel (fp32 mode)
+//   pk      [64][AP_STEM_WLD] 16-bit for the MFMA stems, k' = r*32 + s*4 + c (zero elsewhere: 4th channel slot, 8th tap, row pad):
+//           fp16 for AP_PREC_F16 (*f16_overflow set when a weight leaves its range), bf16 otherwise -- for AP_PREC_BF16X2 the high plane
+//   pk_lo   AP_PREC_BF16X2 only: the low plane, bf16(w - hi) at the same positions
+struct StemPack {
+    std::vector<float> direct;
+    std::vector<uint16_t> pk, pk_lo;
+};
+void pack_stem(const float* w, int prec, StemPack& p, bool* f16_overflow) {
+    p.direct.assign(147 * 64, 0.f);
+    p.pk.assign(64 * AP_STEM_WLD, 0);
+    p.pk_lo.clear();
+    if (prec == AP_PREC_BF16X2) p.pk_lo.assign(64 * AP_STEM_WLD, 0);
     for (int o = 0; o < 64; ++o)
         for (int c = 0; c < 3; ++c)
             for (int r = 0; r < 7; ++r)
-                for (int s = 0; s < 7; ++s) sw[((r * 7 + s) * 3 + c) * 64 + o] = w->data[((o * 3 + c) * 7 + r) * 7 + s];
-    HIP_TRY(upload(h->stem_w, sw.data(), sw.size() * 4));
-    {   // MFMA stem operand: [64][AP_STEM_WLD] bf16, k' = r*32 + s*4 + c (zero elsewhere: 4th channel slot, 8th tap, row pad)
-        std::vector<uint16_t> pk(64 * AP_STEM_WLD, 0);
-        for (int o = 0; o < 64; ++o)
-            for (int c = 0; c < 3; ++c)
-                for (int r = 0; r < 7; ++r)
-                    for (int s2 = 0; s2 < 7; ++s2)
-                        pk[o * AP_STEM_WLD + r * 32 + s2 * 4 + c] = h->h16(w->data[((o * 3 + c) * 7 + r) * 7 + s2]);
-        HIP_TRY(upload(h->stem_wpk, pk.data(), pk.size() * 2));
-        if (h->prec == AP_PREC_BF16X2) {                    // low plane: bf16(w - hi) at the same positions
-            std::vector<uint16_t> pl(64 * AP_STEM_WLD, 0);
-            for (int o = 0; o < 64; ++o)
-                for (int c = 0; c < 3; ++c)
-                    for (int r = 0; r < 7; ++r)
-                        for (int s2 = 0; s2 < 7; ++s2) {
-                            const float wv = w->data[((o * 3 + c) * 7 + r) * 7 + s2];
-                            uint16_t hi, lo;
-                            host_split_parts(wv, &hi, &lo);
-                            pl[o * AP_STEM_WLD + r * 32 + s2 * 4 + c] = lo;
-                        }
-            HIP_TRY(upload(h->stem_wpk_lo, pl.data(), pl.size() * 2));
-        }
+                for (int s = 0; s < 7; ++s) {
+                    const float wv = w[((o * 3 + c) * 7 + r) * 7 + s];
+                    p.direct[((r * 7 + s) * 3 + c) * 64 + o] = wv;
+                    const int k = o * AP_STEM_WLD + r * 32 + s * 4 + c;
+                    p.pk[k] = prec == AP_PREC_F16 ? host_f32_to_f16(wv, f16_overflow) : host_f32_to_bf16(wv);
+                    if (prec == AP_PREC_BF16X2) {
+                        uint16_t hi;
+                        host_split_parts(wv, &hi, &p.pk_lo[k]);
+                    }
+                }
+}
+
+int finalize_trunk(ap_net* h) {
+    const HostTensor* w = find(h, "conv1.weight");
+    if (!w) return fail(AP_ESTATE, "missing tensor conv1.weight");
+    if (w->numel() != 64 * 3 * 49) return fail(AP_ESHAPE, "shape mismatch for conv1.weight");
+    {
+        StemPack sp;
+        pack_stem(w->data.data(), h->prec, sp, &h->f16_overflow);
+        HIP_TRY(upload(h->stem_w, sp.direct.data(), sp.direct.size() * 4));
+        HIP_TRY(upload(h->stem_wpk, sp.pk.data(), sp.pk.size() * 2));
+        if (h->prec == AP_PREC_BF16X2) HIP_TRY(upload(h->stem_wpk_lo, sp.pk_lo.data(), sp.pk_lo.size() * 2));
     }
     std::vector<float> sc, sh;
     int rc = bn_fold(h, "bn1", 64, sc, sh);
@@ -1415,7 +1423,7 @@ int regressor_run(ap_net* h, const RegInputs& in, int B, int iters, int two_view
 // ================================================================================== C ABI
 extern "C" {
 
-const char* ap_version(void) { return "airpose_hip 0.7 (gfx950; abi 10)"; }
+const char* ap_version(void) { return "airpose_hip 0.7 (gfx950; abi 11)"; }
 int ap_abi_version(void) { return AP_ABI_VERSION; }
 const char* ap_last_error(void) { return g_err.c_str(); }
 
@@ -1916,6 +1924,73 @@ int ap_conv_img3_nhwc(int precision, const void* x, const void* wstream, const f
     a.x = x; a.y = y; a.wfrag = wstream; a.scale = scale; a.shift = shift; a.N = N; a.y_tiled = y_tiled != 0;
     HIP_TRY(zero_line(&a.zero));
     HIP_TRY(H16(precision, ap_launch_conv_img3)(a, (hipStream_t)stream));
+    return AP_OK;
+}
+
+// ---- stem and pooling operators: every kernel of stem.hip a trunk pass can launch, through the launch calls the pass makes
+int64_t ap_stem_pack_bytes(int precision) {
+    if (!prec_valid(precision)) return AP_EINVAL;
+    return precision == AP_PREC_FP32 ? 147 * 64 * 4 : (precision == AP_PREC_BF16X2 ? 2 : 1) * 64 * AP_STEM_WLD * 2;
+}
+
+int ap_stem_pack(int precision, const float* w, void* wpacked, void* stream) {
+    if (!prec_valid(precision) || !w || !wpacked) return fail(AP_EINVAL, "ap_stem_pack: precision, w [64][3][7][7] fp32, packed buffer");
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<float> hw(64 * 3 * 49);
+    HIP_TRY(hipMemcpyAsync(hw.data(), w, hw.size() * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    StemPack sp;
+    bool ovf = false;
+    pack_stem(hw.data(), precision, sp, &ovf);
+    if (ovf) return fail(AP_ERANGE, "ap_stem_pack: a weight leaves the fp16 range");
+    if (precision == AP_PREC_FP32) {
+        HIP_TRY(hipMemcpyAsync(wpacked, sp.direct.data(), sp.direct.size() * 4, hipMemcpyHostToDevice, st));
+    } else {
+        const size_t plane = sp.pk.size() * 2;
+        HIP_TRY(hipMemcpyAsync(wpacked, sp.pk.data(), plane, hipMemcpyHostToDevice, st));
+        if (precision == AP_PREC_BF16X2)
+            HIP_TRY(hipMemcpyAsync((char*)wpacked + plane, sp.pk_lo.data(), plane, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));                       // (the host vectors go out of scope)
+    return AP_OK;
+}
+
+int ap_stem_nhwc(int precision, int form, const float* x0, const float* x1, int n_split, const void* wpacked, const float* scale,
+                 const float* shift, void* y, int N, void* stream) {
+    if (!prec_valid(precision) || !wpacked || !scale || !shift || !y || N <= 0 || n_split < 0 || n_split > N || (n_split > 0 && !x0) ||
+        (n_split < N && !x1))
+        return fail(AP_EINVAL, "ap_stem_nhwc: bad argument (x0: the first n_split images, x1: the other N - n_split)");
+    const bool half = prec_half(precision);
+    if (form < 0 || form > (half ? 2 : precision == AP_PREC_BF16X2 ? 1 : 0))
+        return fail(AP_EINVAL, "ap_stem_nhwc: form 0 (un-pooled; every precision), 1 (strip kernel; 16-bit, bf16x2), 2 (persistent kernel; 16-bit)");
+    hipStream_t st = (hipStream_t)stream;
+    const int n1 = N - n_split;
+    if (half) {
+        if (form == 0) HIP_TRY(H16(precision, ap_launch_stem_conv_mfma)(x0, x1, n_split, wpacked, scale, shift, y, N, st));
+        else HIP_TRY(H16(precision, ap_launch_stem_pool)(x0, x1, n_split, wpacked, scale, shift, y, N, nullptr, form, st, nullptr));
+    } else if (precision == AP_PREC_BF16X2) {
+        const void* wlo = (const char*)wpacked + (size_t)64 * AP_STEM_WLD * 2;
+        if (form == 0) HIP_TRY(k_bf16::ap_launch_stem_conv_mfma_split(x0, x1, n_split, wpacked, wlo, scale, shift, y, N, st));
+        else HIP_TRY(k_bf16::ap_launch_stem_pool_split(x0, x1, n_split, wpacked, wlo, scale, shift, y, N, st));
+    } else {
+        if (n_split) HIP_TRY(k_bf16::ap_launch_stem_conv(x0, (const float*)wpacked, scale, shift, y, n_split, K_F32, st));
+        if (n1)
+            HIP_TRY(k_bf16::ap_launch_stem_conv(x1, (const float*)wpacked, scale, shift, (char*)y + (size_t)n_split * 112 * 112 * 64 * 4, n1,
+                                                K_F32, st));
+    }
+    return AP_OK;
+}
+
+int ap_maxpool_nhwc(int precision, const void* x, void* y, int N, void* stream) {
+    if (!prec_valid(precision) || !x || !y || N <= 0) return fail(AP_EINVAL, "ap_maxpool_nhwc: bad argument");
+    HIP_TRY(H16(precision, ap_launch_maxpool)(x, y, N, prec_kind(precision), nullptr, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_avgpool_nhwc(int precision, const void* x, float* y, int N, int C, void* stream) {
+    if (!prec_valid(precision) || !x || !y || N <= 0) return fail(AP_EINVAL, "ap_avgpool_nhwc: bad argument");
+    if (C <= 0 || C % (precision == AP_PREC_FP32 ? 128 : 256)) return fail(AP_ESHAPE, "ap_avgpool_nhwc: C a multiple of 256 (fp32: 128)");
+    HIP_TRY(H16(precision, ap_launch_avgpool)(x, y, N, C, prec_kind(precision), nullptr, (hipStream_t)stream));
     return AP_OK;
 }
 

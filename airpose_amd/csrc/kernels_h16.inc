@@ -47,7 +47,8 @@ int ap_conv_pw_grid(long M, int Cout, int n_cu);
 hipError_t ap_launch_conv_pw_pack(const void* w, void* dst, int Cin, int Cout, int wld, hipStream_t st);
 hipError_t ap_launch_conv_pw(const PwArgs& a, hipStream_t st);
 
-// conv 7x7/2 p3 (3->64) + BN + ReLU from NCHW fp32 into NHWC T [N][112][112][64]
+// conv 7x7/2 p3 (3->64) + BN + ReLU from NCHW fp32 into NHWC fp32 [N][112][112][64]: kind = K_F32 only (the exact fp32 FMA chain of
+// the fp32 parity mode; defined in the bf16 set)
 hipError_t ap_launch_stem_conv(const float* x_nchw, const float* w_k147x64, const float* scale, const float* shift,
                                void* y, int n_img, int kind, hipStream_t st);
 // bf16 MFMA stem: images [0, n_split) come from x0, the rest from x1 (both views in one pass);

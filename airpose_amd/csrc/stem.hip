@@ -17,11 +17,10 @@ constexpr int IMG = 224, SO = 112, PO = 56, SC = 64;
 
 // ------------------------------------------------------------------------------------------------
 // Direct (VALU, exact fp32 FMA chain) stem: one thread = one output pixel x 64 channels.
-// Used by the fp32 parity path; the bf16 throughput path uses the MFMA stem below.
-template <typename T>
+// The fp32 parity path only (fp32 storage): the 16-bit and split-bf16 modes use the MFMA stems below.
 __global__ void __launch_bounds__(256) stem_direct_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                           const float* __restrict__ scale,
-                                                          const float* __restrict__ shift, T* __restrict__ y) {
+                                                          const float* __restrict__ shift, float* __restrict__ y) {
     constexpr int TS = 16, PS = 2 * TS + 5, PLD = PS + 1;       // 37-wide patch, padded rows
     __shared__ __attribute__((aligned(16))) float wsm[147 * 64];
     __shared__ float patch[3 * PS * PLD];
@@ -58,33 +57,13 @@ __global__ void __launch_bounds__(256) stem_direct_kernel(const float* __restric
             }
     const int oy = ty0 + ty, ox = tx0 + tx;
     if (oy >= SO || ox >= SO) return;
-    T* dst = y + (((size_t)n * SO + oy) * SO + ox) * SC;
+    float* dst = y + (((size_t)n * SO + oy) * SO + ox) * SC;
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
         float v[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = fmaxf(acc[4 * q + e] * scale[4 * q + e] + shift[4 * q + e], 0.f);
-        if constexpr (sizeof(T) == 2) {
-            uint2 o;
-            o.x = pack_bf16x2(v[0], v[1]);
-            o.y = pack_bf16x2(v[2], v[3]);
-            *(uint2*)(dst + 4 * q) = o;
-        } else if constexpr (ElemKind<T>::KIND == K_SPLIT) {
-            if (q & 1) {                                    // groups of 8 channels: [8 hi | 8 lo]
-                float v8[8];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v8[e] = fmaxf(acc[4 * (q - 1) + e] * scale[4 * (q - 1) + e] + shift[4 * (q - 1) + e], 0.f);
-                    v8[4 + e] = v[e];
-                }
-                u32x4 hi, lo;
-                split8_pack(v8, hi, lo);
-                *(u32x4*)(dst + 4 * (q - 1)) = hi;
-                *(u32x4*)(dst + 4 * q) = lo;
-            }
-        } else {
-            *(float4*)(dst + 4 * q) = make_float4(v[0], v[1], v[2], v[3]);
-        }
+        *(float4*)(dst + 4 * q) = make_float4(v[0], v[1], v[2], v[3]);
     }
 }
 
@@ -1109,20 +1088,14 @@ hipError_t ap_launch_preprocess(const unsigned char* frames, size_t frame_stride
 }
 #endif
 
+#ifndef AP_F16                                               // (fp32 storage: the bf16 set carries it, the fp16 set does not)
 hipError_t ap_launch_stem_conv(const float* x, const float* w, const float* scale, const float* shift, void* y,
                                int n_img, int kind, hipStream_t st) {
-    dim3 grid(SO / 16, SO / 16, n_img);
-    if (kind == K_BF16)
-        hipLaunchKernelGGL(stem_direct_kernel<bf16_t>, grid, dim3(256), 0, st, x, w, scale, shift, (bf16_t*)y);
-#ifndef AP_F16                                               // (the fp16 set carries the 16-bit kind only)
-    else if (kind == K_SPLIT)
-        hipLaunchKernelGGL(stem_direct_kernel<bsplit_t>, grid, dim3(256), 0, st, x, w, scale, shift, (bsplit_t*)y);
-    else if (kind == K_F32)
-        hipLaunchKernelGGL(stem_direct_kernel<float>, grid, dim3(256), 0, st, x, w, scale, shift, (float*)y);
-#endif
-    else return hipErrorInvalidValue;
+    if (kind != K_F32) return hipErrorInvalidValue;          // 16-bit and split-bf16 storage: the MFMA stems
+    hipLaunchKernelGGL(stem_direct_kernel, dim3(SO / 16, SO / 16, n_img), dim3(256), 0, st, x, w, scale, shift, (float*)y);
     return hipGetLastError();
 }
+#endif
 
 hipError_t ap_launch_stem_conv_mfma(const float* x0, const float* x1, int n_split, const void* w_packed,
                                     const float* scale, const float* shift, void* y, int n_img, hipStream_t st) {

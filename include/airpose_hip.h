@@ -50,11 +50,12 @@ typedef struct ap_net ap_net;     /* ResNet-50 trunk + IEF regressor */
 typedef struct ap_smplx ap_smplx; /* SMPL-X body model */
 
 /* ABI number of this header: bumped whenever an exported signature changes or an entry point is added or removed
- * (10: ap_smplx_bwd, ap_batch_rodrigues_bwd -- the adjoints of ap_smplx_fwd and of lbs.batch_rodrigues;
+ * (11: ap_stem_pack_bytes / ap_stem_pack / ap_stem_nhwc, ap_maxpool_nhwc, ap_avgpool_nhwc -- operator forms of the stem and pooling kernels;
+ *  10: ap_smplx_bwd, ap_batch_rodrigues_bwd -- the adjoints of ap_smplx_fwd and of lbs.batch_rodrigues;
  *  8: round 6 -- ap_net_parity_probe, ap_net_range_peek / _mark_next / _slot, ap_regressor_feat_part / _step_local / _step_finish;
  *  7: ap_conv_pw_*, ap_block_img_*; 6: ap_set_pair_groups removed).  A binding built against another number must refuse to load
  * the library (airpose_amd/_native.py does). */
-#define AP_ABI_VERSION 10
+#define AP_ABI_VERSION 11
 const char* ap_version(void);
 int ap_abi_version(void);
 const char* ap_last_error(void);
@@ -272,6 +273,32 @@ int64_t ap_conv_img3_stream_bytes(void);
 int ap_conv_img3_pack(int precision, const void* w2, void* wstream, void* stream);
 int ap_conv_img3_nhwc(int precision, const void* x, const void* wstream, const float* scale, const float* shift, void* y, int N,
                       int y_tiled, void* stream);
+
+/* The stem of the trunk (conv1 7 x 7 stride 2 pad 3, 3 -> 64 channels, + bn1 + ReLU [+ MaxPool2d(3, 2, 1)]; model_copenet.py:57-61,
+ * 163-166) as an operator, through the launches a trunk pass makes (stem.hip).  Exposed so the kernels can be unit-tested.
+ *   ap_stem_pack   w: conv1.weight [64][3][7][7] fp32 on the device -> wpacked (caller-owned, ap_stem_pack_bytes(precision) bytes), by
+ *                  the SAME host packing ap_net_finalize runs: fp32 [147][64] (AP_PREC_FP32), [64][240] 16-bit rows with
+ *                  k' = r*32 + s*4 + c (AP_PREC_BF16 / AP_PREC_F16), the high then the low bf16 plane of those rows (AP_PREC_BF16X2).
+ *                  Synchronises `stream`.  AP_ERANGE: a weight leaves the fp16 range (AP_PREC_F16).
+ *   ap_stem_nhwc   fp32 NCHW crops as two views -- images [0, n_split) from x0, [n_split, N) from x1, as ap_trunk_fwd_twoview hands
+ *                  them over (a view without images may be NULL) -- scale / shift [64] fp32 (the folded bn1) -> y in the storage
+ *                  type of `precision` (split-bf16: planar groups of 8 channels, as for ap_conv2d_nhwc).  form selects the kernel:
+ *                    0  un-pooled, y [N][112][112][64]: stem_direct_kernel (AP_PREC_FP32), stem_mfma_kernel (AP_PREC_BF16 / _F16),
+ *                       stem_mfma_split_kernel (AP_PREC_BF16X2)
+ *                    1  fused with the max-pool, one workgroup per strip of two pooled rows, y [N][56][56][64]: stem_pool_kernel
+ *                       (16-bit), stem_pool_split_kernel (AP_PREC_BF16X2)
+ *                    2  fused with the max-pool, persistent workgroups, y [N][56][56][64]: stem_pool2_kernel (16-bit; the trunk's default)
+ *                  The fp16 range sentinel is not connected (a handle's business: ap_net_set_range_check).
+ * ap_maxpool_nhwc: MaxPool2d(3, stride 2, pad 1), x [N][112][112][64] -> y [N][56][56][64] in the storage type of `precision`.  Domain:
+ *                  x >= 0 (post-ReLU values, as in the trunk); the result is one of the inputs, bit for bit.
+ * ap_avgpool_nhwc: AvgPool2d(7) + view(B, -1) (model_copenet.py:66, 173-174): x [N][49][C] in the storage type of `precision` -> y [N][C]
+ *                  fp32; C a multiple of 256 (fp32: 128).  A fixed summation order: the same bits on every run. */
+int64_t ap_stem_pack_bytes(int precision);
+int ap_stem_pack(int precision, const float* w, void* wpacked, void* stream);
+int ap_stem_nhwc(int precision, int form, const float* x0, const float* x1, int n_split, const void* wpacked, const float* scale,
+                 const float* shift, void* y, int N, void* stream);
+int ap_maxpool_nhwc(int precision, const void* x, void* y, int N, void* stream);
+int ap_avgpool_nhwc(int precision, const void* x, float* y, int N, int C, void* stream);
 
 /* Stride-2 3x3 convolution of layer2.0 (128 -> 128 channels, 56 x 56 -> 28 x 28) + bn2 + ReLU in polyphase form, a quarter of an
  * output image per workgroup (conv_s2p.hip; replaces conv2 of the stage's first Bottleneck, model_copenet.py:32-34 with :18).

@@ -1816,6 +1816,45 @@ def test_preprocess_crops_matches_oracle(dev):
         preprocess_crops(torch.from_numpy(frames).to(dev), torch.tensor([[0, 300, 0, 10]] * 5))   # outside the frame
 
 
+PREPROCESS_CROPS = [  # (y0, y1, x0, x1) on a 1080 x 1920 frame
+    (0, 1080, 0, 1920), (856, 1080, 1696, 1920),            # the whole frame; a 224 x 224 crop in the bottom right corner
+    (300, 524, 800, 1024),                                   # exactly 224 x 224: an identity resample
+    (0, 1, 0, 1), (5, 7, 9, 11), (100, 101, 200, 300), (100, 102, 200, 201), (500, 700, 1000, 1001), (40, 42, 60, 284),   # h or w of 1, 2
+    (10, 235, 20, 243), (1, 450, 7, 10), (600, 1049, 3, 6),  # 225 x 223, 449 x 3: int(scale w) truncates
+    (30, 254, 50, 271), (200, 300, 400, 437), (7, 230, 1000, 1223), (0, 333, 1700, 1920),   # odd padding (221, 82 -> 83 columns; 223; 148)
+]
+
+
+@pytest.mark.parametrize("bgr", [True, False])
+def test_preprocess_crops_geometry_sweep(dev, bgr):
+    """The input pipeline at the production frame size over crop geometries: one- and two-pixel crops, the identity resample,
+    sizes at which int(scale w) truncates, odd padding; both channel orders; one shared frame and a frame per sample."""
+    from airpose_amd.utils import preprocess_crops
+    from oracle import preprocess_ref as P
+    rs = np.random.RandomState(19)
+    frame = (rs.rand(1080, 1920, 3) * 255).astype(np.uint8)
+    crops = np.array(PREPROCESS_CROPS)
+    as_bgr = lambda f: f if bgr else np.ascontiguousarray(f[:, :, ::-1])       # the oracle takes cv2.imread's order
+    img, scale, pad = preprocess_crops(torch.from_numpy(frame).to(dev), torch.from_numpy(crops), bgr=bgr)
+    for i, c in enumerate(PREPROCESS_CROPS):
+        want, s, p = P.preprocess(as_bgr(frame), c)
+        assert abs(scale[i].item() - s) < 1e-6 * max(1.0, s) and pad[i].tolist() == p, (i, c)
+        assert np.abs(img[i].cpu().numpy() - want).max() < 5e-5, (i, c)
+    # identity resample: the normalised pixels themselves, to fp32 rounding (three roundings of values below 4.5)
+    y0, y1, x0, x1 = PREPROCESS_CROPS[2]
+    px = frame[y0:y1, x0:x1, ::-1] if bgr else frame[y0:y1, x0:x1]
+    exact = (px.astype(np.float64).transpose(2, 0, 1) / 255.0 - P.MEAN[:, None, None]) / P.STD[:, None, None]
+    assert pad[2].tolist() == [0, 0] and np.abs(img[2].cpu().numpy() - exact).max() < 1e-6
+    # a frame per sample: the same crops on four different frames
+    sel = [0, 3, 9, 12]
+    frames = (rs.rand(len(sel), 1080, 1920, 3) * 255).astype(np.uint8)
+    img4, scale4, pad4 = preprocess_crops(torch.from_numpy(frames).to(dev), torch.from_numpy(crops[sel]), bgr=bgr)
+    for j, i in enumerate(sel):
+        want, s, p = P.preprocess(as_bgr(frames[j]), PREPROCESS_CROPS[i])
+        assert abs(scale4[j].item() - s) < 1e-6 * max(1.0, s) and pad4[j].tolist() == p, (j, i)
+        assert np.abs(img4[j].cpu().numpy() - want).max() < 5e-5, (j, i)
+
+
 def test_rotation_matrix_to_angle_axis_matches_oracle(dev):
     """pred_angles conversion (tgm 0.1.2 semantics): all four trace branches, (N,3,3) and the caller's (N,3,4) form."""
     from airpose_amd.geometry import rotation_matrix_to_angle_axis
