@@ -25,6 +25,11 @@ SIGNATURES = {
     "apg_head_fwd": (_i, [_i, _vp, _vp, _vpp, _ip] + [_vp] * 8 + [_u64, _f, _f] + [_vp] * 3 + [_vpp, _vpp, _vp]),
     "apg_head_bwd_workspace_bytes": (_i64, [_i, _i]),
     "apg_head_bwd": (_i, [_i] + [_vp] * 7 + [_u64, _f, _f, _vpp, _vpp, _vpp, _vp, _i64, _vp]),
+    # the generic view-local head (head_local_grad.hip)
+    "apg_head_local_fwd": (_i, [_i, _vp, _i, _vpp, _ip, _ip] + [_vp] * 4 + [_i, _vpp, _vpp, _ip, _ip, _u64, _f, _f] + [_vp] * 4 +
+                           [_vpp, _vp]),
+    "apg_head_local_bwd_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "apg_head_local_bwd": (_i, [_i, _i, _ip, _ip, _i, _ip, _ip] + [_vp] * 6 + [_u64, _f, _f, _vpp, _vpp, _vp, _vpp, _vp, _i64, _vp]),
     "apg_rot6d_to_rotmat_bwd": (_i, [_vp, _i, _vp, _vp, _vp]),
     "apg_perspective_projection_bwd": (_i, [_vp, _i, _i, _vp, _vp, _f, _f] + [_vp] * 5 + [_vp]),
     "apg_transform_points_bwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),

@@ -8,8 +8,9 @@ same outputs, same sub-module / buffer names, hence the same 331 ``state_dict`` 
 work unchanged.  The nn.Conv2d / nn.BatchNorm2d / nn.Linear children are parameter containers
 only: all compute goes through the C ABI of libairpose_hip.so (hand-written gfx950 kernels).
 Inference (eval) only, except the two-view IEF head: forward_ief / forward_reg are differentiable in train mode or with
-inputs that require grad (head_grad.py, libairpose_grad.so), and, after set_trunk_trainable(True), the ResNet-50 trunk:
-forward_feat_ext and forward (trunk_grad.py).  There is no CPU or eager fallback.
+inputs that require grad (head_grad.py, libairpose_grad.so), after set_trunk_trainable(True) the ResNet-50 trunk:
+forward_feat_ext and forward (trunk_grad.py), and after set_trainable(True) the view-local regressor_step and the hmr / muhmr /
+copenet_singleview heads (head_local_grad.py).  There is no CPU or eager fallback.
 """
 import ctypes
 import threading
@@ -19,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as N
-from . import head_grad, trunk_grad
+from . import head_grad, head_local_grad, trunk_grad
 
 
 class Bottleneck(nn.Module):
@@ -233,13 +234,49 @@ class copenet(nn.Module):
         self._trunk_precision = precision
         return self
 
+    def set_trainable(self, on=True, trunk=None):
+        """Opt in (default off) to the view-local / baseline training path (head_local_grad.py, libairpose_grad.so).  When on:
+          * two-view copenet: regressor_step(xf, bb, pose, betas, partner, seed=None) is differentiable, with gradients to xf, bb,
+            pose, betas AND partner (copenet_sep is built from it); `trunk`, when given, is forwarded to set_trunk_trainable;
+          * hmr / muhmr / copenet_singleview: forward_reg is differentiable on the live fc1 / fc2 / decpose / decshape / deccam, and
+            with trunk="fp32" | "bf16" forward / forward_feat_ext run the trainable trunk (trunk_grad.py; train-mode BatchNorm in
+            train mode).  With trunk=None their forward stays the inference path.
+        The differentiable path is taken in train mode, or when grad is enabled and an input or a head parameter requires grad;
+        eval mode under no_grad keeps the inference kernels.  When off, nothing changes.  A runtime switch, not part of state_dict."""
+        if trunk not in (None, "fp32", "bf16"):
+            raise RuntimeError("set_trainable: trunk is None, \"fp32\" or \"bf16\", got %r" % (trunk,))
+        self._trainable = bool(on)
+        if self.variant == 0:
+            if trunk is not None:
+                self.set_trunk_trainable(on, trunk)
+        else:
+            self._local_trunk = trunk if on else None
+        return self
+
+    LOCAL_HEAD = ("fc1", "fc2", "decpose", "decshape")       # the parameters of the view-local head (the baselines add deccam)
+
+    def _local_trains(self, *inputs):
+        """The view-local head takes the differentiable path: after set_trainable(True), in train mode, or when grad is enabled
+        and an input or a head parameter requires grad."""
+        if not getattr(self, "_trainable", False):
+            return False
+        if self.training:
+            return True
+        return torch.is_grad_enabled() and (any(isinstance(t, torch.Tensor) and t.requires_grad for t in inputs) or
+                                            any(p.requires_grad for m in self.LOCAL_HEAD for p in getattr(self, m).parameters()))
+
     @property
     def trunk_precision(self):
-        """The arithmetic of the trainable trunk: "fp32" or "bf16" (set_trunk_trainable)."""
+        """The arithmetic of the trainable trunk: "fp32" or "bf16" (set_trunk_trainable; set_trainable on the baselines)."""
+        if self.variant != 0:
+            return getattr(self, "_local_trunk", None) or "fp32"
         return getattr(self, "_trunk_precision", "fp32")
 
     def _trunk_trains(self, *xs):
-        if self.variant != 0 or not getattr(self, "_trunk_trainable", False):
+        if self.variant != 0:                                # the baselines: set_trainable(True, trunk=...)
+            if not getattr(self, "_trainable", False) or getattr(self, "_local_trunk", None) is None:
+                return False
+        elif not getattr(self, "_trunk_trainable", False):
             return False
         if self.training:
             return True
@@ -381,9 +418,12 @@ class copenet(nn.Module):
         return self.forward_ief(xf0, xf1, bb0, bb1, pred_position0, pred_position1, th0, th1,
                                 pred_shape0, pred_shape1, iters=1)
 
-    def regressor_step(self, xf, bb, pose, betas, partner):
+    def regressor_step(self, xf, bb, pose, betas, partner, seed=None):
         """One forward_reg evaluation for ONE view with the partner's (art_pose | shape) (B,136) supplied by
-        the caller -- the view-split / on-drone exchange step (README.md:238-241)."""
+        the caller -- the view-split / on-drone exchange step (README.md:238-241).  Differentiable after set_trainable(True)
+        (see there); `seed` then fixes the dropout masks (default: a fresh one, recorded in last_dropout_seed)."""
+        if self._local_trains(xf, bb, pose, betas, partner):
+            return head_local_grad.regressor_step(self, xf, bb, pose, betas, partner, seed)
         self._check_eval()
         dev = self._dev(xf)
         B = xf.shape[0]

@@ -20,6 +20,14 @@ class copenet_sep(nn.Module):
         self.copenet0 = copenet(block, layers, smpl_mean_params, precision=precision)
         self.copenet1 = copenet(block, layers, smpl_mean_params, precision=precision)
 
+    def set_trainable(self, on=True, trunk=None):
+        """Opt in (default off) to training: forwards to both sub-models (copenet.set_trainable).  forward_reg / forward_ief /
+        forward then run two differentiable regressor_step calls per evaluation exactly in the order below, so a loss on view 1
+        reaches copenet0's parameters through view 0's new shape inside view 1's partner columns."""
+        self.copenet0.set_trainable(on, trunk)
+        self.copenet1.set_trainable(on, trunk)
+        return self
+
     def forward(self, x0, x1, bb0, bb1, init_position0, init_position1, init_theta0=None, init_theta1=None,
                 init_shape0=None, init_shape1=None, iters=3):
         xf0 = self.copenet0.forward_feat_ext(x0)            # :163-164

@@ -8,6 +8,7 @@ reference module; compute through ap_singleview_fwd (libairpose_hip.so): trunk +
 import torch
 
 from . import _native as N
+from . import head_local_grad
 from .copenet_model import Bottleneck, copenet as _copenet_base
 
 
@@ -21,6 +22,17 @@ class copenet(_copenet_base):
         self.register_buffer("init_position", torch.tensor([[0.0, 0.0, 10.0 / 0.05]], dtype=torch.float32))
 
     def forward(self, x, bb, init_position, init_cam=None, init_theta=None, init_shape=None, iters=3):
+        """After set_trainable(True, trunk="fp32" | "bf16"), in train mode (or eval mode with grad) it runs as the reference does
+        (:112-140): the trainable trunk, then `iters` differentiable forward_reg evaluations."""
+        if self._trunk_trains(x):
+            if int(iters) < 1:
+                raise RuntimeError("iters must be >= 1 (forward always evaluates the regressor once)")
+            B = x.shape[0]
+            xf = self.forward_feat_ext(x)
+            theta = (self.init_pose if init_theta is None else init_theta)[:, :132]
+            pose = torch.cat([init_position.to(xf), theta.to(xf).expand(B, -1)], 1)
+            shape = self.init_shape if init_shape is None else init_shape
+            return head_local_grad.singleview_forward_reg(self, xf, bb, pose, shape, iters)
         self._check_eval()
         dev = self._dev(x)
         if x.dim() != 4 or x.shape[1:] != (3, 224, 224):
@@ -42,7 +54,10 @@ class copenet(_copenet_base):
 
     def forward_reg(self, xf, bb, pred_pose, pred_shape, iters=1):
         """One regressor evaluation from trunk features (model_copenet_singleview.py:159-170):
-        (xf (B,2048), bb (B,3), pose (B,135) = trans3 | 6-D, shape (B,10)) -> the updated (pose, shape)."""
+        (xf (B,2048), bb (B,3), pose (B,135) = trans3 | 6-D, shape (B,10)) -> the updated (pose, shape).  Differentiable after
+        set_trainable(True)."""
+        if self._local_trains(xf, bb, pred_pose, pred_shape):
+            return head_local_grad.singleview_forward_reg(self, xf, bb, pred_pose, pred_shape, iters)
         self._check_eval()
         dev = self._dev(xf)
         B = xf.shape[0]

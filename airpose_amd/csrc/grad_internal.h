@@ -1,4 +1,4 @@
-// Internal helpers shared by the sources of libairpose_grad.so (head_grad.hip, geom_grad.hip, trunk_grad.hip).
+// Internal helpers shared by the sources of libairpose_grad.so (head_grad.hip, head_local_grad.hip, geom_grad.hip, trunk_grad.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -27,3 +27,52 @@ __host__ __device__ __forceinline__ bool apg_keep(uint64_t seed, int layer, int 
     const float u = (float)(uint32_t)(h >> 40) * (1.0f / 16777216.0f);
     return u >= p;
 }
+
+// ---------------------------------------------------------------------------------------------
+// apg_gemm_kernel (head_grad.hip) for the other sources of the library: C = A B with one 64 x 64 tile per workgroup, K reduced in
+// index order inside that workgroup (no split, no atomics), and one of the epilogues below.
+enum {
+    APG_EPI_STORE = 0,                   // C[m * ldc + n] = acc
+    APG_EPI_HID_FWD = 1,                 // C = dropout(acc + bias[n]) of (seed, layer, row m, column n)
+    APG_EPI_DEC_FWD = 2,                 // the two-view decoders: out_v[b * ldo + n] = base[m * ldbase + n] + (acc + bias[n])
+    APG_EPI_HID_BWD = 3,                 // C = dropout'(acc)
+    APG_EPI_DEC_LOCAL = 4                // packed decoders: column n of decoder d = the one with doff[d] <= n < doff[d + 1], j = n - doff[d]:
+                                         // dout[d][m * (doff[d + 1] - doff[d]) + j] = base[m * ldbase + dres[d] + j] + (acc + bias[n])
+};
+
+struct ApgGemmArgs {
+    const float* A;                      // A(m, k) = A[m * sam + k * sak]
+    long long sam, sak;
+    const float* B;                      // B(k, n) = B[k * sbk + n * sbn]
+    long long sbk, sbn;
+    int M, N, K;
+    int epi;
+    float* C;                            // EPI_STORE / EPI_HID_*: C[m * ldc + n]
+    int ldc;
+    const float* bias;                   // EPI_HID_FWD / EPI_DEC_*: + bias[n]
+    uint64_t seed;                       // EPI_HID_*: dropout of (layer, row m, column n)
+    int layer;
+    float p, scale;
+    int nb;                              // EPI_DEC_FWD: rows per view; out_v[b * ldo + n] = base[m * ldbase + n] + acc + bias[n]
+    float* out0;
+    float* out1;
+    int ldo;
+    const float* base;                   // EPI_DEC_*
+    int ldbase;
+    int ndec;                            // EPI_DEC_LOCAL: decoders, their first packed column (doff[ndec] = N), residual column, output
+    int doff[4];
+    int dres[3];
+    float* dout[3];
+};
+
+// A / B given by their two strides (one of each pair is 1); EPI_STORE, no dropout
+__attribute__((visibility("hidden"))) ApgGemmArgs apg_gemm_args(const float* A, long long sam, long long sak, const float* B,
+                                                                long long sbk, long long sbn, int M, int N, int K);
+// epi = APG_EPI_HID_FWD / APG_EPI_HID_BWD with the keep scale of p
+__attribute__((visibility("hidden"))) void apg_gemm_set_dropout(ApgGemmArgs& g, int epi, uint64_t seed, int layer, float p);
+__attribute__((visibility("hidden"))) hipError_t apg_gemm_launch(const ApgGemmArgs& g, hipStream_t st);
+// out[c] = sum over rows of x[r * ld + c] in two fixed-order passes (chunks of APG_CS_ROWS rows in row order, then the chunks in
+// order); part: ceil(rows / APG_CS_ROWS) * cols floats
+constexpr int APG_CS_ROWS = 32;
+__attribute__((visibility("hidden"))) hipError_t apg_colsum(const float* x, int rows, int cols, int ld, float* part, float* out,
+                                                            hipStream_t st);

@@ -21,7 +21,7 @@ constexpr int XC = 2332;                 // fc1 input width
 constexpr int XF = 2048;                 // trunk features
 constexpr int HID = 1024;
 constexpr int NPOSE = 135, NSHAPE = 10, NDEC = NPOSE + NSHAPE;
-constexpr int CS_ROWS = 32;              // rows per partial of the column sums
+constexpr int CS_ROWS = APG_CS_ROWS;     // rows per partial of the column sums
 
 // state inputs of one view: bb, pos, orient, art, shape (column offsets inside the 284 state columns)
 __constant__ const int k_st_off[5] = {0, 3, 6, 12, 138};
@@ -32,28 +32,10 @@ struct StatePtrs {
     int ld[2][5];
 };
 
-enum { EPI_STORE = 0, EPI_HID_FWD = 1, EPI_DEC_FWD = 2, EPI_HID_BWD = 3 };
+enum { EPI_STORE = APG_EPI_STORE, EPI_HID_FWD = APG_EPI_HID_FWD, EPI_DEC_FWD = APG_EPI_DEC_FWD, EPI_HID_BWD = APG_EPI_HID_BWD,
+       EPI_DEC_LOCAL = APG_EPI_DEC_LOCAL };
 
-struct GemmArgs {
-    const float* A;                      // A(m, k) = A[m * sam + k * sak]
-    long long sam, sak;
-    const float* B;                      // B(k, n) = B[k * sbk + n * sbn]
-    long long sbk, sbn;
-    int M, N, K;
-    int epi;
-    float* C;                            // EPI_STORE / EPI_HID_*: C[m * ldc + n]
-    int ldc;
-    const float* bias;                   // EPI_HID_FWD / EPI_DEC_FWD: + bias[n]
-    uint64_t seed;                       // EPI_HID_*: dropout of (layer, row m, column n)
-    int layer;
-    float p, scale;
-    int nb;                              // EPI_DEC_FWD: rows per view; out_v[b * ldo + n] = base[m * ldbase + n] + acc + bias[n]
-    float* out0;
-    float* out1;
-    int ldo;
-    const float* base;
-    int ldbase;
-};
+typedef ApgGemmArgs GemmArgs;            // grad_internal.h
 
 // A: AK = K contiguous (sak == 1), else M contiguous (sam == 1).  B: BN = N contiguous (sbn == 1), else K contiguous.
 // The tile loaders map consecutive threads to consecutive addresses in either case.
@@ -131,6 +113,11 @@ __global__ void __launch_bounds__(256) apg_gemm_kernel(const GemmArgs g) {
                     g.C[(long long)row * g.ldc + col] = apg_keep(g.seed, g.layer, row, col, g.p) ? v * g.scale : 0.f;
                 } else if (g.epi == EPI_HID_BWD) {
                     g.C[(long long)row * g.ldc + col] = apg_keep(g.seed, g.layer, row, col, g.p) ? v * g.scale : 0.f;
+                } else if (g.epi == EPI_DEC_LOCAL) {
+                    int d = 0;
+                    while (d + 1 < g.ndec && col >= g.doff[d + 1]) ++d;
+                    const int j = col - g.doff[d], nd = g.doff[d + 1] - g.doff[d];
+                    g.dout[d][(long long)row * nd + j] = g.base[(long long)row * g.ldbase + g.dres[d] + j] + (v + g.bias[col]);
                 } else {                                         // EPI_DEC_FWD
                     const int vw = row >= g.nb, bi = row - vw * g.nb;
                     float* o = vw ? g.out1 : g.out0;
@@ -297,6 +284,17 @@ BwdLayout bwd_layout(int B, int need_gxf) {
 }
 
 }  // namespace
+
+// the product, its dropout epilogues and the column sums for the library's other sources (grad_internal.h)
+ApgGemmArgs apg_gemm_args(const float* A, long long sam, long long sak, const float* B, long long sbk, long long sbn, int M,
+                          int N, int K) {
+    return gemm_args(A, sam, sak, B, sbk, sbn, M, N, K);
+}
+void apg_gemm_set_dropout(ApgGemmArgs& g, int epi, uint64_t seed, int layer, float p) { set_dropout(g, epi, seed, layer, p); }
+hipError_t apg_gemm_launch(const ApgGemmArgs& g, hipStream_t st) { return launch_gemm(g, st); }
+hipError_t apg_colsum(const float* x, int rows, int cols, int ld, float* part, float* out, hipStream_t st) {
+    return colsum(x, rows, cols, ld, part, out, st);
+}
 
 #define APG_TRY(expr)                                                                               \
     do {                                                                                            \

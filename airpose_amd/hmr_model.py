@@ -9,6 +9,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as N
+from . import geometry, head_local_grad
 from .copenet_model import Bottleneck, copenet as _copenet_base
 
 
@@ -20,7 +21,21 @@ class copenet(_copenet_base):
     def _npose_out(npose):
         return 22 * 6
 
+    LOCAL_HEAD = ("fc1", "fc2", "decpose", "decshape", "deccam")
+
     def forward(self, x, init_cam=None, init_theta=None, init_shape=None, iters=3):
+        """After set_trainable(True, trunk="fp32" | "bf16"), in train mode (or eval mode with grad) it runs as the reference does
+        (:112-141): the trainable trunk, `iters` differentiable forward_reg evaluations, rot6d_to_rotmat."""
+        if self._trunk_trains(x):
+            if int(iters) < 1:
+                raise RuntimeError("iters must be >= 1 (forward always evaluates the regressor once)")
+            B = x.shape[0]
+            xf = self.forward_feat_ext(x)
+            pose = (self.init_pose if init_theta is None else init_theta)[:, :132]
+            shape = self.init_shape if init_shape is None else init_shape
+            cam = self.init_cam if init_cam is None else init_cam
+            pose, shape, cam = head_local_grad.hmr_forward_reg(self, xf, pose, shape, cam, iters)
+            return geometry.rot6d_to_rotmat(pose).view(B, 22, 3, 3), shape, cam
         self._check_eval()
         dev = self._dev(x)
         if x.dim() != 4 or x.shape[1:] != (3, 224, 224):
@@ -41,7 +56,9 @@ class copenet(_copenet_base):
 
     def forward_reg(self, xf, pred_pose, pred_shape, pred_cam, iters=1):
         """One regressor evaluation from trunk features (model_hmr.py:160-172): (xf (B,2048), pose (B,132) 6-D,
-        shape (B,10), cam (B,3)) -> the updated (pose, shape, cam)."""
+        shape (B,10), cam (B,3)) -> the updated (pose, shape, cam).  Differentiable after set_trainable(True)."""
+        if self._local_trains(xf, pred_pose, pred_shape, pred_cam):
+            return head_local_grad.hmr_forward_reg(self, xf, pred_pose, pred_shape, pred_cam, iters)
         self._check_eval()
         dev = self._dev(xf)
         B = xf.shape[0]

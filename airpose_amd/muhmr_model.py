@@ -9,11 +9,13 @@ Same state_dict keys as the reference module; compute through ap_muhmr_fwd (liba
 import torch
 
 from . import _native as N
+from . import head_local_grad
 from .copenet_model import Bottleneck, copenet as _copenet_base
 
 
 class copenet(_copenet_base):
     variant = 3
+    LOCAL_HEAD = ("fc1", "fc2", "decpose", "decshape", "deccam")
     fc1_extra = 3 + 22 * 6 + 10 + 21 * 6 + 10
 
     @staticmethod
@@ -22,6 +24,23 @@ class copenet(_copenet_base):
 
     def forward(self, x0, x1, init_cam0=None, init_cam1=None, init_theta0=None, init_theta1=None, init_shape0=None,
                 init_shape1=None, iters=3):
+        """After set_trainable(True, trunk="fp32" | "bf16"), in train mode (or eval mode with grad) it runs as the reference does
+        (:112-158): the trainable trunk on view 0, then on view 1, then `iters` differentiable forward_reg evaluations."""
+        if self._trunk_trains(x0, x1):
+            if int(iters) < 1:
+                raise RuntimeError("iters must be >= 1 (forward always evaluates the regressor once)")
+            xf0 = self.forward_feat_ext(x0)
+            xf1 = self.forward_feat_ext(x1)
+            th0 = self.init_pose if init_theta0 is None else init_theta0
+            th1 = self.init_pose if init_theta1 is None else init_theta1
+            out = (th0[:, :132], self.init_shape if init_shape0 is None else init_shape0,
+                   self.init_cam if init_cam0 is None else init_cam0,
+                   th1[:, :132], self.init_shape if init_shape1 is None else init_shape1,
+                   self.init_cam if init_cam1 is None else init_cam1)
+            for _ in range(int(iters)):
+                p0, s0, c0, p1, s1, c1 = out
+                out = head_local_grad.muhmr_forward_reg(self, xf0, xf1, p0[:, :6], p1[:, :6], p0[:, 6:], p1[:, 6:], s0, s1, c0, c1)
+            return out
         self._check_eval()
         dev = self._dev(x0)
         if x0.dim() != 4 or x0.shape[1:] != (3, 224, 224) or x1.shape != x0.shape:
@@ -53,7 +72,12 @@ class copenet(_copenet_base):
                     pred_cam0, pred_cam1):
         """One regressor evaluation for both views from trunk features (model_muhmr.py:177-203) ->
         (pred_pose0 (B,132), pred_shape0, pred_cam0, pred_pose1, pred_shape1, pred_cam1).  Runs the two-view kernels
-        with the cameras in the translation slots (the re-mapped fc1 of this variant gives bb zero weight)."""
+        with the cameras in the translation slots (the re-mapped fc1 of this variant gives bb zero weight).  Differentiable
+        after set_trainable(True): both views as one call of 2B rows of the generic head."""
+        if self._local_trains(xf0, xf1, pred_orient0, pred_orient1, pred_art_pose0, pred_art_pose1, pred_shape0, pred_shape1,
+                              pred_cam0, pred_cam1):
+            return head_local_grad.muhmr_forward_reg(self, xf0, xf1, pred_orient0, pred_orient1, pred_art_pose0, pred_art_pose1,
+                                                     pred_shape0, pred_shape1, pred_cam0, pred_cam1)
         self._check_eval()
         dev = self._dev(xf0)
         B = xf0.shape[0]

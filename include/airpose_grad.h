@@ -78,6 +78,54 @@ int apg_head_bwd(int B, const float* xc, const float* h1d, const float* h2d, con
                  void* const* g_param, void* const* g_in, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Generic view-local head (head_local_grad.hip): ONE weight set over R rows, the layout given by the caller.  It serves
+ * copenet.regressor_step (and copenet_sep), model_hmr, model_muhmr (both views as 2B rows) and model_copenet_singleview.
+ *   xc = [xf (2048) | segment 0 | ... | segment nseg-1]        K1 = 2048 + S columns, S = the sum of the segment widths (K1 may be odd)
+ *   h1d = drop1(xc W1^T + b1), h2d = drop2(h1d W2^T + b2)       W1 (1024 x K1), W2 (1024 x 1024)
+ *   out_d = xc[:, 2048 + res_d : 2048 + res_d + n_d] + h2d W_d^T + b_d          for each decoder d, W_d (n_d x 1024)
+ * Dropout rows are the row indices [0, R): apg_dropout_mask(seed, layer, R, 1024, p) is the mask.
+ * Every product reduces over K in index order inside one workgroup and nothing uses atomics: results are bit-reproducible, and a
+ * row's outputs and input gradients depend only on that row.
+ *
+ * apg_head_local_fwd
+ *   seg / seg_ld / seg_w: HOST arrays of nseg (1 .. APG_HEAD_LOCAL_MAX_SEG) entries in fc1 column order -- device pointer, row
+ *     stride in floats (columns contiguous; 0 broadcasts one row to the R rows; otherwise >= width) and width (1 .. 1024).
+ *   dec_W / dec_b / dec_n / dec_res: HOST arrays of ndec (1 .. APG_HEAD_LOCAL_MAX_DEC) entries -- weight, bias, n_d (1 .. 1024) and
+ *     the residual's first column counted from the first segment column; [res_d, res_d + n_d) must lie inside [0, S).
+ *   xc (R x K1), h1d (R x 1024), h2d (R x 1024), wdec (N * 1025 floats, N = sum n_d: the packed (N x 1024)
+ *     [W_0; W_1; ..] followed by the N packed biases): written; what apg_head_local_bwd reads.  xc and wdec are snapshots, so the
+ *     caller may change its inputs in place afterwards.
+ *   out: HOST array of ndec device pointers, (R x n_d) each.  All decoders run as ONE product of N columns.
+ * Bad layouts (R < 1, too many segments or decoders, a residual range outside the segments, a NULL pointer) are APG_EINVAL. */
+#define APG_HEAD_LOCAL_MAX_SEG 8
+#define APG_HEAD_LOCAL_MAX_DEC 3
+int apg_head_local_fwd(int R, const float* xf, int nseg, const void* const* seg, const int* seg_ld, const int* seg_w,
+                       const float* W1, const float* b1, const float* W2, const float* b2, int ndec, const void* const* dec_W,
+                       const void* const* dec_b, const int* dec_n, const int* dec_res, uint64_t seed, float p1, float p2,
+                       float* xc, float* h1d, float* h2d, float* wdec, void* const* out, void* stream);
+
+/* Workspace of apg_head_local_bwd in bytes for K1 fc1 columns and N decoder columns; need_gxf = 1 when g_xf is asked for.
+ * Negative for a bad size. */
+int64_t apg_head_local_bwd_workspace_bytes(int R, int K1, int N, int need_gxf);
+
+/* apg_head_local_bwd
+ *   seg_w, dec_n, dec_res: as in the forward call; seg_bcast[k] != 0: segment k was given with row stride 0, and its gradient is
+ *     (1 x width): the sum over the R rows in row order (two fixed-order passes).
+ *   xc, h1d, h2d, wdec: what apg_head_local_fwd wrote; seed, p1, p2: the values it was given (the masks are regenerated).
+ *   g_out: HOST array of ndec device pointers, (R x n_d); NULL = zero.
+ *   g_param: HOST array of 4 + 2 ndec device pointers -- gW1, gb1, gW2, gb2, then gW_d, gb_d per decoder (each written, not
+ *     accumulated; NULL = not needed), reduced over the R rows in a fixed order.
+ *   g_xf: (R x 2048), written; NULL = not needed (the feature columns of g_xc are then not computed).
+ *   g_seg: HOST array of nseg device pointers, contiguous (R x width), or (1 x width) for a broadcast segment; written; NULL = not
+ *     needed.  Each is the segment's fc1 columns of g_xc plus the output gradient of every decoder whose residual range holds the
+ *     column, in decoder order.
+ *   workspace: at least apg_head_local_bwd_workspace_bytes(R, K1, N, g_xf != NULL) bytes, else APG_ENOMEM. */
+int apg_head_local_bwd(int R, int nseg, const int* seg_w, const int* seg_bcast, int ndec, const int* dec_n, const int* dec_res,
+                       const float* xc, const float* h1d, const float* h2d, const float* wdec, const float* W1, const float* W2,
+                       uint64_t seed, float p1, float p2, const void* const* g_out, void* const* g_param, float* g_xf,
+                       void* const* g_seg, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Geometry adjoints (one workgroup per body for the per-body reductions, fixed order).
  *
  * rot6d_to_rotmat (copenet/src/copenet/utils/geometry.py:47-61, ap_rot6d_to_rotmat): x6 (n x 6), g_rotmat (n x 3 x 3)

@@ -11,6 +11,13 @@ HIP events around windows of --reps calls after --warmup calls; the median of --
 line per batch size; --out also writes them to a file.
 
     python tools/head_grad_bench.py [--sizes 8,64,256,1024] [--reps 10] [--windows 5] [--out profiles/x.json]
+
+--model {step,sep,hmr,muhmr,singleview} times the view-local / baseline heads behind set_trainable(True) (head_local_grad.py,
+apg_head_local_fwd / _bwd) instead: per batch size B one forward_reg evaluation (step: copenet.regressor_step on B rows; sep: the
+two regressor_step calls of copenet_sep.forward_reg; muhmr: 2B rows), forward and forward + backward, next to
+  merged_*     the merged two-view head (apg_head_fwd / apg_head_bwd) at the SAME row count, windows interleaved in one process
+  eager_*      the same evaluation in torch eager fp32 autograd (torch.cat + F.linear + F.dropout)
+--model copenet (the default) is the two-view output described above, unchanged.
 """
 import argparse
 import json
@@ -73,14 +80,116 @@ def eager_step(sd, xf0, xf1, bb0, bb1, pos0, pos1, init_pose, init_shape, iters,
     return P0, b0, P1, b1
 
 
+def timed_interleaved(fns, warmup, reps, windows):
+    """medians of `windows` windows of `reps` calls per function, the functions' windows taking turns (A/B in one process)"""
+    for fn in fns:
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    out = [[] for _ in fns]
+    for _ in range(windows):
+        for i, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                fn()
+            b.record()
+            b.synchronize()
+            out[i].append(a.elapsed_time(b) * 1e3 / reps)
+    return [statistics.median(o) for o in out], [max(o) - min(o) for o in out]
+
+
+def eager_local(net, model, xf, segs, p=0.5):
+    """one evaluation of head_local_grad.LAYOUTS[model] in torch eager"""
+    from airpose_amd.head_local_grad import LAYOUTS
+    xc = torch.cat([xf] + list(segs), 1)
+    h = F.dropout(net.fc2(F.dropout(net.fc1(xc), p)), p)
+    return [xc[:, 2048 + r:2048 + r + n] + getattr(net, d)(h) for d, n, r in LAYOUTS[model][1]]
+
+
+def main_local(args):
+    from airpose_amd import copenet_sep_model, copenet_singleview_model, head_local_grad, hmr_model, muhmr_model
+    dev = torch.device("cuda", 0)
+    model = args.model
+
+    def make(mod, variant, seed):
+        net = mod.getcopenet(MEAN, precision="fp32")
+        net.load_state_dict(W.to_torch(W.copenet_state_dict(seed, MEAN, variant=variant)))
+        return net.to(dev).set_trainable(True).train()
+    merged = make(copenet_model, "copenet", 20240901)
+    if model in ("step", "sep"):
+        nets = [make(copenet_model, "copenet", 20240901 + i) for i in range(2 if model == "sep" else 1)]
+        layout = "step"
+    else:
+        mod = {"hmr": hmr_model, "muhmr": muhmr_model, "singleview": copenet_singleview_model}[model]
+        nets, layout = [make(mod, model, 20240901)], model
+    seg_w = [w for _, w in head_local_grad.LAYOUTS[layout][0]]
+    lines = []
+    for B in [int(s) for s in args.sizes.split(",")]:
+        R = 2 * B if model == "muhmr" else B                 # rows of one generic-head call
+        calls = 2 if model == "sep" else 1
+        rows = R * calls
+        if rows % 2:
+            raise SystemExit("--model %s at B = %d is %d rows: the two-view yardstick needs an even count" % (model, B, rows))
+        g = torch.Generator().manual_seed(B)
+        data = []
+        for _ in range(calls):
+            xf = torch.relu(torch.randn(R, 2048, generator=g)).to(dev).requires_grad_(True)
+            data.append((xf, [torch.randn(R, w, generator=g).to(dev).requires_grad_(True) for w in seg_w]))
+        Bm = rows // 2                                        # the merged head at the same row count
+        mxf = [torch.relu(torch.randn(Bm, 2048, generator=g)).to(dev).requires_grad_(True) for _ in range(2)]
+        mst = [torch.randn(Bm, w, generator=g).to(dev).requires_grad_(True) for w in (3, 3, 3, 3, 6, 6, 126, 126, 10, 10)]
+
+        def new():
+            outs = []
+            for net, (xf, segs) in zip(nets, data):
+                outs += head_local_grad.head(net, layout, xf, segs)
+            return outs
+
+        def old():
+            return merged.forward_reg(*mxf, *mst)
+
+        def eager():
+            outs = []
+            for net, (xf, segs) in zip(nets, data):
+                outs += eager_local(net, layout, xf, segs)
+            return outs
+
+        def nograd(fn):
+            def run():
+                with torch.no_grad():
+                    fn()
+            return run
+
+        def withbwd(fn):
+            return lambda: sum(o.sum() for o in fn()).backward()
+        fns = [nograd(new), nograd(old), nograd(eager), withbwd(new), withbwd(old), withbwd(eager)]
+        med, spread = timed_interleaved(fns, args.warmup, args.reps, args.windows)
+        rec = {"tool": "head_grad_bench", "model": model, "B": B, "rows": rows, "calls": calls,
+               "fwd_us": round(med[0], 1), "merged_fwd_us": round(med[1], 1), "eager_fwd_us": round(med[2], 1),
+               "fwdbwd_us": round(med[3], 1), "merged_fwdbwd_us": round(med[4], 1), "eager_fwdbwd_us": round(med[5], 1),
+               "spread_us": [round(x, 1) for x in spread], "windows": args.windows, "reps": args.reps}
+        print(json.dumps(rec), flush=True)
+        lines.append(rec)
+        for net in nets + [merged]:
+            net.zero_grad(set_to_none=True)
+    if args.out:
+        with open(args.out, "w") as fh:
+            for rec in lines:
+                fh.write(json.dumps(rec) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="copenet", choices=("copenet", "step", "sep", "hmr", "muhmr", "singleview"))
     ap.add_argument("--sizes", default="8,64,256,1024")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.model != "copenet":
+        return main_local(args)
     dev = torch.device("cuda", 0)
     net = copenet_model.getcopenet(MEAN, precision="fp32")
     net.load_state_dict(W.to_torch(W.copenet_state_dict(20240901, MEAN)))
