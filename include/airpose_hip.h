@@ -362,7 +362,7 @@ int ap_conv_pair_ds_nhwc(int precision, const void* t2, const void* x, const voi
  * old or the new value): tile configuration of the convolution kernels.  -1 = automatic, 0..13 = software-pipelined
  * LDS-DMA ring kernel (tile / wave / ring-depth variants, conv_pipe.hip), 100 = register-staged 2-stage kernel,
  * 14 = stride-1 3x3 convolutions with the nine taps read from one LDS slab per 64-channel chunk (conv_slab.hip; bf16,
- * image rows of at most 29 pixels; other shapes run configuration 11), which the automatic choice uses for the conv2
+ * image rows of at most 30 pixels; other shapes run configuration 11), which the automatic choice uses for the conv2
  * layers of layer2-4; 17 = pointwise convolutions on three lean workgroups per CU (conv_lean.hip; bf16; bit-identical to 11;
  * other shapes run configuration 11), which the automatic choice uses for short contractions with many channel tiles
  * (conv3 of layer2-4); -4 = automatic without either (ring kernel everywhere), -5 = automatic without configuration 17.

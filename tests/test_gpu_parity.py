@@ -437,8 +437,6 @@ def test_conv_primitive_split_bf16(dev, case, cfg):
     rounding of the stored result."""
     from airpose_amd import _native as Nn
     N, H, Cin, Cout, k, stride, pad, relu, use_res = case
-    if cfg == 12 and (Cout > 64 * 8 and False):
-        pytest.skip("n/a")
     Nn.check(Nn.lib().ap_set_conv_config(cfg), "ap_set_conv_config")
     try:
         got, ref = _conv_case(dev, "bf16x2", N, H, Cin, Cout, k, stride, pad, relu, use_res, seed=hash(case) % 10000)
