@@ -524,7 +524,8 @@ int ap_smplx_fwd_twoview(ap_smplx* h, int B, float* pred_pose, int pose_ld, floa
                          float* vertices, float* joints_cam, float* joints2d, float* rotmat, void* stream);
 
 /* Arithmetic of the blend-shape contraction v_posed = v_template + [beta | expr | pose_feature] . dirs^T:
- * AP_PREC_BF16X2 (default) = operands as split-bf16 pairs, four-term products on the bf16 matrix pipe, fp32 accumulate
+ * AP_PREC_BF16X2 (default) = operands as split-bf16 pairs, three-term products (hi hi + hi lo + lo hi; the lo lo term, at most
+ * 2^-16 of the product, is dropped) on the bf16 matrix pipe, fp32 accumulate
  * and fp32 result (~1e-7 of the vertex scale from the fp32 path); AP_PREC_FP32 = exact fp32 MFMA chain (4x slower). */
 int ap_smplx_set_blend_precision(ap_smplx* h, int precision);
 /* Blend-shape contraction + skinning as ONE kernel (default on): taken when the call carries no hand / face poses (K = 224),
