@@ -1,0 +1,338 @@
+// Stand-alone operator entry points of libairpose_hip.so: every kernel a trunk pass can launch on caller-owned tensors (the
+// element-wise tests go through these), and the geometry operators.
+#include "api_internal.h"
+
+namespace {
+// what the two bottleneck64 entry points fill alike (the zero line is the caller's: its failure is the caller's error)
+BneckArgs bneck_args(const void* x, const void* w1, const float* s1, const float* h1, const void* w2, const float* s2, const float* h2,
+                     const void* w3, const float* s3, const float* h3, void* y, int N, int H, int W) {
+    BneckArgs a{};
+    a.x = x; a.y = y; a.w1 = w1; a.w2 = w2; a.w3 = w3;
+    a.s1 = s1; a.h1 = h1; a.s2 = s2; a.h2 = h2; a.s3 = s3; a.h3 = h3;
+    a.N = N; a.H = H; a.W = W; a.dbg = g_conv_dbg;
+    return a;
+}
+}  // namespace
+
+extern "C" {
+
+int ap_conv2d_nhwc(int precision, const void* x, const void* w, const float* scale, const float* shift,
+                   const void* res, void* y, int N, int H, int W, int Cin, int Cout, int ksize, int stride, int pad,
+                   int relu, void* stream) {
+    const int bf = prec_half(precision);
+    if (!prec_valid(precision) || !x || !w || !scale ||
+        !shift || !y || N <= 0 ||
+        H <= 0 || W <= 0 || ksize <= 0 || stride <= 0 || pad < 0)
+        return fail(AP_EINVAL, "ap_conv2d_nhwc: bad argument");
+    if (Cin % (bf ? 64 : 32) || Cout % (precision == AP_PREC_FP32 ? 4 : 8) || Cin <= 0 || Cout <= 0)
+        return fail(AP_ESHAPE, "ap_conv2d_nhwc: Cin must be a multiple of 64 (bf16) / 32 (fp32), Cout of 8 / 4");
+    ConvArgs a{};
+    a.x = x; a.w = w; a.scale = scale; a.shift = shift; a.res = res; a.y = y;
+    a.N = N; a.H = H; a.W = W; a.Cin = Cin;
+    a.Ho = (H + 2 * pad - ksize) / stride + 1;
+    a.Wo = (W + 2 * pad - ksize) / stride + 1;
+    if (a.Ho <= 0 || a.Wo <= 0) return fail(AP_ESHAPE, "ap_conv2d_nhwc: empty output");
+    a.Cout = Cout; a.KH = a.KW = ksize; a.stride = stride; a.pad = pad;
+    a.M = N * a.Ho * a.Wo;
+    a.ldx = Cin; a.ldy = Cout; a.ldr = Cout; a.wld = ksize * ksize * Cin; a.relu = relu;
+    HIP_TRY(dispatch_conv(a, precision, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_bottleneck64_nhwc(int precision, const void* x, const void* w1, const float* s1, const float* h1, const void* w2,
+                         const float* s2, const float* h2, const void* w3, const float* s3, const float* h3, void* y,
+                         int N, int H, int W, int Cin, int downsample, void* stream) {
+    if (!prec_half(precision) || !x || !w1 || !s1 || !h1 || !w2 || !s2 || !h2 || !w3 || !s3 || !h3 || !y || N <= 0)
+        return fail(AP_EINVAL, "ap_bottleneck64_nhwc: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16)");
+    if (H <= 0 || W <= 0 || H % 14 || W % 14 || !((Cin == 256 && !downsample) || (Cin == 64 && downsample)))
+        return fail(AP_ESHAPE, "ap_bottleneck64_nhwc: H, W multiples of 14; Cin 256 (identity) or 64 (downsample)");
+    BneckArgs a = bneck_args(x, w1, s1, h1, w2, s2, h2, w3, s3, h3, y, N, H, W);
+    HIP_TRY(zero_line(&a.zero));
+    HIP_TRY(H16(precision, ap_launch_bneck2)(a, downsample ? 1 : 0, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_bottleneck64_tail_nhwc(int precision, const void* x, const void* w1, const float* s1, const float* h1, const void* w2,
+                              const float* s2, const float* h2, const void* w3, const float* s3, const float* h3, void* y,
+                              const void* w1n, const float* s1n, const float* h1n, void* t1n, int y_even, int N, int H, int W,
+                              void* stream) {
+    if (!prec_half(precision) || !x || !w1 || !s1 || !h1 || !w2 || !s2 || !h2 || !w3 || !s3 || !h3 || !y || !w1n || !s1n || !h1n ||
+        !t1n || N <= 0)
+        return fail(AP_EINVAL, "ap_bottleneck64_tail_nhwc: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16)");
+    if (H <= 0 || W <= 0 || H % 14 || W % 14) return fail(AP_ESHAPE, "ap_bottleneck64_tail_nhwc: H, W multiples of 14");
+    BneckArgs a = bneck_args(x, w1, s1, h1, w2, s2, h2, w3, s3, h3, y, N, H, W);
+    a.w1n = w1n; a.s1n = s1n; a.h1n = h1n; a.t1n = t1n; a.y_even = y_even != 0;
+    HIP_TRY(zero_line(&a.zero));
+    HIP_TRY(H16(precision, ap_launch_bneck2)(a, 0, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int64_t ap_conv_pw_stream_bytes(int Cin, int Cout) {
+    return (Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 256 == 0) ? (int64_t)k_bf16::ap_conv_pw_stream_bytes(Cin, Cout) : -1;
+}
+
+int ap_conv_pw_pack(int precision, const void* w, int Cin, int Cout, void* wstream, void* stream) {
+    if (!prec_half(precision) || !w || !wstream || Cin <= 0 || Cout <= 0 || Cin % 32 || Cout % 256)
+        return fail(AP_EINVAL, "ap_conv_pw_pack: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16; Cin % 32 == 0, Cout % 256 == 0)");
+    HIP_TRY(H16(precision, ap_launch_conv_pw_pack)(w, wstream, Cin, Cout, Cin, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_conv_pw_nhwc(int precision, const void* x, const void* wstream, const float* scale, const float* shift, const void* res,
+                    void* y, int M, int Cin, int Cout, void* stream) {
+    if (!prec_half(precision) || !x || !wstream || !scale || !shift || !y)
+        return fail(AP_EINVAL, "ap_conv_pw_nhwc: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16)");
+    if (!k_bf16::ap_conv_pw_supported(M, Cin, Cout))
+        return fail(AP_ESHAPE, "ap_conv_pw_nhwc: M must be a multiple of 196, Cin of 128 (>= 256), Cout of 256");
+    PwArgs p{};
+    p.x = x; p.y = y; p.res = res; p.wfrag = wstream; p.scale = scale; p.shift = shift; p.M = M; p.Cin = Cin; p.Cout = Cout; p.relu = 1;
+    HIP_TRY(H16(precision, ap_launch_conv_pw)(p, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_conv_pw_ds_nhwc(int precision, const void* t2, const void* x, const void* wstream, const float* scale, const float* shift,
+                       void* y, int N, int Ho, int Cin, int Cin2, int Cout, int stride, void* stream) {
+    if (!prec_half(precision) || !t2 || !x || !wstream || !scale || !shift || !y || N <= 0 || Ho <= 0 || stride < 1 || stride > 2)
+        return fail(AP_EINVAL, "ap_conv_pw_ds_nhwc: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16; stride 1 or 2)");
+    PwArgs p{};
+    p.x = t2; p.y = y; p.wfrag = wstream; p.scale = scale; p.shift = shift; p.M = N * Ho * Ho; p.Cin = Cin; p.Cout = Cout; p.relu = 1;
+    p.x2 = x; p.Cin2 = Cin2; p.Ho = p.Wo = Ho; p.H2 = p.W2 = Ho * stride; p.stride2 = stride;
+    if (!k_bf16::ap_conv_pw_ds_supported(p))
+        return fail(AP_ESHAPE, "ap_conv_pw_ds_nhwc: N Ho Ho a multiple of 196 with Ho Ho | 196, Cin and Cin2 multiples of 64 (sum: of 128), Cout of 256");
+    HIP_TRY(H16(precision, ap_launch_conv_pw)(p, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_conv_pw_k3s2_nhwc(int precision, const void* x, const void* wstream, const float* scale, const float* shift, void* y, int N,
+                         int H, int Cin, int Cout, void* stream) {
+    if (!prec_half(precision) || !x || !wstream || !scale || !shift || !y || N <= 0 || H <= 0)
+        return fail(AP_EINVAL, "ap_conv_pw_k3s2_nhwc: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16)");
+    PwArgs p{};
+    p.k3 = 1; p.Ho = p.Wo = H / 2; p.H2 = p.W2 = H; p.stride2 = 2; p.M = N * p.Ho * p.Wo; p.Cin = Cin; p.Cout = Cout; p.relu = 1;
+    p.x = x; p.y = y; p.wfrag = wstream; p.scale = scale; p.shift = shift;
+    if ((H & 1) || !k_bf16::ap_conv_pw_k3_supported(p))
+        return fail(AP_ESHAPE, "ap_conv_pw_k3s2_nhwc: H even with (H / 2)^2 | 196 (14 or 28), N (H / 2)^2 a multiple of 196, Cin / 64 a power of two >= 2, Cout a multiple of 256");
+    HIP_TRY(H16(precision, ap_launch_conv_pw)(p, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int64_t ap_block_img_stream_bytes(void) { return (int64_t)k_bf16::ap_block_img_stream_bytes(); }
+
+int ap_block_img_pack(int precision, const void* w1, const void* w2, const void* w3, void* wstream, void* stream) {
+    if (!prec_half(precision) || !w1 || !w2 || !w3 || !wstream)
+        return fail(AP_EINVAL, "ap_block_img_pack: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16)");
+    HIP_TRY(H16(precision, ap_launch_block_img_pack)(w1, w2, w3, wstream, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_block_img_nhwc(int precision, const void* x, const void* wstream, const float* s1, const float* h1, const float* s2,
+                      const float* h2, const float* s3, const float* h3, void* y, int N, void* stream) {
+    if (!prec_half(precision) || !x || !wstream || !s1 || !h1 || !s2 || !h2 || !s3 || !h3 || !y || N <= 0)
+        return fail(AP_EINVAL, "ap_block_img_nhwc: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16)");
+    BlkImgArgs a{};
+    a.x = x; a.y = y; a.wfrag = wstream; a.s1 = s1; a.h1 = h1; a.s2 = s2; a.h2 = h2; a.s3 = s3; a.h3 = h3; a.N = N;
+    a.dbg = g_conv_dbg;
+    HIP_TRY(H16(precision, ap_launch_block_img)(a, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int64_t ap_conv_img3_stream_bytes(void) { return (int64_t)k_bf16::ap_conv_img3_stream_bytes(); }
+
+int64_t ap_conv_s2p_stream_bytes(void) { return (int64_t)k_bf16::ap_conv_s2p_stream_bytes(); }
+
+int ap_conv_s2p_pack(int precision, const void* w2, void* wstream, void* stream) {
+    if (!prec_half(precision) || !w2 || !wstream) return fail(AP_EINVAL, "ap_conv_s2p_pack: 16-bit precision, w2 [128][3][3][128], stream buffer");
+    HIP_TRY(H16(precision, ap_launch_conv_s2p_pack)(w2, wstream, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_conv_s2p_nhwc(int precision, const void* x, const void* wstream, const float* scale, const float* shift, void* y, int N,
+                     int y_tiled, void* stream) {
+    if (!prec_half(precision) || !x || !wstream || !scale || !shift || !y || N <= 0)
+        return fail(AP_EINVAL, "ap_conv_s2p_nhwc: bad argument");
+    ConvS2pArgs a{};
+    a.x = x; a.y = y; a.wfrag = wstream; a.scale = scale; a.shift = shift; a.N = N; a.y_tiled = y_tiled != 0;
+    HIP_TRY(zero_line(&a.zero));
+    HIP_TRY(H16(precision, ap_launch_conv_s2p)(a, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_conv_img3_pack(int precision, const void* w2, void* wstream, void* stream) {
+    if (!prec_half(precision) || !w2 || !wstream) return fail(AP_EINVAL, "ap_conv_img3_pack: 16-bit precision, w2 [128][3][3][128], stream buffer");
+    HIP_TRY(H16(precision, ap_launch_conv_img3_pack)(w2, wstream, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_conv_img3_nhwc(int precision, const void* x, const void* wstream, const float* scale, const float* shift, void* y, int N,
+                      int y_tiled, void* stream) {
+    if (!prec_half(precision) || !x || !wstream || !scale || !shift || !y || N <= 0)
+        return fail(AP_EINVAL, "ap_conv_img3_nhwc: bad argument");
+    ConvImg3Args a{};
+    a.x = x; a.y = y; a.wfrag = wstream; a.scale = scale; a.shift = shift; a.N = N; a.y_tiled = y_tiled != 0;
+    HIP_TRY(zero_line(&a.zero));
+    HIP_TRY(H16(precision, ap_launch_conv_img3)(a, (hipStream_t)stream));
+    return AP_OK;
+}
+
+// ---- stem and pooling operators: every kernel of stem.hip a trunk pass can launch, through the launch calls the pass makes
+int64_t ap_stem_pack_bytes(int precision) {
+    if (!prec_valid(precision)) return AP_EINVAL;
+    return precision == AP_PREC_FP32 ? 147 * 64 * 4 : (precision == AP_PREC_BF16X2 ? 2 : 1) * 64 * AP_STEM_WLD * 2;
+}
+
+int ap_stem_pack(int precision, const float* w, void* wpacked, void* stream) {
+    if (!prec_valid(precision) || !w || !wpacked) return fail(AP_EINVAL, "ap_stem_pack: precision, w [64][3][7][7] fp32, packed buffer");
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<float> hw(64 * 3 * 49);
+    HIP_TRY(hipMemcpyAsync(hw.data(), w, hw.size() * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    StemPack sp;
+    bool ovf = false;
+    pack_stem(hw.data(), precision, sp, &ovf);
+    if (ovf) return fail(AP_ERANGE, "ap_stem_pack: a weight leaves the fp16 range");
+    if (precision == AP_PREC_FP32) {
+        HIP_TRY(hipMemcpyAsync(wpacked, sp.direct.data(), sp.direct.size() * 4, hipMemcpyHostToDevice, st));
+    } else {
+        const size_t plane = sp.pk.size() * 2;
+        HIP_TRY(hipMemcpyAsync(wpacked, sp.pk.data(), plane, hipMemcpyHostToDevice, st));
+        if (precision == AP_PREC_BF16X2)
+            HIP_TRY(hipMemcpyAsync((char*)wpacked + plane, sp.pk_lo.data(), plane, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));                       // (the host vectors go out of scope)
+    return AP_OK;
+}
+
+int ap_stem_nhwc(int precision, int form, const float* x0, const float* x1, int n_split, const void* wpacked, const float* scale,
+                 const float* shift, void* y, int N, void* stream) {
+    if (!prec_valid(precision) || !wpacked || !scale || !shift || !y || N <= 0 || n_split < 0 || n_split > N || (n_split > 0 && !x0) ||
+        (n_split < N && !x1))
+        return fail(AP_EINVAL, "ap_stem_nhwc: bad argument (x0: the first n_split images, x1: the other N - n_split)");
+    const bool half = prec_half(precision);
+    if (form < 0 || form > (half ? 2 : precision == AP_PREC_BF16X2 ? 1 : 0))
+        return fail(AP_EINVAL, "ap_stem_nhwc: form 0 (un-pooled; every precision), 1 (strip kernel; 16-bit, bf16x2), 2 (persistent kernel; 16-bit)");
+    hipStream_t st = (hipStream_t)stream;
+    const int n1 = N - n_split;
+    if (half) {
+        if (form == 0) HIP_TRY(H16(precision, ap_launch_stem_conv_mfma)(x0, x1, n_split, wpacked, scale, shift, y, N, st));
+        else HIP_TRY(H16(precision, ap_launch_stem_pool)(x0, x1, n_split, wpacked, scale, shift, y, N, nullptr, form, st, nullptr));
+    } else if (precision == AP_PREC_BF16X2) {
+        const void* wlo = (const char*)wpacked + (size_t)64 * AP_STEM_WLD * 2;
+        if (form == 0) HIP_TRY(k_bf16::ap_launch_stem_conv_mfma_split(x0, x1, n_split, wpacked, wlo, scale, shift, y, N, st));
+        else HIP_TRY(k_bf16::ap_launch_stem_pool_split(x0, x1, n_split, wpacked, wlo, scale, shift, y, N, st));
+    } else {
+        if (n_split) HIP_TRY(k_bf16::ap_launch_stem_conv(x0, (const float*)wpacked, scale, shift, y, n_split, K_F32, st));
+        if (n1)
+            HIP_TRY(k_bf16::ap_launch_stem_conv(x1, (const float*)wpacked, scale, shift, (char*)y + (size_t)n_split * 112 * 112 * 64 * 4, n1,
+                                                K_F32, st));
+    }
+    return AP_OK;
+}
+
+int ap_maxpool_nhwc(int precision, const void* x, void* y, int N, void* stream) {
+    if (!prec_valid(precision) || !x || !y || N <= 0) return fail(AP_EINVAL, "ap_maxpool_nhwc: bad argument");
+    HIP_TRY(H16(precision, ap_launch_maxpool)(x, y, N, prec_kind(precision), nullptr, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_avgpool_nhwc(int precision, const void* x, float* y, int N, int C, void* stream) {
+    if (!prec_valid(precision) || !x || !y || N <= 0) return fail(AP_EINVAL, "ap_avgpool_nhwc: bad argument");
+    if (C <= 0 || C % (precision == AP_PREC_FP32 ? 128 : 256)) return fail(AP_ESHAPE, "ap_avgpool_nhwc: C a multiple of 256 (fp32: 128)");
+    HIP_TRY(H16(precision, ap_launch_avgpool)(x, y, N, C, prec_kind(precision), nullptr, (hipStream_t)stream));
+    return AP_OK;
+}
+
+// The fused pair kernel consumes its two weight matrices as ONE stream of 16-KiB tiles in consumption order.  The stream is
+// CALLER-OWNED: packed once by ap_conv_pair_pack into a buffer of ap_conv_pair_stream_bytes, handed to every launch -- the
+// library keeps no hidden copy keyed by weight addresses (an allocator may reuse an address for new contents).
+int64_t ap_conv_pair_stream_bytes(int P, int P2, int N1) {
+    if (!k_bf16::ap_conv_pair_supported(P, P2, 4 * P, N1)) return AP_ESHAPE;
+    return (int64_t)k_bf16::ap_conv_pair_stream_bytes(P, P2, 4 * P, N1);
+}
+
+int ap_conv_pair_pack(int precision, const void* w3, const void* w1, int P, int P2, int N1, void* wstream, void* stream) {
+    if (!prec_half(precision) || !w3 || !wstream || (N1 > 0 && !w1))
+        return fail(AP_EINVAL, "ap_conv_pair_pack: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16)");
+    if (!k_bf16::ap_conv_pair_supported(P, P2, 4 * P, N1))
+        return fail(AP_ESHAPE, "ap_conv_pair_pack: (P, P2, N1) must be (128,0,128), (128,0,256), (256,0,256), (128,256,128) or (256,512,0)");
+    HIP_TRY(H16(precision, ap_launch_pair_pack)(w3, N1 ? w1 : nullptr, wstream, P, P2, 4 * P, N1, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_conv_pair_nhwc(int precision, const void* t2, const void* wstream, const float* s3, const float* h3, const void* res,
+                      const float* s1, const float* h1, void* out, void* t1n, int M, int P, int N1, void* stream) {
+    if (!prec_half(precision) || !t2 || !wstream || !s3 || !h3 || !res || !s1 || !h1 || !out || !t1n || M <= 0)
+        return fail(AP_EINVAL, "ap_conv_pair_nhwc: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16)");
+    if (!k_bf16::ap_conv_pair_supported(P, 0, 4 * P, N1)) return fail(AP_ESHAPE, "ap_conv_pair_nhwc: (P, N1) must be (128,128), (128,256) or (256,256)");
+    PairArgs a{};
+    a.t2 = t2; a.res = res; a.wstream = wstream; a.s3 = s3; a.h3 = h3; a.s1 = s1; a.h1 = h1; a.out = out; a.t1n = t1n; a.M = M;
+    a.dbg = g_conv_dbg;
+    HIP_TRY(H16(precision, ap_launch_conv_pair)(a, P, 0, 4 * P, N1, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_conv_pair_ds_nhwc(int precision, const void* t2, const void* x, const void* wstream, const float* s3, const float* h3,
+                         const float* s1, const float* h1, void* out, void* t1n, int N, int Ho, int P, int P2, int stride, int N1,
+                         void* stream) {
+    if (!prec_half(precision) || !t2 || !x || !wstream || !s3 || !h3 || !out || N <= 0 || Ho <= 0 || (N1 > 0 && (!s1 || !h1 || !t1n)))
+        return fail(AP_EINVAL, "ap_conv_pair_ds_nhwc: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16)");
+    const int C3 = 4 * P;
+    if (!k_bf16::ap_conv_pair_supported(P, P2, C3, N1) || stride < 1 || stride > 2)
+        return fail(AP_ESHAPE, "ap_conv_pair_ds_nhwc: (P, P2, N1) must be (128,256,128) or (256,512,0); stride 1 or 2");
+    PairArgs a{};
+    a.t2 = t2; a.x2 = x; a.wstream = wstream; a.s3 = s3; a.h3 = h3; a.s1 = s1; a.h1 = h1; a.out = out; a.t1n = t1n;
+    a.M = N * Ho * Ho; a.Ho = a.Wo = Ho; a.H2 = a.W2 = Ho * stride; a.stride2 = stride;
+    a.dbg = g_conv_dbg;
+    HIP_TRY(H16(precision, ap_launch_conv_pair)(a, P, P2, C3, N1, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_rotmat_to_angle_axis(const float* rotmat, int n, int cols, float* angle_axis, void* stream) {
+    if (!rotmat || !angle_axis || n <= 0 || (cols != 3 && cols != 4))
+        return fail(AP_EINVAL, "ap_rotmat_to_angle_axis: bad argument (cols must be 3 or 4)");
+    HIP_TRY(ap_launch_rotmat_to_angle_axis(rotmat, n, cols, angle_axis, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_batch_rodrigues(const float* angle_axis, int n, int variant, float* rotmat, void* stream) {
+    if (!angle_axis || !rotmat || n <= 0 || (variant != 0 && variant != 1))
+        return fail(AP_EINVAL, "ap_batch_rodrigues: bad argument (variant 0 = smplx lbs, 1 = copenet geometry)");
+    HIP_TRY(ap_launch_batch_rodrigues(angle_axis, n, variant, rotmat, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_batch_rodrigues_bwd(const float* angle_axis, int n, const float* grad_rotmat, float* grad_angle_axis, void* stream) {
+    if (!angle_axis || !grad_rotmat || !grad_angle_axis || n <= 0) return fail(AP_EINVAL, "ap_batch_rodrigues_bwd: bad argument");
+    HIP_TRY(ap_launch_batch_rodrigues_bwd(angle_axis, n, grad_rotmat, grad_angle_axis, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_rot6d_to_rotmat(const float* x6, int n, float* rotmat, void* stream) {
+    if (!x6 || !rotmat || n <= 0) return fail(AP_EINVAL, "ap_rot6d_to_rotmat: bad argument");
+    HIP_TRY(ap_launch_rot6d(x6, n, rotmat, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_transform_points(const float* rt, const float* pts, int B, int P, float* out, void* stream) {
+    if (!rt || !pts || !out || B <= 0 || P <= 0) return fail(AP_EINVAL, "ap_transform_points: bad argument");
+    HIP_TRY(ap_launch_transform_points(rt, pts, B, P, out, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_preprocess_crops(const unsigned char* frames, int64_t frame_stride_bytes, int n, int H, int W, int bgr,
+                        const int* crop_y0y1x0x1, float* out_nchw, float* scale_out, int* pad_left_top_out, void* stream) {
+    if (!frames || !crop_y0y1x0x1 || !out_nchw || !scale_out || !pad_left_top_out || n <= 0 || H <= 0 || W <= 0 ||
+        frame_stride_bytes < 0)
+        return fail(AP_EINVAL, "ap_preprocess_crops: bad argument");
+    HIP_TRY(k_bf16::ap_launch_preprocess(frames, (size_t)frame_stride_bytes, n, H, W, bgr, crop_y0y1x0x1, out_nchw, scale_out,
+                                 pad_left_top_out, (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_perspective_projection(const float* pts, int B, int P, const float* rotation, const float* translation,
+                              float fx, float fy, const float* center, float* out, void* stream) {
+    if (!pts || !center || !out || B <= 0 || P <= 0) return fail(AP_EINVAL, "ap_perspective_projection: bad argument");
+    HIP_TRY(ap_launch_projection(pts, B, P, rotation, translation, fx, fy, center, out, (hipStream_t)stream));
+    return AP_OK;
+}
+
+}  // extern "C"

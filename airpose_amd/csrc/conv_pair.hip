@@ -65,7 +65,7 @@ template <int OFF> __device__ __forceinline__ f32x4 lds_read_f32x4(uint32_t addr
 // register load the compiler does not count (a load it counts is answered with vmcnt(0) beside LDS-DMA and would drain the
 // weight ring): the destination is valid only behind the hand-placed wait that names it
 // cache policy of the activation traffic: bit 0 = streaming (nt) loads of t2 / identity / x2 (each byte is read once; measured
-// +0.3 % on the whole bench, 5 interleaved pairs, profiles/r04_pair_nt_ab.txt), bit 1 = nt stores (measured -0.5 %: off)
+// +0.3 % on the whole bench, 5 interleaved pairs), bit 1 = nt stores (measured -0.5 %: off)
 #ifndef PR_NT
 #define PR_NT 1
 #endif

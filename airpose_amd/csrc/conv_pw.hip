@@ -25,7 +25,7 @@
 //                                                             zeroed on their way into the LDS.
 // K order per output element = the ring / lean / pair kernels' (K steps of 32 in order -- [tap][Cin] for the 3 x 3 -- one MFMA chain):
 // bit-identical results, so the trunk may choose by problem size and by whether the pass shares the chip (ap_net_set_pw_conv;
-// a one-wave-per-SIMD kernel keeps another pass's workgroups off its CUs: api.hip, trunk_chunk).
+// a one-wave-per-SIMD kernel keeps another pass's workgroups off its CUs: api_trunk.hip, trunk_chunk).
 // Measured (512 images, in the pass): conv1 128 / 57 / 56 us (ring kernel 156 / 70 / 71), conv3 + downsample 171 (208), 3 x 3 / 2
 // 148 / 131 (179 / 153); what bounds it is the latency budget of a staging load: vmcnt retires in order, so a load is waited for at
 // the next ring wait behind it, four K steps after its issue, however deep it was requested.

@@ -78,7 +78,7 @@ __global__ void reg_output_kernel(const float* __restrict__ state, float* __rest
 }
 
 // ---- folded IEF fast path ------------------------------------------------------------------------------------------
-// forward_reg is one affine map (api.hip: Wf = Wd W2 W1, 145 x 2332), so a whole IEF forward is
+// forward_reg is one affine map (api_net.hip: Wf = Wd W2 W1, 145 x 2332), so a whole IEF forward is
 //   H[row]   = bf + Wf[:, :2048] xf[row]                                  (once; split-K, reg_feat_splitk_kernel)
 //   state   += H + Wf[:, 2048:] [bb | state | partner's art, shape]       (iters times; reg_fold_ief_kernel)
 // and the cross-view swap only couples the two views of ONE pair: a workgroup owns a pair and runs all the iterations,
@@ -300,7 +300,7 @@ __global__ void hmr_output_kernel(const float* __restrict__ state, float* __rest
     }
 }
 
-// ---- small helpers of api.hip ---------------------------------------------------------------------------------------
+// ---- small helpers of api_*.hip -------------------------------------------------------------------------------------
 // snapshot of the fp16 range flag (host-mapped word) into a per-slot host-mapped word, in stream order (ap_net_range_mark)
 __global__ void word_copy_kernel(const int* __restrict__ src, int* __restrict__ dst) {
     if (threadIdx.x == 0) __hip_atomic_store(dst, __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM), __ATOMIC_RELAXED,

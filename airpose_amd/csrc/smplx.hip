@@ -334,7 +334,7 @@ __global__ void __launch_bounds__(256) smplx_skin_kernel(const SmplxModelDev m, 
 // (+ transl, then transform_smpl of the caller, copenet_twoview.py:237-246).
 // (The round-3 first cut -- rows = vertices, eight waves with a hand-counted register ring -- was retired in round 5: git history.)
 // The kernel (round 4).  What the first cut's profile said
-// (profiles/r03_lbs_fused_ablation.txt, PMC): every unit at a quarter of its rate, WRITE_SIZE twice the vertex bytes, and an
+// (PMC; docs/DESIGN_rounds1-4.md, Appendix A, round 3): every unit at a quarter of its rate, WRITE_SIZE twice the vertex bytes, and an
 // intermittent wrong vertex in one build of it (hand-counted asm loads with loop-carried destinations).  Changes:
 //   * ORIENTATION: rows = bodies, columns = vertices (A = coefficient rows from LDS, B = direction fragments from L2 -- the same
 //     dirs_frag buffer: A and B fragments of v_mfma_f32_16x16x32 share their (16 x 8-k) lane layout).  A lane then holds (x, y, z)

@@ -1,5 +1,5 @@
 // SMPL-X backward kernels for gfx950: the adjoint of ap_smplx_fwd (upstream smplx 0.1.28 lbs.lbs as plain autograd sees it)
-// and of lbs.batch_rodrigues.  The driver (api.hip, ap_smplx_bwd) first recomputes the forward's bone transforms A and v_posed
+// and of lbs.batch_rodrigues.  The driver (api_smplx.hip, ap_smplx_bwd) first recomputes the forward's bone transforms A and v_posed
 // into the backward's own workspaces (smplx_prep_kernel + the blend-shape GEMM), then:
 //   1. smplx_bwd_lbs_kernel    (vertex range x body): g_v = grad_vertices + the extra-joint / landmark gradients scattered onto
 //                              their vertices; g_vposed = T_v[:3,:3]^T g_v; g_A_k = sum_v w_vk g_v (x) [v_posed_v, 1] per range

@@ -147,6 +147,19 @@ def test_one_library_carries_both_16bit_storage_types():
     assert L.ap_net_range_status(None, None, 0) == -1 and L.ap_net_set_range_check(None, 1) == -1
 
 
+def test_host_layer_exports_the_header_and_nothing_internal():
+    """The host layer is several translation units (csrc/api_*.hip) that share helpers through namespace ap_internal (hidden
+    visibility, csrc/api_internal.h): none of those may reach the dynamic symbol table, and the C names the library defines are
+    exactly the functions include/airpose_hip.h declares."""
+    import subprocess
+    from airpose_amd import _native as Nn
+    out = subprocess.run(["nm", "-D", "--defined-only", Nn.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    syms = [l.split()[-1] for l in out.splitlines() if l.strip()]
+    assert len(syms) >= 99
+    assert [s for s in syms if "ap_internal" in s] == []
+    assert sorted(s for s in syms if s.startswith("ap_")) == _declared()
+
+
 def test_bench_launches_itself_for_n_gpus():
     """`python bench.py --gpus 2` with no launcher environment (the shape of the driver's plain command) must start its own ranks
     (it used to die with SystemExit before touching a GPU).  AIRPOSE_BENCH_LAUNCH_ONLY=1 stops each rank where the GPU

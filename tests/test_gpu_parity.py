@@ -2255,7 +2255,7 @@ def test_fitting_at_the_size_of_config_5(body, smplx_model, dev):
 @pytest.mark.parametrize("max_bones", [6, 9])
 def test_smplx_more_than_four_bones_per_vertex(max_bones, dev):
     """A real SMPL-X weight matrix may carry more than 4 non-zeros per vertex: max_bones = 6 selects
-    smplx_skin_kernel<8>, max_bones = 9 the dynamic-K instantiation (api.hip picks K from the packed model).
+    smplx_skin_kernel<8>, max_bones = 9 the dynamic-K instantiation (api_smplx.hip picks K from the packed model).
     Both the plain SMPLX.forward and the fused pose6d -> LBS -> transform -> projection entry are checked."""
     from airpose_amd import smplx, smplx_model as SM
     from oracle import geometry_ref, smplx_ref

@@ -787,7 +787,7 @@ class Body(object):
 
 
 def plan_of(mo, mode, prec, n, body_only=True, has_transl=True):
-    """What api.hip's smplx_run launches: (fused kernel?, K, split, KB, merged table?)"""
+    """What api_smplx.hip's smplx_run launches: (fused kernel?, K, split, KB, merged table?)"""
     fused = mode != 0 and prec == "bf16x2" and body_only and mo["bones"] <= 4
     K = 224 if body_only else 512
     return fused, K, prec == "bf16x2", (4 if mo["bones"] <= 4 else 8 if mo["bones"] <= 8 else mo["bones"]), fused and mode != 6

@@ -1,6 +1,6 @@
 """Element-wise fp64 ground truth for every kernel of airpose_amd/csrc/stem.hip that a trunk pass can launch, through the
 operator entries ap_stem_pack / ap_stem_nhwc / ap_maxpool_nhwc / ap_avgpool_nhwc (include/airpose_hip.h).  ap_stem_pack runs the
-packing of ap_net_finalize (api.hip: pack_stem), so the k' = r*32 + s*4 + c layout the trunk runs on is what is tested.
+packing of ap_net_finalize (api_net.hip: pack_stem), so the k' = r*32 + s*4 + c layout the trunk runs on is what is tested.
 
 Kernel -> test
   stem_direct_kernel            test_stem_split_and_fp32[fp32]            form 0
