@@ -1,4 +1,5 @@
-// Internal helpers shared by the sources of libairpose_grad.so (head_grad.hip, head_local_grad.hip, geom_grad.hip, trunk_grad.hip).
+// Internal helpers shared by the sources of libairpose_grad.so (head_grad.hip, head_local_grad.hip, geom_grad.hip, trunk_grad.hip,
+// trunk_grad_bf16.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,6 +10,13 @@
 
 // records the thread-local message apg_last_error() returns; returns code
 __attribute__((visibility("hidden"))) int apg_fail(int code, const std::string& msg);
+
+// returns from the calling entry point with the HIP error code of `expr` and a message naming it
+#define APG_TRY(expr)                                                                               \
+    do {                                                                                            \
+        hipError_t _e = (expr);                                                                     \
+        if (_e != hipSuccess) return apg_fail((int)_e, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+    } while (0)
 
 // splitmix64 finaliser
 __host__ __device__ __forceinline__ uint64_t apg_mix64(uint64_t z) {

@@ -296,12 +296,6 @@ hipError_t apg_colsum(const float* x, int rows, int cols, int ld, float* part, f
     return colsum(x, rows, cols, ld, part, out, st);
 }
 
-#define APG_TRY(expr)                                                                               \
-    do {                                                                                            \
-        hipError_t _e = (expr);                                                                     \
-        if (_e != hipSuccess) return apg_fail((int)_e, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 extern "C" {
 
 int apg_dropout_mask(uint64_t seed, int layer, int rows, int cols, float p, uint8_t* out, void* stream) {

@@ -172,12 +172,6 @@ std::string check_layout(int R, int nseg, const int* seg_w, int ndec, const int*
 
 }  // namespace
 
-#define APG_TRY(expr)                                                                               \
-    do {                                                                                            \
-        hipError_t _e = (expr);                                                                     \
-        if (_e != hipSuccess) return apg_fail((int)_e, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 extern "C" {
 
 int apg_head_local_fwd(int R, const float* xf, int nseg, const void* const* seg, const int* seg_ld, const int* seg_w,

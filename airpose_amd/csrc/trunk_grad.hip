@@ -388,38 +388,7 @@ __global__ void __launch_bounds__(256) nhwc_to_nchw_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }
-unsigned nblk(long long total) { return (unsigned)((total + 255) / 256); }
-bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-struct Geom {
-    int n, H, W, C, K, R, S, st, pad, Ho, Wo;
-};
-
-bool geom_ok(const Geom& g) {
-    if (g.n <= 0 || g.H <= 0 || g.W <= 0 || g.C <= 0 || g.K <= 0 || g.R <= 0 || g.S <= 0 || g.st <= 0 || g.pad < 0) return false;
-    // the kernel must fit the padded input: make_geom's division truncates toward zero, so at stride >= 2 a too-large kernel
-    // would otherwise come out as Ho = 1
-    if ((long long)g.H + 2LL * g.pad < g.R || (long long)g.W + 2LL * g.pad < g.S) return false;
-    if (g.Ho <= 0 || g.Wo <= 0) return false;
-    return (long long)g.n * g.H * g.W * g.C < (1LL << 31) && (long long)g.n * g.Ho * g.Wo * g.K < (1LL << 31) &&
-           (long long)g.n * g.Ho * g.Wo < (1LL << 31);
-}
-
-Geom make_geom(int n, int H, int W, int C, int K, int R, int S, int st, int pad) {
-    Geom g{n, H, W, C, K, R, S, st, pad, 0, 0};
-    if (st > 0) {
-        g.Ho = (H + 2 * pad - R) / st + 1;
-        g.Wo = (W + 2 * pad - S) / st + 1;
-    }
-    return g;
-}
-
-ConvArgs conv_args(const Geom& g) {
-    ConvArgs a = {};
-    a.n = g.n; a.H = g.H; a.W = g.W; a.C = g.C; a.K = g.K; a.R = g.R; a.S = g.S; a.st = g.st; a.pad = g.pad; a.Ho = g.Ho; a.Wo = g.Wo;
-    return a;
-}
+#include "trunk_walk.inc"
 
 // split-K of the weight gradient: enough chunks for ~1024 workgroups, chunks of at least 512 pixels (a multiple of 16)
 void wgrad_split(const Geom& g, int* nch, int* chunk) {
@@ -432,14 +401,8 @@ void wgrad_split(const Geom& g, int* nch, int* chunk) {
     *nch = (KK + ch - 1) / ch;
 }
 
-size_t wgrad_floats(const Geom& g) {
-    int nch, chunk;
-    wgrad_split(g, &nch, &chunk);
-    return (size_t)nch * g.K * g.R * g.S * g.C;
-}
-
 hipError_t conv_fwd(const Geom& g, const float* x, const float* w, float* y, hipStream_t st) {
-    ConvArgs a = conv_args(g);
+    ConvArgs a = conv_args<ConvArgs>(g);
     a.x = x; a.w = w; a.out = y;
     a.M = g.n * g.Ho * g.Wo; a.N = g.K; a.KK = g.R * g.S * g.C;
     const dim3 grid((a.M + 63) / 64, (a.N + 63) / 64);
@@ -450,7 +413,7 @@ hipError_t conv_fwd(const Geom& g, const float* x, const float* w, float* y, hip
 
 // gx = dgrad(gy) (+ add); needs K % 16 == 0 and gy 16-byte aligned (argument checks)
 hipError_t conv_dgrad(const Geom& g, const float* gy, const float* w, const float* add, float* gx, hipStream_t st) {
-    ConvArgs a = conv_args(g);
+    ConvArgs a = conv_args<ConvArgs>(g);
     a.gy = gy; a.w = w; a.out = gx; a.add = add;
     a.M = g.n * g.H * g.W; a.N = g.C; a.KK = g.R * g.S * g.K;
     hipLaunchKernelGGL((apg_conv_kernel<CV_DGRAD, true>), dim3((a.M + 63) / 64, (a.N + 63) / 64), dim3(256), 0, st, a);
@@ -459,7 +422,7 @@ hipError_t conv_dgrad(const Geom& g, const float* gy, const float* w, const floa
 
 // gw (OIHW) = wgrad, through `part` (wgrad_floats(g) floats)
 hipError_t conv_wgrad(const Geom& g, const float* x, const float* gy, float* part, float* gw, hipStream_t st) {
-    ConvArgs a = conv_args(g);
+    ConvArgs a = conv_args<ConvArgs>(g);
     a.x = x; a.gy = gy; a.out = part;
     a.M = g.K; a.N = g.R * g.S * g.C; a.KK = g.n * g.Ho * g.Wo;
     int nch;
@@ -471,8 +434,6 @@ hipError_t conv_wgrad(const Geom& g, const float* x, const float* gy, float* par
     hipLaunchKernelGGL(conv_wgrad_combine_kernel, dim3(nblk(tot)), dim3(256), 0, st, part, nch, g.K, g.C, g.R, g.S, gw);
     return hipGetLastError();
 }
-
-size_t bn_part_floats(int M, int C) { return (size_t)bn_tiles(M) * 3 * C + 2 * (size_t)C; }
 
 // forward BN over (M, C): train -> batch statistics (+ running update when rm / rv given), eval -> running statistics
 hipError_t bn_fwd(const float* x, int M, int C, const float* gamma, const float* beta, float* rm, float* rv, int train, float momentum,
@@ -501,104 +462,57 @@ hipError_t bn_bwd(const float* gy, const float* y, const float* x, int M, int C,
     return hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------------------------------------------- the trunk plan
-constexpr int NLAYER = 53;
-constexpr int IMG = 224;
-
-struct Layer {
-    int idx;                             // position in state_dict order (conv + BN pair)
-    Geom g;
-    float *in, *z, *a;                   // conv input, conv output (pre-BN), BN output
-    float *mean, *invstd;
+// ---------------------------------------------------------------------------------------------------------------- the trunk walks
+// The fp32 backend of trunk_walk.inc: NHWC fp32 activations, the live OIHW parameters as the weights (nothing packed, no padding).
+struct F32Ops {
+    using act = float;
+    using L = Layer<float>;
+    static constexpr const char *fwd_name = "apg_trunk_fwd", *bwd_name = "apg_trunk_bwd";
+    static constexpr bool ws_aligned = false, packed = false;
+    static int cpad(int C) { return C; }
+    static void pack(const L&, const float*, hipStream_t) {}
+    static hipError_t conv_fwd(const L& l, const float* w, hipStream_t st) { return ::conv_fwd(l.g, l.in, w, l.z, st); }
+    static hipError_t conv_dgrad(const L& l, const float* gy, const float* w, const float* add, float* gx, hipStream_t st) {
+        return ::conv_dgrad(l.g, gy, w, add, gx, st);
+    }
+    static hipError_t conv_wgrad(const L& l, const float* gz, float* part, float* gw, hipStream_t st) {
+        return ::conv_wgrad(l.g, l.in, gz, part, gw, st);
+    }
+    static constexpr auto bn_fwd = &::bn_fwd;
+    static constexpr auto bn_bwd = &::bn_bwd;
+    static void maxpool_fwd(const float* x, int n, int H, int C, float* y, hipStream_t st) {
+        const int Ho = (H - 1) / 2 + 1;
+        hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(nblk((long long)n * Ho * Ho * C)), dim3(256), 0, st, x, n, H, H, C, Ho, Ho, y);
+    }
+    static void maxpool_bwd(const float* x, const float* gy, int n, int H, int C, float* gx, hipStream_t st) {
+        const int Ho = (H - 1) / 2 + 1;
+        hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(nblk((long long)n * H * H * C)), dim3(256), 0, st, x, gy, n, H, H, C, Ho, Ho, gx);
+    }
+    static void avgpool_fwd(const float* x, int n, int C, float* y, hipStream_t st) {
+        hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(nblk((long long)n * C)), dim3(256), 0, st, x, n, C, y);
+    }
+    static void avgpool_bwd(const float* gy, int n, int C, float* gx, hipStream_t st) {
+        hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(nblk((long long)n * 49 * C)), dim3(256), 0, st, gy, n, C, gx);
+    }
+    static void crops_in(const float* x, int n, float* ximg, hipStream_t st) {
+        hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(nblk((long long)n * 3 * IMG * IMG)), dim3(256), 0, st, x, n, 3, IMG * IMG, ximg);
+    }
+    static hipError_t crop_grad(const L& stem, const float* w, const float* g1, float* g2, int n, float* g_x, hipStream_t st) {
+        hipError_t e = ::conv_dgrad(stem.g, g1, w, nullptr, g2, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(nblk((long long)n * 3 * IMG * IMG)), dim3(256), 0, st, g2, n, 3, IMG * IMG, g_x);
+        return hipGetLastError();
+    }
+    // the downsample's data gradient goes to gnext and conv1's data gradient adds it in place
+    static hipError_t ds_block_dgrad(const L& ds, const float* wds, const float* gres, const L& c1, const float* wc1, const float* g1,
+                                     float*, float* gnext, hipStream_t st) {
+        hipError_t e = ::conv_dgrad(ds.g, gres, wds, nullptr, gnext, st);
+        if (e != hipSuccess) return e;
+        return ::conv_dgrad(c1.g, g1, wc1, gnext, gnext, st);
+    }
 };
-
-struct Block {
-    Layer c1, c2, c3, ds;
-    bool has_ds;
-};
-
-struct Plan {
-    Layer stem;
-    float *ximg, *pool;                  // NHWC copy of the crops; max-pool output
-    Block blk[16];
-    float* G[6];                         // backward: gradient buffers of the largest activation
-    float* part;                         // split-K / BN partials
-    size_t total;                        // floats
-};
-
-// Walks the fixed [3, 4, 6, 3] graph.  base == nullptr: sizes only.  save = 1: every activation has its own buffer (what backward
-// reads) and the backward buffers follow; save = 0: forward only, five rotating buffers, BN in place.
-Plan make_plan(int n, int save, float* base) {
-    Plan P;
-    size_t off = 0;
-    auto take = [&](size_t floats) -> float* {
-        float* p = base ? base + off : nullptr;
-        off += align64(floats);
-        return p;
-    };
-    const size_t big = (size_t)n * 112 * 112 * 64;       // the largest activation (stem output; layer1's 256-channel maps equal it)
-    float* slot[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (!save)
-        for (int k = 0; k < 5; ++k) slot[k] = take(big);
-    size_t part = 0;
-    auto mk = [&](int idx, float* in, int H, int C, int K, int R, int st, int pad, float* zs) {
-        Layer L;
-        L.idx = idx;
-        L.g = make_geom(n, H, H, C, K, R, R, st, pad);
-        L.in = in;
-        const size_t sz = (size_t)n * L.g.Ho * L.g.Wo * K;
-        L.z = save ? take(sz) : zs;
-        L.a = save ? take(sz) : zs;
-        L.mean = take(K);
-        L.invstd = take(K);
-        part = std::max(part, wgrad_floats(L.g));
-        part = std::max(part, bn_part_floats(n * L.g.Ho * L.g.Wo, K));
-        return L;
-    };
-    P.ximg = save ? take((size_t)n * IMG * IMG * 3) : slot[0];
-    P.stem = mk(0, P.ximg, IMG, 3, 64, 7, 2, 3, slot[1]);
-    P.pool = save ? take((size_t)n * 56 * 56 * 64) : slot[2];
-    float* x = P.pool;
-    int H = 56, C = 64, idx = 1, bi = 0;
-    int free_slots[3] = {0, 1, 3};                          // save = 0: the slots not holding the block input (slot 2) ...
-    int in_slot = 2, ds_slot = 4;
-    const int layers[4] = {3, 4, 6, 3}, planes[4] = {64, 128, 256, 512};
-    for (int li = 0; li < 4; ++li)
-        for (int b = 0; b < layers[li]; ++b, ++bi) {
-            const int p = planes[li], st = (b == 0 && li > 0) ? 2 : 1;
-            Block& B = P.blk[bi];
-            B.has_ds = b == 0;
-            float *s1 = nullptr, *s2 = nullptr, *s3 = nullptr;
-            if (!save) { s1 = slot[free_slots[0]]; s2 = slot[free_slots[1]]; s3 = slot[free_slots[2]]; }
-            B.c1 = mk(idx++, x, H, C, p, 1, 1, 0, s1);
-            B.c2 = mk(idx++, B.c1.a, H, p, p, 3, st, 1, s2);
-            const int Ho = B.c2.g.Ho;
-            B.c3 = mk(idx++, B.c2.a, Ho, p, 4 * p, 1, 1, 0, s3);
-            if (B.has_ds) B.ds = mk(idx++, x, H, C, 4 * p, 1, st, 0, save ? nullptr : slot[ds_slot]);
-            x = B.c3.a;
-            H = Ho;
-            C = 4 * p;
-            if (!save) {                                    // the block output (slot free_slots[2]) becomes the next input
-                const int o = free_slots[2];
-                free_slots[2] = in_slot;
-                in_slot = o;
-            }
-        }
-    for (int k = 0; k < 6; ++k) P.G[k] = save ? take(big) : nullptr;
-    P.part = take(part);
-    P.total = off;
-    return P;
-}
-
-const float* prm(const void* const* t, int layer, int k) { return (const float*)t[layer * 5 + k]; }
 
 }  // namespace
-
-#define APG_TRY(expr)                                                                               \
-    do {                                                                                            \
-        hipError_t _e = (expr);                                                                     \
-        if (_e != hipSuccess) return apg_fail((int)_e, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
 
 extern "C" {
 
@@ -693,105 +607,16 @@ int apg_avgpool_bwd(const float* gy, int n, int C, float* gx, void* stream) {
 }
 
 // ------------------------------------------------------------------------------------------------ the trunk walker
-int64_t apg_trunk_workspace_bytes(int n, int save) {
-    if (n <= 0 || n > 2048) return -1;
-    return (int64_t)(make_plan(n, save ? 1 : 0, nullptr).total * sizeof(float));
-}
-
-static int check_table(const void* const* params, const char* what) {
-    if (!params) return apg_fail(APG_EINVAL, std::string(what) + ": parameter table missing");
-    for (int k = 0; k < NLAYER * 5; ++k)
-        if (!params[k]) return apg_fail(APG_EINVAL, std::string(what) + ": parameter table entry " + std::to_string(k) + " is NULL");
-    return APG_OK;
-}
+int64_t apg_trunk_workspace_bytes(int n, int save) { return trunk_bytes<F32Ops>(n, save); }
 
 int apg_trunk_fwd(int n, const float* x, const void* const* params, int train, float momentum, float eps, float* xf, int save,
                   void* workspace, int64_t workspace_bytes, void* stream) {
-    if (n <= 0 || n > 2048 || !x || !xf || !workspace || !(eps >= 0.f) || (train && !(momentum >= 0.f && momentum <= 1.f)))
-        return apg_fail(APG_EINVAL, "apg_trunk_fwd: bad argument");
-    if (int rc = check_table(params, "apg_trunk_fwd")) return rc;
-    if (workspace_bytes < apg_trunk_workspace_bytes(n, save))
-        return apg_fail(APG_ENOMEM, "apg_trunk_fwd: workspace of " + std::to_string(workspace_bytes) + " bytes, " +
-                                        std::to_string(apg_trunk_workspace_bytes(n, save)) + " needed");
-    hipStream_t st = (hipStream_t)stream;
-    const Plan P = make_plan(n, save ? 1 : 0, (float*)workspace);
-    auto run = [&](const Layer& L, const float* res, int relu) -> hipError_t {
-        hipError_t e = conv_fwd(L.g, L.in, prm(params, L.idx, 0), L.z, st);
-        if (e != hipSuccess) return e;
-        return bn_fwd(L.z, n * L.g.Ho * L.g.Wo, L.g.K, prm(params, L.idx, 1), prm(params, L.idx, 2), (float*)prm(params, L.idx, 3),
-                      (float*)prm(params, L.idx, 4), train, momentum, eps, res, relu, L.a, L.mean, L.invstd, P.part, st);
-    };
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(nblk((long long)n * 3 * IMG * IMG)), dim3(256), 0, st, x, n, 3, IMG * IMG, P.ximg);
-    APG_TRY(run(P.stem, nullptr, 1));
-    hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(nblk((long long)n * 56 * 56 * 64)), dim3(256), 0, st, P.stem.a, n, 112, 112, 64, 56,
-                       56, P.pool);
-    APG_TRY(hipGetLastError());
-    for (int b = 0; b < 16; ++b) {
-        const Block& B = P.blk[b];
-        APG_TRY(run(B.c1, nullptr, 1));
-        APG_TRY(run(B.c2, nullptr, 1));
-        if (B.has_ds) APG_TRY(run(B.ds, nullptr, 0));
-        APG_TRY(run(B.c3, B.has_ds ? B.ds.a : B.c1.in, 1));
-    }
-    hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(nblk((long long)n * 2048)), dim3(256), 0, st, P.blk[15].c3.a, n, 2048, xf);
-    APG_TRY(hipGetLastError());
-    return APG_OK;
+    return trunk_fwd_walk<F32Ops>(n, x, params, train, momentum, eps, xf, save, workspace, workspace_bytes, stream);
 }
 
 int apg_trunk_bwd(int n, const void* const* params, int train, const float* g_xf, void* const* g_params, float* g_x, void* workspace,
                   int64_t workspace_bytes, void* stream) {
-    if (n <= 0 || n > 2048 || !g_xf || !g_params || !workspace) return apg_fail(APG_EINVAL, "apg_trunk_bwd: bad argument");
-    if (int rc = check_table(params, "apg_trunk_bwd")) return rc;
-    if (workspace_bytes < apg_trunk_workspace_bytes(n, 1))
-        return apg_fail(APG_ENOMEM, "apg_trunk_bwd: workspace of " + std::to_string(workspace_bytes) + " bytes, " +
-                                        std::to_string(apg_trunk_workspace_bytes(n, 1)) + " needed (the one apg_trunk_fwd filled, save = 1)");
-    hipStream_t st = (hipStream_t)stream;
-    const Plan P = make_plan(n, 1, (float*)workspace);
-    float *gcur = P.G[0], *gnext = P.G[1], *g3 = P.G[2], *g2 = P.G[3], *g1 = P.G[4], *gres = P.G[5];
-    auto gp = [&](const Layer& L, int k) { return (float*)g_params[L.idx * 3 + k]; };
-    // BN backward of layer L (gy -> gx, ReLU mask from L.a when relu), then its weight gradient
-    auto bnb = [&](const Layer& L, const float* gy, int relu, float* gx, float* g_res) -> hipError_t {
-        return bn_bwd(gy, relu ? L.a : nullptr, L.z, n * L.g.Ho * L.g.Wo, L.g.K, prm(params, L.idx, 1), L.mean, L.invstd, train, gx,
-                      g_res, gp(L, 1), gp(L, 2), P.part, st);
-    };
-    auto wg = [&](const Layer& L, const float* gz) -> hipError_t {
-        if (!gp(L, 0)) return hipSuccess;
-        return conv_wgrad(L.g, L.in, gz, P.part, gp(L, 0), st);
-    };
-    hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(nblk((long long)n * 49 * 2048)), dim3(256), 0, st, g_xf, n, 2048, gcur);
-    APG_TRY(hipGetLastError());
-    for (int b = 15; b >= 0; --b) {
-        const Block& B = P.blk[b];
-        APG_TRY(bnb(B.c3, gcur, 1, g3, gres));
-        APG_TRY(wg(B.c3, g3));
-        APG_TRY(conv_dgrad(B.c3.g, g3, prm(params, B.c3.idx, 0), nullptr, g2, st));
-        APG_TRY(bnb(B.c2, g2, 1, g2, nullptr));
-        APG_TRY(wg(B.c2, g2));
-        APG_TRY(conv_dgrad(B.c2.g, g2, prm(params, B.c2.idx, 0), nullptr, g1, st));
-        APG_TRY(bnb(B.c1, g1, 1, g1, nullptr));
-        APG_TRY(wg(B.c1, g1));
-        if (B.has_ds) {
-            APG_TRY(bnb(B.ds, gres, 0, gres, nullptr));
-            APG_TRY(wg(B.ds, gres));
-            APG_TRY(conv_dgrad(B.ds.g, gres, prm(params, B.ds.idx, 0), nullptr, gnext, st));
-            APG_TRY(conv_dgrad(B.c1.g, g1, prm(params, B.c1.idx, 0), gnext, gnext, st));
-        } else {
-            APG_TRY(conv_dgrad(B.c1.g, g1, prm(params, B.c1.idx, 0), gres, gnext, st));
-        }
-        std::swap(gcur, gnext);
-    }
-    // stem: max-pool, BN + ReLU, the 7 x 7 convolution
-    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(nblk((long long)n * 112 * 112 * 64)), dim3(256), 0, st, P.stem.a, gcur, n, 112, 112, 64,
-                       56, 56, g1);
-    APG_TRY(hipGetLastError());
-    APG_TRY(bnb(P.stem, g1, 1, g1, nullptr));
-    APG_TRY(wg(P.stem, g1));
-    if (g_x) {
-        APG_TRY(conv_dgrad(P.stem.g, g1, prm(params, 0, 0), nullptr, g2, st));
-        hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(nblk((long long)n * 3 * IMG * IMG)), dim3(256), 0, st, g2, n, 3, IMG * IMG, g_x);
-        APG_TRY(hipGetLastError());
-    }
-    return APG_OK;
+    return trunk_bwd_walk<F32Ops>(n, params, train, g_xf, g_params, g_x, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

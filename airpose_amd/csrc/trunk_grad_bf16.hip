@@ -482,36 +482,11 @@ __global__ void __launch_bounds__(256) nhwc8_to_nchw_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-unsigned nblk(long long total) { return (unsigned)((total + 255) / 256); }
-bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+#include "trunk_walk.inc"
 
-struct Geom {
-    int n, H, W, C, K, R, S, st, pad, Ho, Wo;                   // C: the channel count of x as stored (a multiple of 8)
-};
-
-bool geom_ok(const Geom& g) {
-    if (g.n <= 0 || g.H <= 0 || g.W <= 0 || g.C <= 0 || g.K <= 0 || g.R <= 0 || g.S <= 0 || g.st <= 0 || g.pad < 0) return false;
-    if ((long long)g.H + 2LL * g.pad < g.R || (long long)g.W + 2LL * g.pad < g.S) return false;
-    if (g.Ho <= 0 || g.Wo <= 0) return false;
-    if (g.C % 8 != 0 || g.K % 8 != 0) return false;             // a 16-byte load holds 8 channels of one pixel / tap
-    return (long long)g.n * g.H * g.W * g.C < (1LL << 31) && (long long)g.n * g.Ho * g.Wo * g.K < (1LL << 31) &&
-           (long long)g.n * g.Ho * g.Wo < (1LL << 31) && (long long)g.R * g.S * g.C * g.K < (1LL << 31);
-}
-
-Geom make_geom(int n, int H, int W, int C, int K, int R, int S, int st, int pad) {
-    Geom g{n, H, W, C, K, R, S, st, pad, 0, 0};
-    if (st > 0) {
-        g.Ho = (H + 2 * pad - R) / st + 1;
-        g.Wo = (W + 2 * pad - S) / st + 1;
-    }
-    return g;
-}
-
-BArgs conv_args(const Geom& g) {
-    BArgs a = {};
-    a.n = g.n; a.H = g.H; a.W = g.W; a.C = g.C; a.K = g.K; a.R = g.R; a.S = g.S; a.st = g.st; a.pad = g.pad; a.Ho = g.Ho; a.Wo = g.Wo;
-    return a;
+// the bf16 kernels' geometry: a 16-byte load holds 8 channels of one pixel / tap; packed weights indexed in 32 bits
+bool geom_ok8(const Geom& g) {
+    return geom_ok(g) && g.C % 8 == 0 && g.K % 8 == 0 && (long long)g.R * g.S * g.C * g.K < (1LL << 31);
 }
 
 // the 128 x 128 tile where it fills the part (256 CUs) and both sides reach it, else 64 x 64
@@ -530,12 +505,6 @@ void wgrad_split(const Geom& g, int* nch, int* chunk) {
     *nch = (KK + ch - 1) / ch;
 }
 
-size_t wgrad_floats(const Geom& g) {
-    int nch, chunk;
-    wgrad_split(g, &nch, &chunk);
-    return (size_t)nch * g.K * g.R * g.S * g.C;
-}
-
 template <int MODE>
 void launch_conv(const BArgs& a, int nz, bool big, hipStream_t st) {
     if (big) hipLaunchKernelGGL((bconv_kernel<MODE, 128, 128>), dim3((a.M + 127) / 128, (a.N + 127) / 128, nz), dim3(256), 0, st, a);
@@ -543,7 +512,7 @@ void launch_conv(const BArgs& a, int nz, bool big, hipStream_t st) {
 }
 
 hipError_t conv_fwd(const Geom& g, const bf16_t* x, const bf16_t* wf, bf16_t* y, hipStream_t st) {
-    BArgs a = conv_args(g);
+    BArgs a = conv_args<BArgs>(g);
     a.a = x; a.b = wf; a.out = y;
     a.M = g.n * g.Ho * g.Wo; a.N = g.K; a.KK = g.R * g.S * g.C;
     launch_conv<CV_FWD>(a, 1, big_tile(a.M, a.N), st);
@@ -552,7 +521,7 @@ hipError_t conv_fwd(const Geom& g, const bf16_t* x, const bf16_t* wf, bf16_t* y,
 
 hipError_t conv_dgrad(const Geom& g, const bf16_t* gy, const bf16_t* wd, const void* add, int add_f32, void* gx, int out_f32,
                       hipStream_t st) {
-    BArgs a = conv_args(g);
+    BArgs a = conv_args<BArgs>(g);
     a.a = gy; a.b = wd; a.out = gx; a.add = add; a.add_f32 = add_f32; a.out_f32 = out_f32;
     a.M = g.n * g.H * g.W; a.N = g.C; a.KK = g.R * g.S * g.K;
     launch_conv<CV_DGRAD>(a, 1, big_tile(a.M, a.N), st);
@@ -561,7 +530,7 @@ hipError_t conv_dgrad(const Geom& g, const bf16_t* gy, const bf16_t* wd, const v
 
 // gw (OIHW fp32, c_real <= C input channels) through `part` (wgrad_floats(g) floats)
 hipError_t conv_wgrad(const Geom& g, const bf16_t* x, const bf16_t* gy, float* part, float* gw, int c_real, hipStream_t st) {
-    BArgs a = conv_args(g);
+    BArgs a = conv_args<BArgs>(g);
     a.a = gy; a.b = x; a.out = part;
     a.M = g.K; a.N = g.R * g.S * g.C; a.KK = g.n * g.Ho * g.Wo;
     int nch;
@@ -575,8 +544,6 @@ hipError_t conv_wgrad(const Geom& g, const bf16_t* x, const bf16_t* gy, float* p
 void pack_weights(const float* w, int K, int C, int Cp, int R, int S, bf16_t* wf, bf16_t* wd, hipStream_t st) {
     hipLaunchKernelGGL(pack_weights_kernel, dim3(nblk((long long)K * R * S * Cp)), dim3(256), 0, st, w, K, C, Cp, R, S, wf, wd);
 }
-
-size_t bn_part_floats(int M, int C) { return (size_t)bn_tiles(M) * 3 * C + 2 * (size_t)C; }
 
 hipError_t bn_fwd(const bf16_t* x, int M, int C, const float* gamma, const float* beta, float* rm, float* rv, int train, float momentum,
                   float eps, const bf16_t* res, int relu, bf16_t* y, float* mean, float* invstd, float* part, hipStream_t st) {
@@ -604,122 +571,62 @@ hipError_t bn_bwd(const bf16_t* gy, const bf16_t* y, const bf16_t* x, int M, int
     return hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------------------------------------------- the trunk plan
-constexpr int NLAYER = 53;
-constexpr int IMG = 224;
-
-struct Layer {
-    int idx, c_real;                     // position in state_dict order; input channels of the fp32 weight (3 for the stem)
-    Geom g;
-    bf16_t *in, *z, *a;                  // conv input, conv output (pre-BN), BN output
-    bf16_t *wf, *wd;                     // this call's packed bf16 weights
-    float *mean, *invstd;
+// ---------------------------------------------------------------------------------------------------------------- the trunk walks
+// The bf16 backend of trunk_walk.inc: NHWC bf16 activations and activation gradients on channel counts padded to 8, a bf16 copy of
+// the fp32 master weights packed into the workspace in front of every forward convolution (the fp32 parameter `w` goes unused
+// after that), element-wise kernels on 8 channels per thread.
+struct Bf16Ops {
+    using act = bf16_t;
+    using L = Layer<bf16_t>;
+    static constexpr const char *fwd_name = "apg_trunk_fwd_p", *bwd_name = "apg_trunk_bwd_p";
+    static constexpr bool ws_aligned = true, packed = true;
+    static int cpad(int C) { return (C + 7) & ~7; }
+    static void pack(const L& l, const float* w, hipStream_t st) { pack_weights(w, l.g.K, l.c_real, l.g.C, l.g.R, l.g.S, l.wf, l.wd, st); }
+    static hipError_t conv_fwd(const L& l, const float*, hipStream_t st) { return ::conv_fwd(l.g, l.in, l.wf, l.z, st); }
+    static hipError_t conv_dgrad(const L& l, const bf16_t* gy, const float*, const bf16_t* add, bf16_t* gx, hipStream_t st) {
+        return ::conv_dgrad(l.g, gy, l.wd, add, 0, gx, 0, st);
+    }
+    static hipError_t conv_wgrad(const L& l, const bf16_t* gz, float* part, float* gw, hipStream_t st) {
+        return ::conv_wgrad(l.g, l.in, gz, part, gw, l.c_real, st);
+    }
+    static constexpr auto bn_fwd = &::bn_fwd;
+    static constexpr auto bn_bwd = &::bn_bwd;
+    static void maxpool_fwd(const bf16_t* x, int n, int H, int C, bf16_t* y, hipStream_t st) {
+        const int Ho = (H - 1) / 2 + 1;
+        hipLaunchKernelGGL(bmaxpool_fwd_kernel, dim3(nblk((long long)n * Ho * Ho * C / 8)), dim3(256), 0, st, x, n, H, H, C, Ho, Ho, y);
+    }
+    static void maxpool_bwd(const bf16_t* x, const bf16_t* gy, int n, int H, int C, bf16_t* gx, hipStream_t st) {
+        const int Ho = (H - 1) / 2 + 1;
+        hipLaunchKernelGGL(bmaxpool_bwd_kernel, dim3(nblk((long long)n * H * H * C / 8)), dim3(256), 0, st, x, gy, n, H, H, C, Ho, Ho, gx);
+    }
+    static void avgpool_fwd(const bf16_t* x, int n, int C, float* y, hipStream_t st) {
+        hipLaunchKernelGGL(bavgpool_fwd_kernel, dim3(nblk((long long)n * C)), dim3(256), 0, st, x, n, C, y);
+    }
+    static void avgpool_bwd(const float* gy, int n, int C, bf16_t* gx, hipStream_t st) {
+        hipLaunchKernelGGL(bavgpool_bwd_kernel, dim3(nblk((long long)n * 49 * C / 8)), dim3(256), 0, st, gy, n, C, gx);
+    }
+    static void crops_in(const float* x, int n, bf16_t* ximg, hipStream_t st) {
+        hipLaunchKernelGGL(nchw_to_nhwc8_kernel, dim3(nblk((long long)n * IMG * IMG)), dim3(256), 0, st, x, n, 3, IMG * IMG, ximg);
+    }
+    // fp32 crop gradient: 8 channels per pixel in g2 (a bf16 buffer of the largest activation holds exactly that), then NCHW
+    static hipError_t crop_grad(const L& stem, const float*, const bf16_t* g1, bf16_t* g2, int n, float* g_x, hipStream_t st) {
+        hipError_t e = ::conv_dgrad(stem.g, g1, stem.wd, nullptr, 0, g2, 1, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(nhwc8_to_nchw_kernel, dim3(nblk((long long)n * 3 * IMG * IMG)), dim3(256), 0, st, (const float*)g2, n, 3,
+                           IMG * IMG, g_x);
+        return hipGetLastError();
+    }
+    // the downsample's data gradient stays fp32 (g3 and g2 are free here and adjacent: 2 x big bytes hold the block input in fp32)
+    // and conv1's data gradient adds it before the one rounding
+    static hipError_t ds_block_dgrad(const L& ds, const float*, const bf16_t* gres, const L& c1, const float*, const bf16_t* g1,
+                                     bf16_t* g3, bf16_t* gnext, hipStream_t st) {
+        hipError_t e = ::conv_dgrad(ds.g, gres, ds.wd, nullptr, 0, g3, 1, st);
+        if (e != hipSuccess) return e;
+        return ::conv_dgrad(c1.g, g1, c1.wd, g3, 1, gnext, 0, st);
+    }
 };
-
-struct Block {
-    Layer c1, c2, c3, ds;
-    bool has_ds;
-};
-
-struct Plan {
-    Layer stem;
-    bf16_t *ximg, *pool;                 // 8-channel NHWC bf16 copy of the crops; max-pool output
-    Block blk[16];
-    bf16_t* G[6];                        // backward: gradient buffers of the largest activation
-    float* part;                         // split-K / BN partials
-    size_t total;                        // bytes
-};
-
-// The walk of trunk_grad.hip's make_plan with bf16 activations.  base == nullptr: sizes only.  Every buffer starts on a 256-byte
-// boundary.  Order: packed weights (wf, and wd when save = 1, per layer), then activations / statistics as the fp32 plan lists them,
-// the six gradient
-// buffers (save = 1), the fp32 partials.
-Plan make_plan(int n, int save, char* base) {
-    Plan P;
-    size_t off = 0;
-    auto take = [&](size_t bytes) -> char* {
-        char* p = base ? base + off : nullptr;
-        off += align256(bytes);
-        return p;
-    };
-    const size_t big = (size_t)n * 112 * 112 * 64 * 2;      // the largest activation in bytes (= the fp32 8-channel crop gradient)
-    bf16_t* slot[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t part = 0;
-    std::vector<Layer*> order;
-    auto mk = [&](Layer& L, int idx, bf16_t* in, int H, int C, int K, int R, int st, int pad, bf16_t* zs) {
-        L.idx = idx;
-        L.c_real = C;
-        const int Cp = (C + 7) & ~7;
-        L.g = make_geom(n, H, H, Cp, K, R, R, st, pad);
-        L.in = in;
-        L.wf = (bf16_t*)take((size_t)K * R * R * Cp * 2);
-        L.wd = save ? (bf16_t*)take((size_t)K * R * R * Cp * 2) : nullptr;    // the data gradient's packing: backward only
-        const size_t sz = (size_t)n * L.g.Ho * L.g.Wo * K * 2;
-        L.z = save ? (bf16_t*)take(sz) : zs;
-        L.a = save ? (bf16_t*)take(sz) : zs;
-        L.mean = (float*)take((size_t)K * 4);
-        L.invstd = (float*)take((size_t)K * 4);
-        part = std::max(part, wgrad_floats(L.g));
-        part = std::max(part, bn_part_floats(n * L.g.Ho * L.g.Wo, K));
-    };
-    if (!save)
-        for (int k = 0; k < 5; ++k) slot[k] = (bf16_t*)take(big);
-    P.ximg = save ? (bf16_t*)take((size_t)n * IMG * IMG * 8 * 2) : slot[0];
-    mk(P.stem, 0, P.ximg, IMG, 3, 64, 7, 2, 3, slot[1]);
-    P.pool = save ? (bf16_t*)take((size_t)n * 56 * 56 * 64 * 2) : slot[2];
-    bf16_t* x = P.pool;
-    int H = 56, C = 64, idx = 1, bi = 0;
-    int free_slots[3] = {0, 1, 3};
-    int in_slot = 2, ds_slot = 4;
-    const int layers[4] = {3, 4, 6, 3}, planes[4] = {64, 128, 256, 512};
-    for (int li = 0; li < 4; ++li)
-        for (int b = 0; b < layers[li]; ++b, ++bi) {
-            const int p = planes[li], st = (b == 0 && li > 0) ? 2 : 1;
-            Block& B = P.blk[bi];
-            B.has_ds = b == 0;
-            bf16_t *s1 = nullptr, *s2 = nullptr, *s3 = nullptr;
-            if (!save) { s1 = slot[free_slots[0]]; s2 = slot[free_slots[1]]; s3 = slot[free_slots[2]]; }
-            mk(B.c1, idx++, x, H, C, p, 1, 1, 0, s1);
-            mk(B.c2, idx++, B.c1.a, H, p, p, 3, st, 1, s2);
-            const int Ho = B.c2.g.Ho;
-            mk(B.c3, idx++, B.c2.a, Ho, p, 4 * p, 1, 1, 0, s3);
-            if (B.has_ds) mk(B.ds, idx++, x, H, C, 4 * p, 1, st, 0, save ? nullptr : slot[ds_slot]);
-            x = B.c3.a;
-            H = Ho;
-            C = 4 * p;
-            if (!save) {
-                const int o = free_slots[2];
-                free_slots[2] = in_slot;
-                in_slot = o;
-            }
-        }
-    for (int k = 0; k < 6; ++k) P.G[k] = save ? (bf16_t*)take(big) : nullptr;
-    P.part = (float*)take(part * 4);
-    P.total = off;
-    return P;
-}
-
-const float* prm(const void* const* t, int layer, int k) { return (const float*)t[layer * 5 + k]; }
-
-int check_table(const void* const* params, const char* what) {
-    if (!params) return apg_fail(APG_EINVAL, std::string(what) + ": parameter table missing");
-    for (int k = 0; k < NLAYER * 5; ++k)
-        if (!params[k]) return apg_fail(APG_EINVAL, std::string(what) + ": parameter table entry " + std::to_string(k) + " is NULL");
-    return APG_OK;
-}
-
-int64_t bf16_trunk_bytes(int n, int save) {
-    if (n <= 0 || n > 2048) return -1;
-    return (int64_t)make_plan(n, save ? 1 : 0, nullptr).total;
-}
 
 }  // namespace
-
-#define APG_TRY(expr)                                                                               \
-    do {                                                                                            \
-        hipError_t _e = (expr);                                                                     \
-        if (_e != hipSuccess) return apg_fail((int)_e, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
 
 extern "C" {
 
@@ -738,7 +645,7 @@ int apg_pack_weights_bf16(const float* w, int K, int C, int Cp, int R, int S, vo
 int apg_conv_fwd_bf16(const void* x, int n, int H, int W, int C, const void* wf, int K, int R, int S, int stride, int pad, void* y,
                       void* stream) {
     const Geom g = make_geom(n, H, W, C, K, R, S, stride, pad);
-    if (!x || !wf || !y || !geom_ok(g) || !al16(x) || !al16(wf) || !al16(y))
+    if (!x || !wf || !y || !geom_ok8(g) || !al16(x) || !al16(wf) || !al16(y))
         return apg_fail(APG_EINVAL, "apg_conv_fwd_bf16: bad argument (C and C_out multiples of 8, pointers 16-byte aligned)");
     APG_TRY(conv_fwd(g, (const bf16_t*)x, (const bf16_t*)wf, (bf16_t*)y, (hipStream_t)stream));
     return APG_OK;
@@ -746,7 +653,7 @@ int apg_conv_fwd_bf16(const void* x, int n, int H, int W, int C, const void* wf,
 
 int64_t apg_conv_bwd_bf16_workspace_bytes(int n, int H, int W, int C, int K, int R, int S, int stride, int pad) {
     const Geom g = make_geom(n, H, W, C, K, R, S, stride, pad);
-    if (!geom_ok(g)) return -1;
+    if (!geom_ok8(g)) return -1;
     return (int64_t)(wgrad_floats(g) * sizeof(float));
 }
 
@@ -754,7 +661,7 @@ int apg_conv_bwd_bf16(const void* x, int n, int H, int W, int C, const void* wd,
                       const void* add, int add_fp32, void* gx, int gx_fp32, float* gw, int gw_channels, void* workspace, int64_t workspace_bytes,
                       void* stream) {
     const Geom g = make_geom(n, H, W, C, K, R, S, stride, pad);
-    if (!gy || !geom_ok(g) || (!gx && !gw) || (gx && !wd) || (gw && !x) || !al16(gy) || !al16(x) || !al16(wd) || !al16(gx) || !al16(add) ||
+    if (!gy || !geom_ok8(g) || (!gx && !gw) || (gx && !wd) || (gw && !x) || !al16(gy) || !al16(x) || !al16(wd) || !al16(gx) || !al16(add) ||
         (add && (!gx || gx_fp32)) || (add && add_fp32 && add == gx) || (gw && (gw_channels <= 0 || gw_channels > C)))
         return apg_fail(APG_EINVAL, "apg_conv_bwd_bf16: bad argument (C and C_out multiples of 8, pointers 16-byte aligned, "
                                     "1 <= gw_channels <= C)");
@@ -840,104 +747,21 @@ int apg_avgpool_bwd_bf16(const float* gy, int n, int C, void* gx, void* stream) 
 int64_t apg_trunk_workspace_bytes_p(int n, int save, int precision) {
     if (precision == APG_PREC_FP32) return apg_trunk_workspace_bytes(n, save);
     if (precision != APG_PREC_BF16) return -1;
-    return bf16_trunk_bytes(n, save);
+    return trunk_bytes<Bf16Ops>(n, save);
 }
 
 int apg_trunk_fwd_p(int precision, int n, const float* x, const void* const* params, int train, float momentum, float eps, float* xf,
                     int save, void* workspace, int64_t workspace_bytes, void* stream) {
     if (precision == APG_PREC_FP32) return apg_trunk_fwd(n, x, params, train, momentum, eps, xf, save, workspace, workspace_bytes, stream);
     if (precision != APG_PREC_BF16) return apg_fail(APG_EINVAL, "apg_trunk_fwd_p: unknown precision " + std::to_string(precision));
-    if (n <= 0 || n > 2048 || !x || !xf || !workspace || !(eps >= 0.f) || (train && !(momentum >= 0.f && momentum <= 1.f)))
-        return apg_fail(APG_EINVAL, "apg_trunk_fwd_p: bad argument");
-    if (((uintptr_t)workspace & 255) != 0) return apg_fail(APG_EINVAL, "apg_trunk_fwd_p: the workspace must be 256-byte aligned");
-    if (int rc = check_table(params, "apg_trunk_fwd_p")) return rc;
-    if (workspace_bytes < bf16_trunk_bytes(n, save))
-        return apg_fail(APG_ENOMEM, "apg_trunk_fwd_p: workspace of " + std::to_string(workspace_bytes) + " bytes, " +
-                                        std::to_string(bf16_trunk_bytes(n, save)) + " needed");
-    hipStream_t st = (hipStream_t)stream;
-    const Plan P = make_plan(n, save ? 1 : 0, (char*)workspace);
-    auto run = [&](const Layer& L, const bf16_t* res, int relu) -> hipError_t {
-        pack_weights(prm(params, L.idx, 0), L.g.K, L.c_real, L.g.C, L.g.R, L.g.S, L.wf, L.wd, st);
-        hipError_t e = conv_fwd(L.g, L.in, L.wf, L.z, st);
-        if (e != hipSuccess) return e;
-        return bn_fwd(L.z, n * L.g.Ho * L.g.Wo, L.g.K, prm(params, L.idx, 1), prm(params, L.idx, 2), (float*)prm(params, L.idx, 3),
-                      (float*)prm(params, L.idx, 4), train, momentum, eps, res, relu, L.a, L.mean, L.invstd, P.part, st);
-    };
-    hipLaunchKernelGGL(nchw_to_nhwc8_kernel, dim3(nblk((long long)n * IMG * IMG)), dim3(256), 0, st, x, n, 3, IMG * IMG, P.ximg);
-    APG_TRY(run(P.stem, nullptr, 1));
-    hipLaunchKernelGGL(bmaxpool_fwd_kernel, dim3(nblk((long long)n * 56 * 56 * 64 / 8)), dim3(256), 0, st, P.stem.a, n, 112, 112, 64, 56,
-                       56, P.pool);
-    APG_TRY(hipGetLastError());
-    for (int b = 0; b < 16; ++b) {
-        const Block& B = P.blk[b];
-        APG_TRY(run(B.c1, nullptr, 1));
-        APG_TRY(run(B.c2, nullptr, 1));
-        if (B.has_ds) APG_TRY(run(B.ds, nullptr, 0));
-        APG_TRY(run(B.c3, B.has_ds ? B.ds.a : B.c1.in, 1));
-    }
-    hipLaunchKernelGGL(bavgpool_fwd_kernel, dim3(nblk((long long)n * 2048)), dim3(256), 0, st, P.blk[15].c3.a, n, 2048, xf);
-    APG_TRY(hipGetLastError());
-    return APG_OK;
+    return trunk_fwd_walk<Bf16Ops>(n, x, params, train, momentum, eps, xf, save, workspace, workspace_bytes, stream);
 }
 
 int apg_trunk_bwd_p(int precision, int n, const void* const* params, int train, const float* g_xf, void* const* g_params, float* g_x,
                     void* workspace, int64_t workspace_bytes, void* stream) {
     if (precision == APG_PREC_FP32) return apg_trunk_bwd(n, params, train, g_xf, g_params, g_x, workspace, workspace_bytes, stream);
     if (precision != APG_PREC_BF16) return apg_fail(APG_EINVAL, "apg_trunk_bwd_p: unknown precision " + std::to_string(precision));
-    if (n <= 0 || n > 2048 || !g_xf || !g_params || !workspace) return apg_fail(APG_EINVAL, "apg_trunk_bwd_p: bad argument");
-    if (((uintptr_t)workspace & 255) != 0) return apg_fail(APG_EINVAL, "apg_trunk_bwd_p: the workspace must be 256-byte aligned");
-    if (int rc = check_table(params, "apg_trunk_bwd_p")) return rc;
-    if (workspace_bytes < bf16_trunk_bytes(n, 1))
-        return apg_fail(APG_ENOMEM, "apg_trunk_bwd_p: workspace of " + std::to_string(workspace_bytes) + " bytes, " +
-                                        std::to_string(bf16_trunk_bytes(n, 1)) + " needed (the one apg_trunk_fwd_p filled, save = 1)");
-    hipStream_t st = (hipStream_t)stream;
-    const Plan P = make_plan(n, 1, (char*)workspace);
-    bf16_t *gcur = P.G[0], *gnext = P.G[1], *g3 = P.G[2], *g2 = P.G[3], *g1 = P.G[4], *gres = P.G[5];
-    auto gp = [&](const Layer& L, int k) { return (float*)g_params[L.idx * 3 + k]; };
-    auto bnb = [&](const Layer& L, const bf16_t* gy, int relu, bf16_t* gx, bf16_t* g_res) -> hipError_t {
-        return bn_bwd(gy, relu ? L.a : nullptr, L.z, n * L.g.Ho * L.g.Wo, L.g.K, prm(params, L.idx, 1), L.mean, L.invstd, train, gx,
-                      g_res, gp(L, 1), gp(L, 2), P.part, st);
-    };
-    auto wg = [&](const Layer& L, const bf16_t* gz) -> hipError_t {
-        if (!gp(L, 0)) return hipSuccess;
-        return conv_wgrad(L.g, L.in, gz, P.part, gp(L, 0), L.c_real, st);
-    };
-    hipLaunchKernelGGL(bavgpool_bwd_kernel, dim3(nblk((long long)n * 49 * 2048 / 8)), dim3(256), 0, st, g_xf, n, 2048, gcur);
-    APG_TRY(hipGetLastError());
-    for (int b = 15; b >= 0; --b) {
-        const Block& B = P.blk[b];
-        APG_TRY(bnb(B.c3, gcur, 1, g3, gres));
-        APG_TRY(wg(B.c3, g3));
-        APG_TRY(conv_dgrad(B.c3.g, g3, B.c3.wd, nullptr, 0, g2, 0, st));
-        APG_TRY(bnb(B.c2, g2, 1, g2, nullptr));
-        APG_TRY(wg(B.c2, g2));
-        APG_TRY(conv_dgrad(B.c2.g, g2, B.c2.wd, nullptr, 0, g1, 0, st));
-        APG_TRY(bnb(B.c1, g1, 1, g1, nullptr));
-        APG_TRY(wg(B.c1, g1));
-        if (B.has_ds) {
-            APG_TRY(bnb(B.ds, gres, 0, gres, nullptr));
-            APG_TRY(wg(B.ds, gres));
-            // the downsample's data gradient stays fp32 (g3 and g2 are free here and adjacent: 2 x big bytes hold the block
-            // input in fp32) and conv1's data gradient adds it before the one rounding
-            APG_TRY(conv_dgrad(B.ds.g, gres, B.ds.wd, nullptr, 0, g3, 1, st));
-            APG_TRY(conv_dgrad(B.c1.g, g1, B.c1.wd, g3, 1, gnext, 0, st));
-        } else {
-            APG_TRY(conv_dgrad(B.c1.g, g1, B.c1.wd, gres, 0, gnext, 0, st));
-        }
-        std::swap(gcur, gnext);
-    }
-    hipLaunchKernelGGL(bmaxpool_bwd_kernel, dim3(nblk((long long)n * 112 * 112 * 64 / 8)), dim3(256), 0, st, P.stem.a, gcur, n, 112, 112,
-                       64, 56, 56, g1);
-    APG_TRY(hipGetLastError());
-    APG_TRY(bnb(P.stem, g1, 1, g1, nullptr));
-    APG_TRY(wg(P.stem, g1));
-    if (g_x) {                                                   // fp32 crop gradient: 8 channels per pixel in g2, then NCHW
-        APG_TRY(conv_dgrad(P.stem.g, g1, P.stem.wd, nullptr, 0, g2, 1, st));
-        hipLaunchKernelGGL(nhwc8_to_nchw_kernel, dim3(nblk((long long)n * 3 * IMG * IMG)), dim3(256), 0, st, (const float*)g2, n, 3,
-                           IMG * IMG, g_x);
-        APG_TRY(hipGetLastError());
-    }
-    return APG_OK;
+    return trunk_bwd_walk<Bf16Ops>(n, params, train, g_xf, g_params, g_x, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"
