@@ -5,6 +5,15 @@ Public mirrors of the reference interfaces:
   smplx.SMPLX                          <- the smplx submodule as called by copenet_twoview.py
   geometry.rot6d_to_rotmat / perspective_projection, utils.transform_smpl
   pipeline.TwoViewInference            <- inference branch of copenet_twoview.fwd_pass_and_loss
+  TrainingLoss (loss.py)               <- get_loss of copenet_twoview / copenet_singleview / hmr / muhmr
 The compute lives in libairpose_hip.so (include/airpose_hip.h); nothing here falls back to CPU.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # airpose_amd.TrainingLoss, resolved on first use: importing the package loads neither loss.py nor the gradient library
+    if name == "TrainingLoss":
+        from .loss import TrainingLoss
+        return TrainingLoss
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -62,6 +62,9 @@ SIGNATURES = {
     "apg_trunk_workspace_bytes_p": (_i64, [_i, _i, _i]),
     "apg_trunk_fwd_p": (_i, [_i, _i, _vp, _vpp, _i, _f, _f, _vp, _i, _vp, _i64, _vp]),
     "apg_trunk_bwd_p": (_i, [_i, _i, _vpp, _i, _vp, _vpp, _vp, _vp, _i64, _vp]),
+    # the training loss and its gradient seeds (loss_grad.hip)
+    "apg_loss_workspace_bytes": (_i64, [_i, _i]),
+    "apg_loss_fwd_bwd": (_i, [_i] * 6 + [_c.POINTER(_f), _vpp, _vpp, _vp, _vpp, _vp, _i64, _vp]),
 }
 PRECISIONS = {"fp32": 0, "bf16": 1}          # include/airpose_grad.h: APG_PREC_*
 

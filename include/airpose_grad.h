@@ -281,6 +281,69 @@ int apg_trunk_fwd_p(int precision, int n, const float* x, const void* const* par
 int apg_trunk_bwd_p(int precision, int n, const void* const* params, int train, const float* g_xf, void* const* g_params, float* g_x,
                     void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The training loss (loss_grad.hip): get_loss of the four reference trainers (copenet_twoview.py:83-161, copenet_singleview.py:
+ * 76-117, hmr.py:75-116, muhmr.py:76-131) and the gradient of the total with respect to every prediction, in one pass.  Additive
+ * under ABI 2: a binding tells a library that has it by looking up apg_loss_fwd_bwd.
+ *
+ * With m(x) the mean of x over all its elements, and per view v (summed over the views):
+ *   trans          m((trans_v - gt_trans_v)^2)                                  (B x 3); absent when trans is NULL
+ *   keypoints      m((j2d_v[:, :22] - gt_j2d_v[:, :22])^2)                      (B x 22 x 2)
+ *   keypoints_3d   m(L3 * sum_v (joints_v[:, :22] - gt_joints[:, :22])^2 [+ (joints_0 - joints_1)^2])     ONE mean over B x 22 x 3;
+ *                  L3 = limbs3d on joints {4, 5, 18, 19}, limbs3d^2 on {7, 8, 20, 21}, 1 elsewhere
+ *   shape          m((verts_v - gt_verts)^2) [+ m((verts_0 - verts_1)^2)]       (B x V x 3)
+ *   rootrot        m((rotmat_v[:, 0] - gt_root_v)^2)                            (B x 3 x 3)
+ *   pose           m(LT * sum_v (rotmat_v[:, 1:] - gt_pose)^2 [+ (rotmat_0[:, 1:] - rotmat_1[:, 1:])^2])  ONE mean over B x 21 x 9;
+ *                  LT = limbstheta on rotations {3, 4, 17, 18} of the 21, limbstheta^2 on {6, 7, 19, 20}
+ *   betas          m(betas_v^2) [+ m((betas_0 - betas_1)^2)]                    (B x 10)
+ *   cam            m(exp(-10 cam_v[:, 0])^2)                                    (B); absent when cam is NULL
+ *   loss           scale * (w_trans trans + w_kp2d keypoints + w_kp3d keypoints_3d + w_shape shape + w_rootrot rootrot
+ *                           + w_pose pose + w_beta betas + w_cam cam)
+ * The bracketed cross-view shares exist with two views and their APG_LOSS_CROSS_* bit: the two-view trainer sets all four, muhmr
+ * APG_LOSS_CROSS_POSE alone, the single-view trainer and hmr (nviews = 1) none.  The reference's scale is 60 and its w_cam is 1.
+ *
+ *   weights: HOST array of 11 floats, indexed by APG_LOSS_W_*.
+ *   pred: HOST array of APG_LOSS_PER_VIEW * nviews device pointers; per view trans (B x 3), rotmat (B x 22 x 3 x 3), betas (B x 10),
+ *     joints (B x J x 3), verts (B x V x 3), j2d (B x J x 2), cam (B x 3).  J >= 22; rows 22 .. J - 1 are never read.  trans and cam may
+ *     be NULL (for both views or for neither); the others are required.  The two views may be the same pointers.
+ *   gt: HOST array of 3 + 3 * nviews device pointers: gt_pose (B x 21 x 3 x 3), gt_joints (B x Jg x 3), gt_verts (B x V x 3), then per
+ *     view gt_root (B x 3 x 3), gt_j2d (B x Jg x 2), gt_trans (B x 3; required when trans is given).  Jg >= 22.
+ *   terms: 9 device floats, written in the order loss, trans, keypoints, keypoints_3d, shape, rootrot, pose, betas, cam; an absent term
+ *     is written as 0.
+ *   grads: NULL (no gradient: a forward-only call), or a HOST array of APG_LOSS_PER_VIEW * nviews device pointers in pred's order and
+ *     shapes, each NULL = not needed.  Each given gradient is written in full, not accumulated: d loss / d input, rows >= 22 of
+ *     g_joints / g_j2d and columns 1, 2 of g_cam as zeros.  A gradient of an absent trans / cam is APG_EINVAL.  No output may overlap
+ *     an input or another output.
+ *   workspace: at least apg_loss_workspace_bytes(B, V) bytes (negative for B < 1 or V < 1), else APG_ENOMEM; the per-workgroup
+ *     partial sums.  It carries nothing from call to call and needs no initialisation.
+ * Pointers need only their natural 4-byte alignment; when every vertex pointer is 16-byte aligned the vertex stream moves in 16-byte
+ * accesses.  Determinism: no atomics; every sum is per-thread in index order, a fixed tree per workgroup, and the workgroups'
+ * partials in index order.  The partition depends on (B, V, J) alone -- not on the pointers, their alignment or which gradients are
+ * asked for -- so terms and gradients are bit-identical from run to run and from one such choice to another.
+ * Two launches.  B < 1, V < 1, J < 22, Jg < 22, nviews outside {1, 2}, cross bits with nviews = 1 and a NULL required pointer are
+ * APG_EINVAL before any launch. */
+#define APG_LOSS_CROSS_JOINTS 1
+#define APG_LOSS_CROSS_VERTS 2
+#define APG_LOSS_CROSS_POSE 4
+#define APG_LOSS_CROSS_BETAS 8
+#define APG_LOSS_CROSS_ALL 15
+#define APG_LOSS_PER_VIEW 7
+#define APG_LOSS_NTERMS 9
+#define APG_LOSS_W_TRANS 0
+#define APG_LOSS_W_KEYPOINT2D 1
+#define APG_LOSS_W_KEYPOINT3D 2
+#define APG_LOSS_W_SHAPE 3
+#define APG_LOSS_W_ROOTROT 4
+#define APG_LOSS_W_POSE 5
+#define APG_LOSS_W_BETA 6
+#define APG_LOSS_W_CAM 7
+#define APG_LOSS_W_LIMBS3D 8
+#define APG_LOSS_W_LIMBSTHETA 9
+#define APG_LOSS_W_SCALE 10
+int64_t apg_loss_workspace_bytes(int B, int V);
+int apg_loss_fwd_bwd(int nviews, int cross, int B, int J, int Jg, int V, const float* weights, const void* const* pred,
+                     const void* const* gt, float* terms, void* const* grads, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
