@@ -6,6 +6,7 @@ Public mirrors of the reference interfaces:
   geometry.rot6d_to_rotmat / perspective_projection, utils.transform_smpl
   pipeline.TwoViewInference            <- inference branch of copenet_twoview.fwd_pass_and_loss
   TrainingLoss (loss.py)               <- get_loss of copenet_twoview / copenet_singleview / hmr / muhmr
+  FusedAdam (optim.py)                 <- torch.optim.Adam(..., amsgrad=True) of the trainers' configure_optimizers
 The compute lives in libairpose_hip.so (include/airpose_hip.h); nothing here falls back to CPU.
 """
 __version__ = "0.1.0"
@@ -16,4 +17,7 @@ def __getattr__(name):
     if name == "TrainingLoss":
         from .loss import TrainingLoss
         return TrainingLoss
+    if name == "FusedAdam":                                               # likewise (optim.py)
+        from .optim import FusedAdam
+        return FusedAdam
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

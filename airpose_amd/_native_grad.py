@@ -65,6 +65,8 @@ SIGNATURES = {
     # the training loss and its gradient seeds (loss_grad.hip)
     "apg_loss_workspace_bytes": (_i64, [_i, _i]),
     "apg_loss_fwd_bwd": (_i, [_i] * 6 + [_c.POINTER(_f), _vpp, _vpp, _vp, _vpp, _vp, _i64, _vp]),
+    # the optimizer step (optim.hip)
+    "apg_adam_step": (_i, [_i] + [_vpp] * 5 + [_c.POINTER(_i64)] * 2 + [_c.c_double] * 5 + [_vp]),
 }
 PRECISIONS = {"fp32": 0, "bf16": 1}          # include/airpose_grad.h: APG_PREC_*
 

@@ -344,6 +344,39 @@ int64_t apg_loss_workspace_bytes(int B, int V);
 int apg_loss_fwd_bwd(int nviews, int cross, int B, int J, int Jg, int V, const float* weights, const void* const* pred,
                      const void* const* gt, float* terms, void* const* grads, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The optimizer step (optim.hip): torch.optim.Adam's update (_single_tensor_adam with maximize = False; L2 weight decay, not the
+ * decoupled AdamW form), with or without amsgrad, over a whole list of fp32 tensors in one pass.  Additive under ABI 2: a binding
+ * tells a library that has it by looking up apg_adam_step.
+ *
+ * Per element of tensor i, in place:
+ *   g'   = g + weight_decay p
+ *   m    = m + (1 - beta1) (g' - m)
+ *   v    = beta2 v + (1 - beta2) g'^2
+ *   vmax = max(vmax, v)                                                    (amsgrad only, taken after v is updated)
+ *   p    = p - (lr / (1 - beta1^step[i])) m / (sqrt(vmax or v) / sqrt(1 - beta2^step[i]) + eps)
+ * g is read only.  The host forms lr / (1 - beta1^step[i]) and 1 / sqrt(1 - beta2^step[i]) in double per tensor and rounds each to
+ * float once, as it does weight_decay, 1 - beta1, beta2, 1 - beta2 and eps; optim.hip states which products of the sequence are
+ * fused.
+ *
+ *   p, g, m, v, vmax: HOST arrays of ntensors device pointers (like apg_trunk_fwd's params table).  vmax = NULL (the table itself)
+ *     selects plain Adam; any other table NULL is APG_EINVAL.
+ *   numel, step: HOST arrays of ntensors counts.  step[i] >= 1 is tensor i's step count AFTER this update (torch keeps one per
+ *     parameter: a parameter that had no gradient for some steps lags the others).  numel[i] = 0 is accepted and the tensor skipped.
+ * The call is stateless: no handle, no workspace, no device-side table, no host synchronisation; the tensors travel in the kernels'
+ * argument blocks, 64 per launch, so there are ceil(tensors with elements / 64) launches, each of one workgroup per 4096 elements of
+ * each tensor.  Pointers need only 4-byte alignment: a tensor whose pointers are all 16-byte aligned moves in 16-byte accesses, any
+ * other in 4-byte accesses, with identical arithmetic -- alignment does not change a bit of any result.  No atomics and no
+ * reduction, so results are bit-identical from run to run.
+ * Two tensors of one call must not overlap (neither two of its 5 ntensors arrays, nor the same array under two indices).  The
+ * library does not check this.
+ * APG_EINVAL, before any launch and with nothing written: ntensors < 0, a NULL table other than vmax, a NULL numel or step, a
+ * NULL or not 4-byte aligned pointer of a tensor with numel > 0 (a misaligned one also with numel = 0), numel[i] < 0 or above
+ * (2^31 - 1) * 4096, step[i] < 1, lr < 0, eps < 0, weight_decay < 0, beta1 or beta2 outside [0, 1) (a NaN fails each of these). */
+int apg_adam_step(int ntensors, const void* const* p, const void* const* g, const void* const* m, const void* const* v,
+                  const void* const* vmax, const int64_t* numel, const int64_t* step, double lr, double beta1, double beta2, double eps,
+                  double weight_decay, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
