@@ -6,6 +6,7 @@ Public mirrors of the reference interfaces:
   geometry.rot6d_to_rotmat / perspective_projection, utils.transform_smpl
   pipeline.TwoViewInference            <- inference branch of copenet_twoview.fwd_pass_and_loss
   TrainingLoss (loss.py)               <- get_loss of copenet_twoview / copenet_singleview / hmr / muhmr
+  RealDataLoss (loss_real.py)          <- get_loss of the copenet_real fine-tune trainers (2-D keypoints + VPoser prior)
   FusedAdam (optim.py)                 <- torch.optim.Adam(..., amsgrad=True) of the trainers' configure_optimizers
 The compute lives in libairpose_hip.so (include/airpose_hip.h); nothing here falls back to CPU.
 """
@@ -17,6 +18,9 @@ def __getattr__(name):
     if name == "TrainingLoss":
         from .loss import TrainingLoss
         return TrainingLoss
+    if name == "RealDataLoss":                                            # likewise (loss_real.py)
+        from .loss_real import RealDataLoss
+        return RealDataLoss
     if name == "FusedAdam":                                               # likewise (optim.py)
         from .optim import FusedAdam
         return FusedAdam

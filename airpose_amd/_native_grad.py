@@ -65,6 +65,11 @@ SIGNATURES = {
     # the training loss and its gradient seeds (loss_grad.hip)
     "apg_loss_workspace_bytes": (_i64, [_i, _i]),
     "apg_loss_fwd_bwd": (_i, [_i] * 6 + [_c.POINTER(_f), _vpp, _vpp, _vp, _vpp, _vp, _i64, _vp]),
+    # the real-data fine-tuning loss with the VPoser prior (loss_real_grad.hip)
+    "apg_real_loss_workspace_bytes": (_i64, [_i]),
+    "apg_real_loss_encoder_bytes": (_i64, []),
+    "apg_real_loss_pack_encoder": (_i, [_vp] * 5 + [_i64, _vp]),
+    "apg_real_loss_fwd_bwd": (_i, [_i] * 6 + [_f, _c.POINTER(_f), _vp, _vpp, _vpp, _vp, _vpp, _vp, _i64, _vp]),
     # the optimizer step (optim.hip)
     "apg_adam_step": (_i, [_i] + [_vpp] * 5 + [_c.POINTER(_i64)] * 2 + [_c.c_double] * 5 + [_vp]),
 }

@@ -377,6 +377,68 @@ int apg_adam_step(int ntensors, const void* const* p, const void* const* g, cons
                   const void* const* vmax, const int64_t* numel, const int64_t* step, double lr, double beta1, double beta2, double eps,
                   double weight_decay, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The real-data fine-tuning loss (loss_real_grad.hip): get_loss of the reference's copenet_real trainers (copenet_twoview.py:100-160,
+ * copenet_twoview_sep.py:93-150, hmr.py:82-118, hmr_camswap_difffl.py:92-128, spin.py:86-122) and the gradient of the total with
+ * respect to every prediction, in one pass.  2-D keypoints with detector confidences, no 3-D ground truth, a VPoser prior on the body
+ * pose.  Additive under ABI 2: a binding tells a library that has it by looking up apg_real_loss_fwd_bwd.
+ *
+ * With m(x) the mean of x over all its elements, and per view v (summed over the views):
+ *   keypoints   m((j2d_v[:, :22] - gt_v[:, :22, :2])^2 conf_v L2)      (B x 22 x 2); conf_v = gt_v[:, :22, 2];
+ *               L2 = limbs2d on joints {4, 5, 18, 19}, limbs2d^2 on {7, 8, 20, 21}, 1 elsewhere
+ *   vposer      m(z_v^2), z_v = mu + softplus(s) eps_v                  (B x 32); [mu | s] = E(aa_v), aa_v (B x 63) the tgm 0.1.2
+ *               axis-angle of rotmat_v[:, 1:22] (the quaternion branches of the zero-padded 3 x 4 form); E below
+ *   pose        m((rotmat_0[:, 1:] - rotmat_1[:, 1:])^2)                (B x 21 x 9); with APG_LOSS_CROSS_POSE only
+ *   betas       m(betas_v^2) [+ m((betas_0 - betas_1)^2) with APG_LOSS_CROSS_BETAS]      (B x 10)
+ *   depth       m(exp(-depth_gain depth_v[:, depth_col])^2)             (B); unweighted, as in the reference
+ *   loss        scale * (w_kp keypoints + w_beta betas + w_vposer vposer + w_pose pose + depth)
+ * The two-view trainers set APG_LOSS_CROSS_POSE | APG_LOSS_CROSS_BETAS and (depth_col, depth_gain) = (2, 1) on trans; hmr is one
+ * view with (0, 10) on its camera, hmr_camswap and spin one view with (2, 1).  The reference's scale is 60.
+ *
+ * E is VPoser V02_05's encoder_net in eval mode (BatchNorm on running statistics, Dropout the identity), which is two affine maps
+ * around one LeakyReLU(0.01): h = W1 aa + b1 (512), [mu | s] = W2 leaky(h) + b2 (64; rows 0 .. 31 mu, 32 .. 63 the logvar head).
+ * The caller folds the layers (in fp64) into W1 (512 x 63), b1 (512), W2 (64 x 512), b2 (64), row-major fp32 on the device, and
+ * apg_real_loss_pack_encoder lays them out for the kernel in `packed`: apg_real_loss_encoder_bytes() bytes (about 512 KB: each
+ * matrix in both orientations, so that the forward and the backward GEMVs both read it coalesced), opaque, valid until overwritten.
+ * softplus is torch's (threshold 20).
+ *
+ *   weights: HOST array of 6 floats, indexed by APG_REAL_LOSS_W_*.
+ *   encoder: the packed table (device).
+ *   pred: HOST array of APG_REAL_LOSS_PER_VIEW * nviews device pointers; per view rotmat (B x 22 x 3 x 3), betas (B x 10), j2d
+ *     (B x J x 2), depth (B x 3: the view's trans or cam).  J >= 22; rows 22 .. J - 1 are never read.  All required.  The two views
+ *     may be the same pointers.
+ *   gt: HOST array of 2 * nviews device pointers; per view gt (B x Jg x 3: x, y, confidence; Jg >= 22) and eps (B x 32).
+ *   terms: 6 device floats, written in the order loss, vposer, pose, keypoints, betas, depth; an absent term is written as 0.
+ *   grads: NULL (a forward-only call), or a HOST array of APG_REAL_LOSS_PER_VIEW * nviews device pointers in pred's order and
+ *     shapes, each NULL = not needed.  Each given gradient is written in full, not accumulated: rows >= 22 of g_j2d, row 0 of
+ *     g_rotmat and the two other columns of g_depth as exact zeros; rows 1 .. 21 of g_rotmat are the pose term's share plus the
+ *     vposer term's, which goes back through softplus, E and the axis-angle conversion.  (At an exact identity rotation the
+ *     conversion's derivative is the limit 2 daa, where the reference's autograd is NaN.)
+ *   workspace: at least apg_real_loss_workspace_bytes(B) bytes (negative for B < 1 or B > 2^30), else APG_ENOMEM; the per-row partial
+ *     sums.  It carries nothing from call to call and needs no initialisation.
+ * Pointers need only 4-byte alignment; every access is a 4-byte one.  Determinism: no atomics; one workgroup per (view, body) row,
+ * every dot product an fmaf chain in index order (the two long ones in four fixed segments added in order), the rows' partials summed
+ * per view in index order and a fixed tree -- so terms and gradients are bit-identical from run to run, whatever the alignment and
+ * whichever gradients are asked for.  Two launches.
+ * APG_EINVAL before any launch, the message naming the argument: a NULL weights, encoder, pred, gt, terms, workspace or table entry
+ * of pred / gt, B < 1, J < 22, Jg < 22, nviews outside {1, 2}, cross bits other than APG_LOSS_CROSS_POSE | APG_LOSS_CROSS_BETAS or
+ * with nviews = 1, depth_col outside 0 .. 2, and an output (terms, a gradient, the workspace) that overlaps an input. */
+#define APG_REAL_LOSS_PER_VIEW 4
+#define APG_REAL_LOSS_NTERMS 6
+#define APG_REAL_LOSS_W_KEYPOINT2D 0
+#define APG_REAL_LOSS_W_BETA 1
+#define APG_REAL_LOSS_W_VPOSER 2
+#define APG_REAL_LOSS_W_POSE 3
+#define APG_REAL_LOSS_W_LIMBS2D 4
+#define APG_REAL_LOSS_W_SCALE 5
+int64_t apg_real_loss_workspace_bytes(int B);
+int64_t apg_real_loss_encoder_bytes(void);
+int apg_real_loss_pack_encoder(const float* W1, const float* b1, const float* W2, const float* b2, void* packed, int64_t bytes,
+                               void* stream);
+int apg_real_loss_fwd_bwd(int nviews, int cross, int B, int J, int Jg, int depth_col, float depth_gain, const float* weights,
+                          const void* encoder, const void* const* pred, const void* const* gt, float* terms, void* const* grads,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
