@@ -4,13 +4,18 @@
 //                 per workgroup of 4 waves, K in stages of 16 through LDS, v_mfma_f32_16x16x4_f32 (exact fp32):
 //                   CV_FWD    M = n Ho Wo, N = C_out, K = (r, s, c_in)
 //                   CV_DGRAD  M = n H W,   N = C_in,  K = (r, s, c_out), a gather with per-tap validity (stride 2 included)
-//                   CV_WGRAD  M = C_out,   N = (r, s, c_in), K = n Ho Wo in fixed split-K chunks; conv_wgrad_combine_kernel
+//                   CV_WGRAD  M = C_out,   N = (r, s, c_in), K = n Ho Wo in fixed split-K chunks; wgrad_combine_kernel
 //                             sums the chunks in chunk order straight into the OIHW gradient
-//   BatchNorm:    per-channel statistics over the n H W rows as per-tile centred partials (mean, M2) combined by Chan's formula in a
-//                 fixed tree; normalise + affine (+ residual) (+ ReLU) in one pass; backward with the ReLU mask and the residual
-//                 split fused in
+// Everything else is trunk_elem.inc, the one source this file shares with trunk_grad_bf16.hip, instantiated on F32Store (fp32
+// storage, one channel per thread):
+//   BatchNorm:    per-channel statistics over the n H W rows as per-tile centred partials (mean, M2: bn_stats_part_kernel) combined
+//                 by Chan's formula in a fixed tree (bn_stats_final_kernel; eval mode: bn_eval_stats_kernel); normalise + affine
+//                 (+ residual) (+ ReLU) in one pass (bn_apply_kernel); backward with the ReLU mask and the residual split fused in
+//                 (bn_bwd_part_kernel, bn_bwd_final_kernel, bn_bwd_apply_kernel)
 //   pools:        max-pool 3 x 3 / s2 / p1 (padding = -inf, the first maximum in row-major window order takes the gradient, as in
-//                 torch) and avg-pool 7 x 7, forward and backward as gathers
+//                 torch: maxpool_fwd_kernel, maxpool_bwd_kernel) and avg-pool 7 x 7 (avgpool_fwd_kernel, avgpool_bwd_kernel),
+//                 forward and backward as gathers
+//   layout:       wgrad_combine_kernel; nhwc_to_nchw_kernel for the crop gradient
 // No floating-point atomics anywhere: every reduction runs in a fixed order, so results are bit-reproducible run to run.
 #include "ap_common.h"
 #include "grad_internal.h"
@@ -189,186 +194,21 @@ __global__ void __launch_bounds__(256) apg_conv_kernel(const ConvArgs a) {
             }
 }
 
-// gW[co][c][r][s] = sum over the chunks, in chunk order, of part[chunk][co][(r S + s) C + c]
-__global__ void __launch_bounds__(256) conv_wgrad_combine_kernel(const float* __restrict__ part, int nch, int K, int C, int R, int S,
-                                                                 float* __restrict__ gw) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, per = (long long)C * R * S;
-    if (idx >= (long long)K * per) return;
-    const int co = (int)(idx / per), rem = (int)(idx - co * per);
-    const int c = rem / (R * S), rs = rem - c * R * S;
-    const long long src = (long long)co * per + (long long)rs * C + c, stride = (long long)K * per;
-    float s = 0.f;
-    for (int ch = 0; ch < nch; ++ch) s += part[ch * stride + src];
-    gw[idx] = s;
-}
+// ---------------------------------------------------------------------------------------------------------------- BatchNorm, pools
+// fp32 storage for the kernels of trunk_elem.inc: one channel per thread, 4-byte accesses (no alignment demand beyond the float's)
+struct F32Store {
+    using T = float;
+    static constexpr int W = 1;
+    struct V {
+        float v[1];
+    };
+    static __device__ __forceinline__ float rd(float x) { return x; }
+    static __device__ __forceinline__ V ld(const float* p) { return V{{*p}}; }
+    static __device__ __forceinline__ void st(float* p, const V& f) { *p = f.v[0]; }
+};
+#include "trunk_elem.inc"
 
-// ---------------------------------------------------------------------------------------------------------------- BatchNorm
-// Rows (n H W) are cut into tiles of `tr` rows (tr % 4 == 0, at most 256 tiles); a workgroup takes 64 channels x one tile, its 4
-// waves a quarter of the tile each.
-#include "bn_common.inc"
-
-// per tile: count, mean, M2 = sum (x - mean)^2 (centred on the tile's own mean)
-__global__ void __launch_bounds__(256) bn_stats_part_kernel(const float* __restrict__ x, int M, int C, int tr,
-                                                            float* __restrict__ part) {
-    __shared__ float sh[4][64];
-    __shared__ float smean[64];
-    const int t = threadIdx.x, cl = t & 63, g = t >> 6, c = blockIdx.x * 64 + cl, tile = blockIdx.y;
-    const int t0 = tile * tr, tcnt = min(tr, M - t0), r0 = t0 + g * (tr / 4), r1 = min(r0 + tr / 4, M);
-    float s = 0.f;
-    if (c < C)
-        for (int r = r0; r < r1; ++r) s += x[(long long)r * C + c];
-    sh[g][cl] = s;
-    __syncthreads();
-    if (g == 0) smean[cl] = (((sh[0][cl] + sh[1][cl]) + sh[2][cl]) + sh[3][cl]) / (float)tcnt;
-    __syncthreads();
-    const float mean = smean[cl];
-    float m2 = 0.f;
-    if (c < C)
-        for (int r = r0; r < r1; ++r) {
-            const float d = x[(long long)r * C + c] - mean;
-            m2 += d * d;
-        }
-    sh[g][cl] = m2;
-    __syncthreads();
-    if (g == 0 && c < C) {
-        part[((long long)tile * 3 + 0) * C + c] = (float)tcnt;
-        part[((long long)tile * 3 + 1) * C + c] = mean;
-        part[((long long)tile * 3 + 2) * C + c] = ((sh[0][cl] + sh[1][cl]) + sh[2][cl]) + sh[3][cl];
-    }
-}
-
-// y = (x - mean) invstd gamma + beta (+ res) (ReLU); y may alias x or res (same index)
-__global__ void __launch_bounds__(256) bn_apply_kernel(const float* x, long long total, int C, const float* __restrict__ mean,
-                                                       const float* __restrict__ invstd, const float* __restrict__ gamma,
-                                                       const float* __restrict__ beta, const float* res, int relu, float* y) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int c = (int)(idx % C);
-    float v = (x[idx] - mean[c]) * invstd[c] * gamma[c] + beta[c];
-    if (res) v += res[idx];
-    if (relu) v = fmaxf(v, 0.f);
-    y[idx] = v;
-}
-
-// per tile: sum g and sum g xhat, g = gy masked by y > 0 (y NULL: no ReLU)
-__global__ void __launch_bounds__(256) bn_bwd_part_kernel(const float* __restrict__ gy, const float* __restrict__ y,
-                                                          const float* __restrict__ x, int M, int C, int tr, const float* __restrict__ mean,
-                                                          const float* __restrict__ invstd, float* __restrict__ part) {
-    __shared__ float s1[4][64], s2[4][64];
-    const int t = threadIdx.x, cl = t & 63, g = t >> 6, c = blockIdx.x * 64 + cl, tile = blockIdx.y;
-    const int r0 = tile * tr + g * (tr / 4), r1 = min(r0 + tr / 4, M);
-    float a = 0.f, b = 0.f;
-    if (c < C) {
-        const float mu = mean[c], is = invstd[c];
-        for (int r = r0; r < r1; ++r) {
-            const long long o = (long long)r * C + c;
-            float gv = gy[o];
-            if (y && !(y[o] > 0.f)) gv = 0.f;
-            a += gv;
-            b += gv * ((x[o] - mu) * is);
-        }
-    }
-    s1[g][cl] = a;
-    s2[g][cl] = b;
-    __syncthreads();
-    if (g == 0 && c < C) {
-        part[((long long)tile * 2 + 0) * C + c] = ((s1[0][cl] + s1[1][cl]) + s1[2][cl]) + s1[3][cl];
-        part[((long long)tile * 2 + 1) * C + c] = ((s2[0][cl] + s2[1][cl]) + s2[2][cl]) + s2[3][cl];
-    }
-}
-
-// gx = gamma invstd (g - sum g / M - xhat sum(g xhat) / M) (train) or gamma invstd g (eval); g_res = g.  gx may alias gy.
-__global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const float* gy, const float* __restrict__ y, const float* __restrict__ x,
-                                                           long long total, int C, float inv_m, int train, const float* __restrict__ mean,
-                                                           const float* __restrict__ invstd, const float* __restrict__ gamma,
-                                                           const float* __restrict__ sums, float* gx, float* g_res) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int c = (int)(idx % C);
-    float g = gy[idx];
-    if (y && !(y[idx] > 0.f)) g = 0.f;
-    const float k = gamma[c] * invstd[c];
-    float v;
-    if (train) {
-        const float xhat = (x[idx] - mean[c]) * invstd[c];
-        v = k * ((g - sums[c] * inv_m) - xhat * (sums[C + c] * inv_m));
-    } else {
-        v = k * g;
-    }
-    if (g_res) g_res[idx] = g;
-    gx[idx] = v;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- pools
-// max-pool 3 x 3 / s2 / p1, NHWC: padding is -inf; the first maximum in row-major window order is the argmax
-__device__ __forceinline__ int maxpool_arg(const float* __restrict__ x, int b, int ho, int wo, int c, int H, int W, int C, float* best) {
-    float m = -INFINITY;
-    int arg = -1;
-    for (int r = 0; r < 3; ++r) {
-        const int h = ho * 2 - 1 + r;
-        if (h < 0 || h >= H) continue;
-        for (int s = 0; s < 3; ++s) {
-            const int w = wo * 2 - 1 + s;
-            if (w < 0 || w >= W) continue;
-            const float v = x[(((long long)b * H + h) * W + w) * C + c];
-            if (arg < 0 || v > m || v != v) { m = v; arg = h * W + w; }
-        }
-    }
-    *best = m;
-    return arg;
-}
-
-__global__ void __launch_bounds__(256) maxpool_fwd_kernel(const float* __restrict__ x, int n, int H, int W, int C, int Ho, int Wo,
-                                                          float* __restrict__ y) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)n * Ho * Wo * C) return;
-    const int c = (int)(idx % C);
-    const long long p = idx / C;
-    const int wo = (int)(p % Wo), ho = (int)((p / Wo) % Ho), b = (int)(p / ((long long)Wo * Ho));
-    float m;
-    maxpool_arg(x, b, ho, wo, c, H, W, C, &m);
-    y[idx] = m;
-}
-
-// gx[b][h][w][c] = sum, over the windows (ho, wo ascending) whose argmax is (h, w), of gy[b][ho][wo][c]
-__global__ void __launch_bounds__(256) maxpool_bwd_kernel(const float* __restrict__ x, const float* __restrict__ gy, int n, int H, int W,
-                                                          int C, int Ho, int Wo, float* __restrict__ gx) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)n * H * W * C) return;
-    const int c = (int)(idx % C);
-    const long long p = idx / C;
-    const int w = (int)(p % W), h = (int)((p / W) % H), b = (int)(p / ((long long)W * H));
-    float s = 0.f;
-    const int me = h * W + w;
-    for (int ho = max(0, h / 2 - 1); ho <= min(Ho - 1, (h + 1) / 2); ++ho) {
-        if (h < ho * 2 - 1 || h > ho * 2 + 1) continue;
-        for (int wo = max(0, w / 2 - 1); wo <= min(Wo - 1, (w + 1) / 2); ++wo) {
-            if (w < wo * 2 - 1 || w > wo * 2 + 1) continue;
-            float m;
-            if (maxpool_arg(x, b, ho, wo, c, H, W, C, &m) == me) s += gy[(((long long)b * Ho + ho) * Wo + wo) * C + c];
-        }
-    }
-    gx[idx] = s;
-}
-
-// avg-pool 7 x 7 over a (n, 7, 7, C) map -> (n, C): the 49 pixels summed in row-major order, / 49
-__global__ void __launch_bounds__(256) avgpool_fwd_kernel(const float* __restrict__ x, int n, int C, float* __restrict__ y) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)n * C) return;
-    const int c = (int)(idx % C), b = (int)(idx / C);
-    float s = 0.f;
-    for (int p = 0; p < 49; ++p) s += x[((long long)b * 49 + p) * C + c];
-    y[idx] = s / 49.f;
-}
-
-__global__ void __launch_bounds__(256) avgpool_bwd_kernel(const float* __restrict__ gy, int n, int C, float* __restrict__ gx) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)n * 49 * C) return;
-    const int c = (int)(idx % C), b = (int)(idx / (49LL * C));
-    gx[idx] = gy[(long long)b * C + c] / 49.f;
-}
-
-// NCHW <-> NHWC of the (n, 3, 224, 224) crops
+// NCHW -> NHWC of the (n, 3, 224, 224) crops
 __global__ void __launch_bounds__(256) nchw_to_nhwc_kernel(const float* __restrict__ x, int n, int C, int HW, float* __restrict__ y) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long long)n * C * HW) return;
@@ -376,15 +216,6 @@ __global__ void __launch_bounds__(256) nchw_to_nhwc_kernel(const float* __restri
     const long long p = idx / C;
     const int hw = (int)(p % HW), b = (int)(p / HW);
     y[idx] = x[((long long)b * C + c) * HW + hw];
-}
-
-__global__ void __launch_bounds__(256) nhwc_to_nchw_kernel(const float* __restrict__ x, int n, int C, int HW, float* __restrict__ y) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)n * C * HW) return;
-    const int hw = (int)(idx % HW);
-    const long long p = idx / HW;
-    const int c = (int)(p % C), b = (int)(p / C);
-    y[idx] = x[((long long)b * HW + hw) * C + c];
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
@@ -431,41 +262,13 @@ hipError_t conv_wgrad(const Geom& g, const float* x, const float* gy, float* par
     if (g.C % 64 == 0 && al16(x)) hipLaunchKernelGGL((apg_conv_kernel<CV_WGRAD, true>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((apg_conv_kernel<CV_WGRAD, false>), grid, dim3(256), 0, st, a);
     const long long tot = (long long)g.K * g.C * g.R * g.S;
-    hipLaunchKernelGGL(conv_wgrad_combine_kernel, dim3(nblk(tot)), dim3(256), 0, st, part, nch, g.K, g.C, g.R, g.S, gw);
-    return hipGetLastError();
-}
-
-// forward BN over (M, C): train -> batch statistics (+ running update when rm / rv given), eval -> running statistics
-hipError_t bn_fwd(const float* x, int M, int C, const float* gamma, const float* beta, float* rm, float* rv, int train, float momentum,
-                  float eps, const float* res, int relu, float* y, float* mean, float* invstd, float* part, hipStream_t st) {
-    if (train) {
-        const int tr = bn_tile_rows(M), nt = bn_tiles(M);
-        hipLaunchKernelGGL(bn_stats_part_kernel, dim3((C + 63) / 64, nt), dim3(256), 0, st, x, M, C, tr, part);
-        hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C), dim3(64), 0, st, part, nt, C, momentum, eps, rm, rv, mean, invstd);
-    } else {
-        hipLaunchKernelGGL(bn_eval_stats_kernel, dim3((C + 255) / 256), dim3(256), 0, st, rm, rv, C, eps, mean, invstd);
-    }
-    const long long tot = (long long)M * C;
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(nblk(tot)), dim3(256), 0, st, x, tot, C, mean, invstd, gamma, beta, res, relu, y);
-    return hipGetLastError();
-}
-
-hipError_t bn_bwd(const float* gy, const float* y, const float* x, int M, int C, const float* gamma, const float* mean,
-                  const float* invstd, int train, float* gx, float* g_res, float* g_gamma, float* g_beta, float* part, hipStream_t st) {
-    const int tr = bn_tile_rows(M), nt = bn_tiles(M);
-    float* sums = part + (size_t)nt * 2 * C;
-    hipLaunchKernelGGL(bn_bwd_part_kernel, dim3((C + 63) / 64, nt), dim3(256), 0, st, gy, y, x, M, C, tr, mean, invstd, part);
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C), dim3(64), 0, st, part, nt, C, sums, g_gamma, g_beta);
-    const long long tot = (long long)M * C;
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(nblk(tot)), dim3(256), 0, st, gy, y, x, tot, C, 1.f / (float)M, train, mean, invstd,
-                       gamma, sums, gx, g_res);
+    hipLaunchKernelGGL(wgrad_combine_kernel, dim3(nblk(tot)), dim3(256), 0, st, part, nch, g.K, g.C, g.C, g.R, g.S, gw);
     return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the trunk walks
 // The fp32 backend of trunk_walk.inc: NHWC fp32 activations, the live OIHW parameters as the weights (nothing packed, no padding).
-struct F32Ops {
-    using act = float;
+struct F32Ops : ElemOps<F32Store> {
     using L = Layer<float>;
     static constexpr const char *fwd_name = "apg_trunk_fwd", *bwd_name = "apg_trunk_bwd";
     static constexpr bool ws_aligned = false, packed = false;
@@ -478,29 +281,13 @@ struct F32Ops {
     static hipError_t conv_wgrad(const L& l, const float* gz, float* part, float* gw, hipStream_t st) {
         return ::conv_wgrad(l.g, l.in, gz, part, gw, st);
     }
-    static constexpr auto bn_fwd = &::bn_fwd;
-    static constexpr auto bn_bwd = &::bn_bwd;
-    static void maxpool_fwd(const float* x, int n, int H, int C, float* y, hipStream_t st) {
-        const int Ho = (H - 1) / 2 + 1;
-        hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(nblk((long long)n * Ho * Ho * C)), dim3(256), 0, st, x, n, H, H, C, Ho, Ho, y);
-    }
-    static void maxpool_bwd(const float* x, const float* gy, int n, int H, int C, float* gx, hipStream_t st) {
-        const int Ho = (H - 1) / 2 + 1;
-        hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(nblk((long long)n * H * H * C)), dim3(256), 0, st, x, gy, n, H, H, C, Ho, Ho, gx);
-    }
-    static void avgpool_fwd(const float* x, int n, int C, float* y, hipStream_t st) {
-        hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(nblk((long long)n * C)), dim3(256), 0, st, x, n, C, y);
-    }
-    static void avgpool_bwd(const float* gy, int n, int C, float* gx, hipStream_t st) {
-        hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(nblk((long long)n * 49 * C)), dim3(256), 0, st, gy, n, C, gx);
-    }
     static void crops_in(const float* x, int n, float* ximg, hipStream_t st) {
         hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(nblk((long long)n * 3 * IMG * IMG)), dim3(256), 0, st, x, n, 3, IMG * IMG, ximg);
     }
     static hipError_t crop_grad(const L& stem, const float* w, const float* g1, float* g2, int n, float* g_x, hipStream_t st) {
         hipError_t e = ::conv_dgrad(stem.g, g1, w, nullptr, g2, st);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(nblk((long long)n * 3 * IMG * IMG)), dim3(256), 0, st, g2, n, 3, IMG * IMG, g_x);
+        hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(nblk((long long)n * 3 * IMG * IMG)), dim3(256), 0, st, g2, n, 3, 3, IMG * IMG, g_x);
         return hipGetLastError();
     }
     // the downsample's data gradient goes to gnext and conv1's data gradient adds it in place
@@ -558,8 +345,8 @@ int apg_bn_fwd(const float* x, int M, int C, const float* gamma, const float* be
         return apg_fail(APG_EINVAL, "apg_bn_fwd: bad argument");
     if (train && (!workspace || workspace_bytes < apg_bn_workspace_bytes(M, C)))
         return apg_fail(APG_ENOMEM, "apg_bn_fwd: workspace too small");
-    APG_TRY(bn_fwd(x, M, C, gamma, beta, running_mean, running_var, train, momentum, eps, res, relu, y, save_mean, save_invstd,
-                   (float*)workspace, (hipStream_t)stream));
+    APG_TRY(bn_fwd<F32Store>(x, M, C, gamma, beta, running_mean, running_var, train, momentum, eps, res, relu, y, save_mean, save_invstd,
+                             (float*)workspace, (hipStream_t)stream));
     return APG_OK;
 }
 
@@ -569,39 +356,35 @@ int apg_bn_bwd(const float* gy, const float* y, const float* x, int M, int C, co
     if (!gy || !x || M <= 0 || C <= 0 || !gamma || !save_mean || !save_invstd || !gx)
         return apg_fail(APG_EINVAL, "apg_bn_bwd: bad argument");
     if (!workspace || workspace_bytes < apg_bn_workspace_bytes(M, C)) return apg_fail(APG_ENOMEM, "apg_bn_bwd: workspace too small");
-    APG_TRY(bn_bwd(gy, y, x, M, C, gamma, save_mean, save_invstd, train, gx, g_res, g_gamma, g_beta, (float*)workspace,
-                   (hipStream_t)stream));
+    APG_TRY(bn_bwd<F32Store>(gy, y, x, M, C, gamma, save_mean, save_invstd, train, gx, g_res, g_gamma, g_beta, (float*)workspace,
+                             (hipStream_t)stream));
     return APG_OK;
 }
 
 int apg_maxpool_fwd(const float* x, int n, int H, int W, int C, float* y, void* stream) {
     if (!x || !y || n <= 0 || H <= 0 || W <= 0 || C <= 0) return apg_fail(APG_EINVAL, "apg_maxpool_fwd: bad argument");
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(nblk((long long)n * Ho * Wo * C)), dim3(256), 0, (hipStream_t)stream, x, n, H, W, C,
-                       Ho, Wo, y);
+    F32Ops::maxpool_fwd(x, n, H, W, C, y, (hipStream_t)stream);
     APG_TRY(hipGetLastError());
     return APG_OK;
 }
 
 int apg_maxpool_bwd(const float* x, int n, int H, int W, int C, const float* gy, float* gx, void* stream) {
     if (!x || !gy || !gx || n <= 0 || H <= 0 || W <= 0 || C <= 0) return apg_fail(APG_EINVAL, "apg_maxpool_bwd: bad argument");
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(nblk((long long)n * H * W * C)), dim3(256), 0, (hipStream_t)stream, x, gy, n, H, W, C,
-                       Ho, Wo, gx);
+    F32Ops::maxpool_bwd(x, gy, n, H, W, C, gx, (hipStream_t)stream);
     APG_TRY(hipGetLastError());
     return APG_OK;
 }
 
 int apg_avgpool_fwd(const float* x, int n, int C, float* y, void* stream) {
     if (!x || !y || n <= 0 || C <= 0) return apg_fail(APG_EINVAL, "apg_avgpool_fwd: bad argument");
-    hipLaunchKernelGGL(avgpool_fwd_kernel, dim3(nblk((long long)n * C)), dim3(256), 0, (hipStream_t)stream, x, n, C, y);
+    F32Ops::avgpool_fwd(x, n, C, y, (hipStream_t)stream);
     APG_TRY(hipGetLastError());
     return APG_OK;
 }
 
 int apg_avgpool_bwd(const float* gy, int n, int C, float* gx, void* stream) {
     if (!gy || !gx || n <= 0 || C <= 0) return apg_fail(APG_EINVAL, "apg_avgpool_bwd: bad argument");
-    hipLaunchKernelGGL(avgpool_bwd_kernel, dim3(nblk((long long)n * 49 * C)), dim3(256), 0, (hipStream_t)stream, gy, n, C, gx);
+    F32Ops::avgpool_bwd(gy, n, C, gx, (hipStream_t)stream);
     APG_TRY(hipGetLastError());
     return APG_OK;
 }

@@ -13,9 +13,13 @@
 //                   CV_WGRAD  M = C_out,   N = (r, s, c_in), K = n Ho Wo in fixed split-K chunks: neither operand is k-contiguous
 //                             in NHWC, so both are transposed on the way into LDS: a thread loads 8 channels of two consecutive
 //                             pixels (two 16-byte loads) and writes 8 dwords, each one channel's pixel pair
-//   BatchNorm:    the kernels of trunk_grad.hip on bf16 storage: same tiles (bn_tile_rows / bn_tiles), same per-channel order and
-//                 trees, fp32 math; the element-wise passes move 8 bf16 (16 bytes) per thread
-//   pools, layout: bf16 storage, 8 channels per thread; the crops are cast into an 8-channel NHWC image (channels 3 .. 7 zero)
+//   BatchNorm, pools, layout: trunk_elem.inc, the one source this file shares with trunk_grad.hip, instantiated on Bf16Store (bf16
+//                 storage, 8 channels = 16 bytes per thread in the element-wise passes, fp32 math, RNE at the store):
+//                 bn_stats_part_kernel and bn_bwd_part_kernel (one channel per lane, 2-byte loads: the fp32 path's per-channel
+//                 order), bn_stats_final_kernel, bn_eval_stats_kernel, bn_bwd_final_kernel, bn_apply_kernel, bn_bwd_apply_kernel,
+//                 maxpool_fwd_kernel / maxpool_bwd_kernel, avgpool_fwd_kernel / avgpool_bwd_kernel, wgrad_combine_kernel, and
+//                 nhwc_to_nchw_kernel at a pitch of 8 for the crop gradient.  The crops are cast into an 8-channel NHWC image
+//                 (channels 3 .. 7 zero) by this file's nchw_to_nhwc8_kernel
 // No floating-point atomics: every reduction runs in a fixed order, so results are bit-reproducible run to run.
 #include "ap_common.h"
 #include "grad_internal.h"
@@ -227,19 +231,6 @@ __global__ void __launch_bounds__(256) bconv_kernel(const BArgs a) {
             }
 }
 
-// gW[co][c][r][s] (c < C) = sum over the chunks, in chunk order, of part[chunk][co][(r S + s) Cp + c]
-__global__ void __launch_bounds__(256) bwgrad_combine_kernel(const float* __restrict__ part, int nch, int K, int C, int Cp, int R, int S,
-                                                             float* __restrict__ gw) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, per = (long long)C * R * S, perp = (long long)Cp * R * S;
-    if (idx >= (long long)K * per) return;
-    const int co = (int)(idx / per), rem = (int)(idx - co * per);
-    const int c = rem / (R * S), rs = rem - c * R * S;
-    const long long src = (long long)co * perp + (long long)rs * Cp + c, stride = (long long)K * perp;
-    float s = 0.f;
-    for (int ch = 0; ch < nch; ++ch) s += part[ch * stride + src];
-    gw[idx] = s;
-}
-
 // fp32 OIHW master weights -> bf16 (RNE), channels padded with zeros to Cp: wf[co][r][s][c] and / or wd[c][r][s][co]
 __global__ void __launch_bounds__(256) pack_weights_kernel(const float* __restrict__ w, int K, int C, int Cp, int R, int S,
                                                            bf16_t* __restrict__ wf, bf16_t* __restrict__ wd) {
@@ -271,194 +262,17 @@ __device__ __forceinline__ void st8(bf16_t* p, const F8& f) {
     *(u32x4*)p = u;
 }
 
-// ---------------------------------------------------------------------------------------------------------------- BatchNorm
-// The tiling and the per-channel order of trunk_grad.hip: rows in tiles of `tr` (tr % 4 == 0, at most 256 tiles), a workgroup takes
-// 64 channels x one tile, its 4 waves a quarter of the tile each.
-#include "bn_common.inc"
-
-__global__ void __launch_bounds__(256) bbn_stats_part_kernel(const bf16_t* __restrict__ x, int M, int C, int tr, float* __restrict__ part) {
-    __shared__ float sh[4][64];
-    __shared__ float smean[64];
-    const int t = threadIdx.x, cl = t & 63, g = t >> 6, c = blockIdx.x * 64 + cl, tile = blockIdx.y;
-    const int t0 = tile * tr, tcnt = min(tr, M - t0), r0 = t0 + g * (tr / 4), r1 = min(r0 + tr / 4, M);
-    float s = 0.f;
-    if (c < C)
-        for (int r = r0; r < r1; ++r) s += bf16_to_f32(x[(long long)r * C + c]);
-    sh[g][cl] = s;
-    __syncthreads();
-    if (g == 0) smean[cl] = (((sh[0][cl] + sh[1][cl]) + sh[2][cl]) + sh[3][cl]) / (float)tcnt;
-    __syncthreads();
-    const float mean = smean[cl];
-    float m2 = 0.f;
-    if (c < C)
-        for (int r = r0; r < r1; ++r) {
-            const float d = bf16_to_f32(x[(long long)r * C + c]) - mean;
-            m2 += d * d;
-        }
-    sh[g][cl] = m2;
-    __syncthreads();
-    if (g == 0 && c < C) {
-        part[((long long)tile * 3 + 0) * C + c] = (float)tcnt;
-        part[((long long)tile * 3 + 1) * C + c] = mean;
-        part[((long long)tile * 3 + 2) * C + c] = ((sh[0][cl] + sh[1][cl]) + sh[2][cl]) + sh[3][cl];
-    }
-}
-
-// y = (x - mean) invstd gamma + beta (+ res) (ReLU) on 8 channels per thread (C % 8 == 0); y may alias x or res
-__global__ void __launch_bounds__(256) bbn_apply_kernel(const bf16_t* x, long long groups, int C, const float* __restrict__ mean,
-                                                        const float* __restrict__ invstd, const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, const bf16_t* res, int relu, bf16_t* y) {
-    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (gi >= groups) return;
-    const long long idx = gi * 8;
-    const int c = (int)(idx % C);
-    F8 v = ld8(x + idx), r;
-    if (res) r = ld8(res + idx);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        float f = (v.v[j] - mean[c + j]) * invstd[c + j] * gamma[c + j] + beta[c + j];
-        if (res) f += r.v[j];
-        if (relu) f = fmaxf(f, 0.f);
-        v.v[j] = f;
-    }
-    st8(y + idx, v);
-}
-
-__global__ void __launch_bounds__(256) bbn_bwd_part_kernel(const bf16_t* __restrict__ gy, const bf16_t* __restrict__ y,
-                                                           const bf16_t* __restrict__ x, int M, int C, int tr, const float* __restrict__ mean,
-                                                           const float* __restrict__ invstd, float* __restrict__ part) {
-    __shared__ float s1[4][64], s2[4][64];
-    const int t = threadIdx.x, cl = t & 63, g = t >> 6, c = blockIdx.x * 64 + cl, tile = blockIdx.y;
-    const int r0 = tile * tr + g * (tr / 4), r1 = min(r0 + tr / 4, M);
-    float a = 0.f, b = 0.f;
-    if (c < C) {
-        const float mu = mean[c], is = invstd[c];
-        for (int r = r0; r < r1; ++r) {
-            const long long o = (long long)r * C + c;
-            float gv = bf16_to_f32(gy[o]);
-            if (y && !(bf16_to_f32(y[o]) > 0.f)) gv = 0.f;
-            a += gv;
-            b += gv * ((bf16_to_f32(x[o]) - mu) * is);
-        }
-    }
-    s1[g][cl] = a;
-    s2[g][cl] = b;
-    __syncthreads();
-    if (g == 0 && c < C) {
-        part[((long long)tile * 2 + 0) * C + c] = ((s1[0][cl] + s1[1][cl]) + s1[2][cl]) + s1[3][cl];
-        part[((long long)tile * 2 + 1) * C + c] = ((s2[0][cl] + s2[1][cl]) + s2[2][cl]) + s2[3][cl];
-    }
-}
-
-// gx = gamma invstd (g - sum g / M - xhat sum(g xhat) / M) (train) or gamma invstd g (eval); g_res = g.  gx may alias gy.
-__global__ void __launch_bounds__(256) bbn_bwd_apply_kernel(const bf16_t* gy, const bf16_t* __restrict__ y, const bf16_t* __restrict__ x,
-                                                            long long groups, int C, float inv_m, int train, const float* __restrict__ mean,
-                                                            const float* __restrict__ invstd, const float* __restrict__ gamma,
-                                                            const float* __restrict__ sums, bf16_t* gx, bf16_t* g_res) {
-    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (gi >= groups) return;
-    const long long idx = gi * 8;
-    const int c = (int)(idx % C);
-    F8 g = ld8(gy + idx), xv = ld8(x + idx), o;
-    if (y) {
-        const F8 yv = ld8(y + idx);
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (!(yv.v[j] > 0.f)) g.v[j] = 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float k = gamma[c + j] * invstd[c + j];
-        if (train) {
-            const float xhat = (xv.v[j] - mean[c + j]) * invstd[c + j];
-            o.v[j] = k * ((g.v[j] - sums[c + j] * inv_m) - xhat * (sums[C + c + j] * inv_m));
-        } else {
-            o.v[j] = k * g.v[j];
-        }
-    }
-    if (g_res) st8(g_res + idx, g);                              // exact: g is gy or 0
-    st8(gx + idx, o);
-}
-
-// ---------------------------------------------------------------------------------------------------------------- pools, layout
-// max-pool 3 x 3 / s2 / p1 on 8 channels per thread: padding is -inf; the first maximum in row-major window order is the argmax
-__device__ __forceinline__ void maxpool_arg8(const bf16_t* __restrict__ x, int b, int ho, int wo, int c, int H, int W, int C, float* best,
-                                             int* arg) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { best[j] = -INFINITY; arg[j] = -1; }
-    for (int r = 0; r < 3; ++r) {
-        const int h = ho * 2 - 1 + r;
-        if (h < 0 || h >= H) continue;
-        for (int s = 0; s < 3; ++s) {
-            const int w = wo * 2 - 1 + s;
-            if (w < 0 || w >= W) continue;
-            const F8 v = ld8(x + (((long long)b * H + h) * W + w) * C + c);
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (arg[j] < 0 || v.v[j] > best[j] || v.v[j] != v.v[j]) { best[j] = v.v[j]; arg[j] = h * W + w; }
-        }
-    }
-}
-
-__global__ void __launch_bounds__(256) bmaxpool_fwd_kernel(const bf16_t* __restrict__ x, int n, int H, int W, int C, int Ho, int Wo,
-                                                           bf16_t* __restrict__ y) {
-    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x, idx = gi * 8;
-    if (idx >= (long long)n * Ho * Wo * C) return;
-    const int c = (int)(idx % C);
-    const long long p = idx / C;
-    const int wo = (int)(p % Wo), ho = (int)((p / Wo) % Ho), b = (int)(p / ((long long)Wo * Ho));
-    F8 m;
-    int arg[8];
-    maxpool_arg8(x, b, ho, wo, c, H, W, C, m.v, arg);
-    st8(y + idx, m);                                             // a selection: exact
-}
-
-__global__ void __launch_bounds__(256) bmaxpool_bwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ gy, int n, int H, int W,
-                                                           int C, int Ho, int Wo, bf16_t* __restrict__ gx) {
-    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x, idx = gi * 8;
-    if (idx >= (long long)n * H * W * C) return;
-    const int c = (int)(idx % C);
-    const long long p = idx / C;
-    const int w = (int)(p % W), h = (int)((p / W) % H), b = (int)(p / ((long long)W * H));
-    F8 s;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s.v[j] = 0.f;
-    const int me = h * W + w;
-    for (int ho = max(0, h / 2 - 1); ho <= min(Ho - 1, (h + 1) / 2); ++ho) {
-        if (h < ho * 2 - 1 || h > ho * 2 + 1) continue;
-        for (int wo = max(0, w / 2 - 1); wo <= min(Wo - 1, (w + 1) / 2); ++wo) {
-            if (w < wo * 2 - 1 || w > wo * 2 + 1) continue;
-            float m[8];
-            int arg[8];
-            maxpool_arg8(x, b, ho, wo, c, H, W, C, m, arg);
-            const F8 g = ld8(gy + (((long long)b * Ho + ho) * Wo + wo) * C + c);
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (arg[j] == me) s.v[j] += g.v[j];
-        }
-    }
-    st8(gx + idx, s);
-}
-
-// avg-pool 7 x 7 over a bf16 (n, 7, 7, C) map -> fp32 (n, C): the 49 pixels summed in row-major order in fp32, / 49
-__global__ void __launch_bounds__(256) bavgpool_fwd_kernel(const bf16_t* __restrict__ x, int n, int C, float* __restrict__ y) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)n * C) return;
-    const int c = (int)(idx % C), b = (int)(idx / C);
-    float s = 0.f;
-    for (int p = 0; p < 49; ++p) s += bf16_to_f32(x[((long long)b * 49 + p) * C + c]);
-    y[idx] = s / 49.f;
-}
-
-__global__ void __launch_bounds__(256) bavgpool_bwd_kernel(const float* __restrict__ gy, int n, int C, bf16_t* __restrict__ gx) {
-    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x, idx = gi * 8;
-    if (idx >= (long long)n * 49 * C) return;
-    const int c = (int)(idx % C), b = (int)(idx / (49LL * C));
-    F8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o.v[j] = gy[(long long)b * C + c + j] / 49.f;
-    st8(gx + idx, o);
-}
+// ---------------------------------------------------------------------------------------------------------------- BatchNorm, pools
+// bf16 storage for the kernels of trunk_elem.inc: 8 channels = one 16-byte access per thread, RNE at the store
+struct Bf16Store {
+    using T = bf16_t;
+    static constexpr int W = 8;
+    using V = F8;
+    static __device__ __forceinline__ float rd(bf16_t x) { return bf16_to_f32(x); }
+    static __device__ __forceinline__ F8 ld(const bf16_t* p) { return ld8(p); }
+    static __device__ __forceinline__ void st(bf16_t* p, const F8& f) { st8(p, f); }
+};
+#include "trunk_elem.inc"
 
 // fp32 NCHW (n, C, HW) -> bf16 NHWC with 8 channels per pixel (C <= 8; channels C .. 7 zero), RNE
 __global__ void __launch_bounds__(256) nchw_to_nhwc8_kernel(const float* __restrict__ x, int n, int C, int HW, bf16_t* __restrict__ y) {
@@ -469,16 +283,6 @@ __global__ void __launch_bounds__(256) nchw_to_nhwc8_kernel(const float* __restr
 #pragma unroll
     for (int j = 0; j < 8; ++j) o.v[j] = j < C ? x[((long long)b * C + j) * HW + hw] : 0.f;
     st8(y + idx * 8, o);
-}
-
-// fp32 NHWC with 8 channels per pixel -> fp32 NCHW (n, C, HW), the first C channels
-__global__ void __launch_bounds__(256) nhwc8_to_nchw_kernel(const float* __restrict__ x, int n, int C, int HW, float* __restrict__ y) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)n * C * HW) return;
-    const int hw = (int)(idx % HW);
-    const long long p = idx / HW;
-    const int c = (int)(p % C), b = (int)(p / C);
-    y[idx] = x[((long long)b * HW + hw) * 8 + c];
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
@@ -537,7 +341,7 @@ hipError_t conv_wgrad(const Geom& g, const bf16_t* x, const bf16_t* gy, float* p
     wgrad_split(g, &nch, &a.kchunk);
     launch_conv<CV_WGRAD>(a, nch, wgrad_big(g), st);
     const long long tot = (long long)g.K * c_real * g.R * g.S;
-    hipLaunchKernelGGL(bwgrad_combine_kernel, dim3(nblk(tot)), dim3(256), 0, st, part, nch, g.K, c_real, g.C, g.R, g.S, gw);
+    hipLaunchKernelGGL(wgrad_combine_kernel, dim3(nblk(tot)), dim3(256), 0, st, part, nch, g.K, c_real, g.C, g.R, g.S, gw);
     return hipGetLastError();
 }
 
@@ -545,38 +349,11 @@ void pack_weights(const float* w, int K, int C, int Cp, int R, int S, bf16_t* wf
     hipLaunchKernelGGL(pack_weights_kernel, dim3(nblk((long long)K * R * S * Cp)), dim3(256), 0, st, w, K, C, Cp, R, S, wf, wd);
 }
 
-hipError_t bn_fwd(const bf16_t* x, int M, int C, const float* gamma, const float* beta, float* rm, float* rv, int train, float momentum,
-                  float eps, const bf16_t* res, int relu, bf16_t* y, float* mean, float* invstd, float* part, hipStream_t st) {
-    if (train) {
-        const int tr = bn_tile_rows(M), nt = bn_tiles(M);
-        hipLaunchKernelGGL(bbn_stats_part_kernel, dim3((C + 63) / 64, nt), dim3(256), 0, st, x, M, C, tr, part);
-        hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C), dim3(64), 0, st, part, nt, C, momentum, eps, rm, rv, mean, invstd);
-    } else {
-        hipLaunchKernelGGL(bn_eval_stats_kernel, dim3((C + 255) / 256), dim3(256), 0, st, rm, rv, C, eps, mean, invstd);
-    }
-    const long long groups = (long long)M * C / 8;
-    hipLaunchKernelGGL(bbn_apply_kernel, dim3(nblk(groups)), dim3(256), 0, st, x, groups, C, mean, invstd, gamma, beta, res, relu, y);
-    return hipGetLastError();
-}
-
-hipError_t bn_bwd(const bf16_t* gy, const bf16_t* y, const bf16_t* x, int M, int C, const float* gamma, const float* mean,
-                  const float* invstd, int train, bf16_t* gx, bf16_t* g_res, float* g_gamma, float* g_beta, float* part, hipStream_t st) {
-    const int tr = bn_tile_rows(M), nt = bn_tiles(M);
-    float* sums = part + (size_t)nt * 2 * C;
-    hipLaunchKernelGGL(bbn_bwd_part_kernel, dim3((C + 63) / 64, nt), dim3(256), 0, st, gy, y, x, M, C, tr, mean, invstd, part);
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C), dim3(64), 0, st, part, nt, C, sums, g_gamma, g_beta);
-    const long long groups = (long long)M * C / 8;
-    hipLaunchKernelGGL(bbn_bwd_apply_kernel, dim3(nblk(groups)), dim3(256), 0, st, gy, y, x, groups, C, 1.f / (float)M, train, mean,
-                       invstd, gamma, sums, gx, g_res);
-    return hipGetLastError();
-}
-
 // ---------------------------------------------------------------------------------------------------------------- the trunk walks
 // The bf16 backend of trunk_walk.inc: NHWC bf16 activations and activation gradients on channel counts padded to 8, a bf16 copy of
 // the fp32 master weights packed into the workspace in front of every forward convolution (the fp32 parameter `w` goes unused
 // after that), element-wise kernels on 8 channels per thread.
-struct Bf16Ops {
-    using act = bf16_t;
+struct Bf16Ops : ElemOps<Bf16Store> {
     using L = Layer<bf16_t>;
     static constexpr const char *fwd_name = "apg_trunk_fwd_p", *bwd_name = "apg_trunk_bwd_p";
     static constexpr bool ws_aligned = true, packed = true;
@@ -589,22 +366,6 @@ struct Bf16Ops {
     static hipError_t conv_wgrad(const L& l, const bf16_t* gz, float* part, float* gw, hipStream_t st) {
         return ::conv_wgrad(l.g, l.in, gz, part, gw, l.c_real, st);
     }
-    static constexpr auto bn_fwd = &::bn_fwd;
-    static constexpr auto bn_bwd = &::bn_bwd;
-    static void maxpool_fwd(const bf16_t* x, int n, int H, int C, bf16_t* y, hipStream_t st) {
-        const int Ho = (H - 1) / 2 + 1;
-        hipLaunchKernelGGL(bmaxpool_fwd_kernel, dim3(nblk((long long)n * Ho * Ho * C / 8)), dim3(256), 0, st, x, n, H, H, C, Ho, Ho, y);
-    }
-    static void maxpool_bwd(const bf16_t* x, const bf16_t* gy, int n, int H, int C, bf16_t* gx, hipStream_t st) {
-        const int Ho = (H - 1) / 2 + 1;
-        hipLaunchKernelGGL(bmaxpool_bwd_kernel, dim3(nblk((long long)n * H * H * C / 8)), dim3(256), 0, st, x, gy, n, H, H, C, Ho, Ho, gx);
-    }
-    static void avgpool_fwd(const bf16_t* x, int n, int C, float* y, hipStream_t st) {
-        hipLaunchKernelGGL(bavgpool_fwd_kernel, dim3(nblk((long long)n * C)), dim3(256), 0, st, x, n, C, y);
-    }
-    static void avgpool_bwd(const float* gy, int n, int C, bf16_t* gx, hipStream_t st) {
-        hipLaunchKernelGGL(bavgpool_bwd_kernel, dim3(nblk((long long)n * 49 * C / 8)), dim3(256), 0, st, gy, n, C, gx);
-    }
     static void crops_in(const float* x, int n, bf16_t* ximg, hipStream_t st) {
         hipLaunchKernelGGL(nchw_to_nhwc8_kernel, dim3(nblk((long long)n * IMG * IMG)), dim3(256), 0, st, x, n, 3, IMG * IMG, ximg);
     }
@@ -612,7 +373,7 @@ struct Bf16Ops {
     static hipError_t crop_grad(const L& stem, const float*, const bf16_t* g1, bf16_t* g2, int n, float* g_x, hipStream_t st) {
         hipError_t e = ::conv_dgrad(stem.g, g1, stem.wd, nullptr, 0, g2, 1, st);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(nhwc8_to_nchw_kernel, dim3(nblk((long long)n * 3 * IMG * IMG)), dim3(256), 0, st, (const float*)g2, n, 3,
+        hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(nblk((long long)n * 3 * IMG * IMG)), dim3(256), 0, st, (const float*)g2, n, 3, 8,
                            IMG * IMG, g_x);
         return hipGetLastError();
     }
@@ -687,8 +448,8 @@ int apg_bn_fwd_bf16(const void* x, int M, int C, const float* gamma, const float
         return apg_fail(APG_EINVAL, "apg_bn_fwd_bf16: bad argument (C a multiple of 8, x / y / res 16-byte aligned)");
     if (train && (!workspace || workspace_bytes < apg_bn_bf16_workspace_bytes(M, C)))
         return apg_fail(APG_ENOMEM, "apg_bn_fwd_bf16: workspace too small");
-    APG_TRY(bn_fwd((const bf16_t*)x, M, C, gamma, beta, running_mean, running_var, train, momentum, eps, (const bf16_t*)res, relu,
-                   (bf16_t*)y, save_mean, save_invstd, (float*)workspace, (hipStream_t)stream));
+    APG_TRY(bn_fwd<Bf16Store>((const bf16_t*)x, M, C, gamma, beta, running_mean, running_var, train, momentum, eps, (const bf16_t*)res,
+                              relu, (bf16_t*)y, save_mean, save_invstd, (float*)workspace, (hipStream_t)stream));
     return APG_OK;
 }
 
@@ -700,8 +461,8 @@ int apg_bn_bwd_bf16(const void* gy, const void* y, const void* x, int M, int C, 
         return apg_fail(APG_EINVAL, "apg_bn_bwd_bf16: bad argument (C a multiple of 8, activation pointers 16-byte aligned)");
     if (!workspace || workspace_bytes < apg_bn_bf16_workspace_bytes(M, C))
         return apg_fail(APG_ENOMEM, "apg_bn_bwd_bf16: workspace too small");
-    APG_TRY(bn_bwd((const bf16_t*)gy, (const bf16_t*)y, (const bf16_t*)x, M, C, gamma, save_mean, save_invstd, train, (bf16_t*)gx,
-                   (bf16_t*)g_res, g_gamma, g_beta, (float*)workspace, (hipStream_t)stream));
+    APG_TRY(bn_bwd<Bf16Store>((const bf16_t*)gy, (const bf16_t*)y, (const bf16_t*)x, M, C, gamma, save_mean, save_invstd, train,
+                              (bf16_t*)gx, (bf16_t*)g_res, g_gamma, g_beta, (float*)workspace, (hipStream_t)stream));
     return APG_OK;
 }
 
@@ -709,9 +470,7 @@ int apg_maxpool_fwd_bf16(const void* x, int n, int H, int W, int C, void* y, voi
     if (!x || !y || n <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 != 0 || !al16(x) || !al16(y) ||
         (long long)n * H * W * C >= (1LL << 31))
         return apg_fail(APG_EINVAL, "apg_maxpool_fwd_bf16: bad argument (C a multiple of 8, pointers 16-byte aligned)");
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    hipLaunchKernelGGL(bmaxpool_fwd_kernel, dim3(nblk((long long)n * Ho * Wo * C / 8)), dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)x, n, H, W, C, Ho, Wo, (bf16_t*)y);
+    Bf16Ops::maxpool_fwd((const bf16_t*)x, n, H, W, C, (bf16_t*)y, (hipStream_t)stream);
     APG_TRY(hipGetLastError());
     return APG_OK;
 }
@@ -720,16 +479,14 @@ int apg_maxpool_bwd_bf16(const void* x, int n, int H, int W, int C, const void* 
     if (!x || !gy || !gx || n <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 != 0 || !al16(x) || !al16(gy) || !al16(gx) ||
         (long long)n * H * W * C >= (1LL << 31))
         return apg_fail(APG_EINVAL, "apg_maxpool_bwd_bf16: bad argument (C a multiple of 8, pointers 16-byte aligned)");
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    hipLaunchKernelGGL(bmaxpool_bwd_kernel, dim3(nblk((long long)n * H * W * C / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                       (const bf16_t*)gy, n, H, W, C, Ho, Wo, (bf16_t*)gx);
+    Bf16Ops::maxpool_bwd((const bf16_t*)x, (const bf16_t*)gy, n, H, W, C, (bf16_t*)gx, (hipStream_t)stream);
     APG_TRY(hipGetLastError());
     return APG_OK;
 }
 
 int apg_avgpool_fwd_bf16(const void* x, int n, int C, float* y, void* stream) {
     if (!x || !y || n <= 0 || C <= 0) return apg_fail(APG_EINVAL, "apg_avgpool_fwd_bf16: bad argument");
-    hipLaunchKernelGGL(bavgpool_fwd_kernel, dim3(nblk((long long)n * C)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, n, C, y);
+    Bf16Ops::avgpool_fwd((const bf16_t*)x, n, C, y, (hipStream_t)stream);
     APG_TRY(hipGetLastError());
     return APG_OK;
 }
@@ -737,8 +494,7 @@ int apg_avgpool_fwd_bf16(const void* x, int n, int C, float* y, void* stream) {
 int apg_avgpool_bwd_bf16(const float* gy, int n, int C, void* gx, void* stream) {
     if (!gy || !gx || n <= 0 || C <= 0 || C % 8 != 0 || !al16(gx))
         return apg_fail(APG_EINVAL, "apg_avgpool_bwd_bf16: bad argument (C a multiple of 8, gx 16-byte aligned)");
-    hipLaunchKernelGGL(bavgpool_bwd_kernel, dim3(nblk((long long)n * 49 * C / 8)), dim3(256), 0, (hipStream_t)stream, gy, n, C,
-                       (bf16_t*)gx);
+    Bf16Ops::avgpool_bwd(gy, n, C, (bf16_t*)gx, (hipStream_t)stream);
     APG_TRY(hipGetLastError());
     return APG_OK;
 }

@@ -1,13 +1,15 @@
 // The precision-agnostic host side of the trainable ResNet-50 trunk, shared by trunk_grad.hip (F32Ops) and trunk_grad_bf16.hip
 // (Bf16Ops): convolution geometry, the workspace plan of the fixed [3, 4, 6, 3] graph, and the forward and backward walks over it.
-// Included inside each file's unnamed namespace, after its kernels (and bn_common.inc) and in front of its launch helpers, which use
-// Geom; nothing here is exported.  A backend is a struct `Ops` of static functions over that file's launchers (no virtual calls):
-//   act                        activation / activation-gradient storage type
+// Included inside each file's unnamed namespace, after its kernels (and trunk_elem.inc) and in front of its launch helpers, which use
+// Geom; nothing here is exported.  A backend is a struct `Ops` of static functions over that file's launchers (no virtual calls);
+// what only depends on the file's storage trait S (trunk_elem.inc) it inherits from ElemOps<S>:
+//   act                        activation / activation-gradient storage type (ElemOps)
 //   fwd_name, bwd_name         the entry points' names, the prefix of every message
 //   ws_aligned                 refuse a workspace that is not 256-byte aligned
 //   packed, cpad(C)            a bf16 copy of the weights lives in the workspace (Layer::wf / wd); channels of x as stored
 //   pack                       fill wf / wd in front of a forward convolution
-//   conv_fwd, conv_dgrad, conv_wgrad, bn_fwd, bn_bwd, maxpool_fwd / _bwd, avgpool_fwd / _bwd
+//   conv_fwd, conv_dgrad, conv_wgrad
+//   bn_fwd, bn_bwd, maxpool_fwd / _bwd, avgpool_fwd / _bwd   (ElemOps)
 //   crops_in, crop_grad        NCHW fp32 crops -> Plan::ximg; stem data gradient (through g2) -> NCHW fp32 g_x
 //   ds_block_dgrad             the input gradient of a block with a downsample branch
 
@@ -55,6 +57,62 @@ size_t wgrad_floats(const Geom& g) {
 }
 
 size_t bn_part_floats(int M, int C) { return (size_t)bn_tiles(M) * 3 * C + 2 * (size_t)C; }
+
+// ---------------------------------------------------------------------------------------------------------------- BatchNorm, pools
+// forward BN over (M, C): train -> batch statistics (+ running update when rm / rv given), eval -> running statistics
+template <class S>
+hipError_t bn_fwd(const typename S::T* x, int M, int C, const float* gamma, const float* beta, float* rm, float* rv, int train,
+                  float momentum, float eps, const typename S::T* res, int relu, typename S::T* y, float* mean, float* invstd, float* part,
+                  hipStream_t st) {
+    if (train) {
+        const int tr = bn_tile_rows(M), nt = bn_tiles(M);
+        hipLaunchKernelGGL(bn_stats_part_kernel<S>, dim3((C + 63) / 64, nt), dim3(256), 0, st, x, M, C, tr, part);
+        hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C), dim3(64), 0, st, part, nt, C, momentum, eps, rm, rv, mean, invstd);
+    } else {
+        hipLaunchKernelGGL(bn_eval_stats_kernel, dim3((C + 255) / 256), dim3(256), 0, st, rm, rv, C, eps, mean, invstd);
+    }
+    const long long groups = (long long)M * C / S::W;
+    hipLaunchKernelGGL(bn_apply_kernel<S>, dim3(nblk(groups)), dim3(256), 0, st, x, groups, C, mean, invstd, gamma, beta, res, relu, y);
+    return hipGetLastError();
+}
+
+template <class S>
+hipError_t bn_bwd(const typename S::T* gy, const typename S::T* y, const typename S::T* x, int M, int C, const float* gamma,
+                  const float* mean, const float* invstd, int train, typename S::T* gx, typename S::T* g_res, float* g_gamma,
+                  float* g_beta, float* part, hipStream_t st) {
+    const int tr = bn_tile_rows(M), nt = bn_tiles(M);
+    float* sums = part + (size_t)nt * 2 * C;
+    hipLaunchKernelGGL(bn_bwd_part_kernel<S>, dim3((C + 63) / 64, nt), dim3(256), 0, st, gy, y, x, M, C, tr, mean, invstd, part);
+    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C), dim3(64), 0, st, part, nt, C, sums, g_gamma, g_beta);
+    const long long groups = (long long)M * C / S::W;
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<S>, dim3(nblk(groups)), dim3(256), 0, st, gy, y, x, groups, C, 1.f / (float)M, train, mean,
+                       invstd, gamma, sums, gx, g_res);
+    return hipGetLastError();
+}
+
+// the launchers a backend's Ops inherits: one thread per S::W channels in the element-wise kernels
+template <class S>
+struct ElemOps {
+    using act = typename S::T;
+    static constexpr auto bn_fwd = &::bn_fwd<S>;
+    static constexpr auto bn_bwd = &::bn_bwd<S>;
+    static void maxpool_fwd(const act* x, int n, int H, int W, int C, act* y, hipStream_t st) {
+        const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+        hipLaunchKernelGGL(maxpool_fwd_kernel<S>, dim3(nblk((long long)n * Ho * Wo * C / S::W)), dim3(256), 0, st, x, n, H, W, C, Ho, Wo,
+                           y);
+    }
+    static void maxpool_bwd(const act* x, const act* gy, int n, int H, int W, int C, act* gx, hipStream_t st) {
+        const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+        hipLaunchKernelGGL(maxpool_bwd_kernel<S>, dim3(nblk((long long)n * H * W * C / S::W)), dim3(256), 0, st, x, gy, n, H, W, C, Ho, Wo,
+                           gx);
+    }
+    static void avgpool_fwd(const act* x, int n, int C, float* y, hipStream_t st) {
+        hipLaunchKernelGGL(avgpool_fwd_kernel<S>, dim3(nblk((long long)n * C)), dim3(256), 0, st, x, n, C, y);
+    }
+    static void avgpool_bwd(const float* gy, int n, int C, act* gx, hipStream_t st) {
+        hipLaunchKernelGGL(avgpool_bwd_kernel<S>, dim3(nblk((long long)n * 49 * C / S::W)), dim3(256), 0, st, gy, n, C, gx);
+    }
+};
 
 // ---------------------------------------------------------------------------------------------------------------- the trunk plan
 constexpr int NLAYER = 53;
@@ -205,7 +263,7 @@ int trunk_fwd_walk(int n, const float* x, const void* const* params, int train, 
     };
     Ops::crops_in(x, n, P.ximg, st);
     APG_TRY(run(P.stem, nullptr, 1));
-    Ops::maxpool_fwd(P.stem.a, n, 112, 64, P.pool, st);
+    Ops::maxpool_fwd(P.stem.a, n, 112, 112, 64, P.pool, st);
     APG_TRY(hipGetLastError());
     for (int b = 0; b < 16; ++b) {
         const Block<T>& B = P.blk[b];
@@ -265,7 +323,7 @@ int trunk_bwd_walk(int n, const void* const* params, int train, const float* g_x
         std::swap(gcur, gnext);
     }
     // stem: max-pool, BN + ReLU, the 7 x 7 convolution
-    Ops::maxpool_bwd(P.stem.a, gcur, n, 112, 64, g1, st);
+    Ops::maxpool_bwd(P.stem.a, gcur, n, 112, 112, 64, g1, st);
     APG_TRY(hipGetLastError());
     APG_TRY(bnb(P.stem, g1, 1, g1, nullptr));
     APG_TRY(wg(P.stem, g1));

@@ -381,6 +381,40 @@ def test_batchnorm_cancellation_at_stem_size(dev):
     _report("cancellation M401408 ratio 100", ratios, " ".join("%s %.1e" % kv for kv in e.items()))
 
 
+@pytest.mark.parametrize("M,C", [(3, 8), (257, 64), (1027, 72)])
+def test_batchnorm_reductions_are_bitwise_the_fp32_path(dev, M, C):
+    """The fp32 and bf16 BatchNorm are one source (csrc/trunk_elem.inc) on two storage types: on bf16-representable x and gy both
+    read the same fp32 values and reduce them in the same per-channel order, so every fp32 output of the reductions is equal bit
+    for bit (y and gx differ in storage and are not compared).  Train mode, no residual, no ReLU.  (3, 8): one tile, only its
+    first quarter has rows, one partial channel group; (257, 64): two tiles, the second of one row; (1027, 72): five tiles with a
+    ragged last one, the second channel group cut at 8 of 64 lanes."""
+    from airpose_amd import _native as N
+    from airpose_amd import _native_grad as G
+    x, gam, bet, _, rm, rv, gy = _bn_inputs(M, C, seed=M + C)
+    L = G.lib()
+    s = N.stream_ptr(dev)
+    gd, bd = gam.to(dev), bet.to(dev)
+    nan32 = lambda *shape: torch.full(shape, float("nan"), device=dev)
+    outs = {}
+    for name, dt, nbytes, fwd, bwd in (("fp32", torch.float32, L.apg_bn_workspace_bytes, L.apg_bn_fwd, L.apg_bn_bwd),
+                                       ("bf16", BF, L.apg_bn_bf16_workspace_bytes, L.apg_bn_fwd_bf16, L.apg_bn_bwd_bf16)):
+        nb = nbytes(M, C)
+        ws = torch.empty(nb, device=dev, dtype=torch.uint8)
+        xd, gyd = x.to(dev, dt), gy.to(dev, dt)
+        yd, gxd = torch.empty_like(xd), torch.empty_like(xd)
+        rmd, rvd, mean, invstd, gg, gb = rm.to(dev), rv.to(dev), nan32(C), nan32(C), nan32(C), nan32(C)
+        G.check(fwd(_p(xd), M, C, N.dptr(gd), N.dptr(bd), N.dptr(rmd), N.dptr(rvd), 1, MOM, EPS, None, 0, _p(yd), N.dptr(mean),
+                    N.dptr(invstd), ws.data_ptr(), nb, s), "apg_bn_fwd " + name)
+        G.check(bwd(_p(gyd), None, _p(xd), M, C, N.dptr(gd), N.dptr(mean), N.dptr(invstd), 1, _p(gxd), None, N.dptr(gg), N.dptr(gb),
+                    ws.data_ptr(), nb, s), "apg_bn_bwd " + name)
+        outs[name] = {"save_mean": mean, "save_invstd": invstd, "running_mean": rmd, "running_var": rvd, "g_gamma": gg, "g_beta": gb}
+    torch.cuda.synchronize()
+    for k, a in outs["fp32"].items():
+        b = outs["bf16"][k]
+        assert torch.isfinite(a).all() and torch.isfinite(b).all(), (M, C, k, "non-finite output (an element never written?)")
+        assert torch.equal(a, b), (M, C, k, "fp32 and bf16 storage differ by up to %.3e" % float((a - b).abs().max()))
+
+
 # ------------------------------------------------------------------------------------------------ pools
 @pytest.mark.parametrize("n,H,C", [(2, 112, 64), (2, 1, 64), (2, 2, 64), (2, 3, 64), (1, 3, 16), (1, 5, 8)])
 def test_maxpool_matches_torch_bitwise(dev, n, H, C):
