@@ -1,5 +1,5 @@
-// Internal helpers shared by the sources of libairpose_grad.so (head_grad.hip, head_local_grad.hip, geom_grad.hip, trunk_grad.hip,
-// trunk_grad_bf16.hip, loss_grad.hip, loss_real_grad.hip, optim.hip).
+// Internal helpers shared by the sources of libairpose_grad.so (head_mlp.hip, head_grad.hip, head_local_grad.hip, geom_grad.hip,
+// trunk_grad.hip, trunk_grad_bf16.hip, loss_grad.hip, loss_real_grad.hip, optim.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -37,8 +37,9 @@ __host__ __device__ __forceinline__ bool apg_keep(uint64_t seed, int layer, int 
 }
 
 // ---------------------------------------------------------------------------------------------
-// apg_gemm_kernel (head_grad.hip) for the other sources of the library: C = A B with one 64 x 64 tile per workgroup, K reduced in
-// index order inside that workgroup (no split, no atomics), and one of the epilogues below.
+// head_mlp.hip: the library's fp32 product and what the two trainable heads (head_grad.hip, head_local_grad.hip) run on it.
+// apg_gemm_kernel: C = A B with one 64 x 64 tile per workgroup, K reduced in index order inside that workgroup (no split, no
+// atomics), and one of the epilogues below.
 enum {
     APG_EPI_STORE = 0,                   // C[m * ldc + n] = acc
     APG_EPI_HID_FWD = 1,                 // C = dropout(acc + bias[n]) of (seed, layer, row m, column n)
@@ -84,3 +85,34 @@ __attribute__((visibility("hidden"))) hipError_t apg_gemm_launch(const ApgGemmAr
 constexpr int APG_CS_ROWS = 32;
 __attribute__((visibility("hidden"))) hipError_t apg_colsum(const float* x, int rows, int cols, int ld, float* part, float* out,
                                                             hipStream_t st);
+
+// The heads' network on a packed fc1 input xc (R x K1, K1 = XF + the head's state columns): h1d = drop1(xc W1^T + b1),
+// h2d = drop2(h1d W2^T + b2), then ndec decoders packed as N columns (wdec: N x HID).
+constexpr int XF = 2048;                 // trunk features, the first columns of xc
+constexpr int HID = 1024;
+inline size_t al64(size_t n) { return (n + 63) & ~(size_t)63; }
+
+// the fc1 and fc2 launches; -> APG_OK or apg_fail's code
+__attribute__((visibility("hidden"))) int apg_head_hidden_fwd(int R, int K1, const float* xc, const float* W1, const float* b1,
+                                                              const float* W2, const float* b2, uint64_t seed, float p1, float p2,
+                                                              float* h1d, float* h2d, hipStream_t st);
+
+// the backward chain's pieces of a head's workspace, in floats from its start; the head's own pieces go behind total
+struct ApgChainLayout {
+    size_t gd, gh2, gh1, gxc, part, total;
+    int c0;                              // first column of g_xc that is computed: 0, or XF when no feature gradient is wanted
+};
+__attribute__((visibility("hidden"))) ApgChainLayout apg_chain_layout(size_t R, int K1, int N, int need_gxf);
+
+struct ApgChainBwd {
+    int R, K1, N, ndec;
+    const int* doff;                     // first packed column of each decoder; doff[ndec] = N
+    const float *xc, *h1d, *h2d, *wdec, *W1, *W2;
+    uint64_t seed;
+    float p1, p2;
+    void* const* g_param;                // fc1 W, b, fc2 W, b, then W, b of each decoder; NULL = skipped
+    bool want_gxc;                       // g_xc[:, c0:] = g_h1 W1[:, c0:] into the layout's gxc, for the head to scatter
+};
+// From g_delta (the head has packed it into the layout's gd): per decoder g_W then g_b; g_h2, g_W2, g_b2; g_h1, g_W1, g_b1; g_xc.
+__attribute__((visibility("hidden"))) int apg_head_chain_bwd(const ApgChainBwd& c, const ApgChainLayout& l, float* ws,
+                                                             hipStream_t st);

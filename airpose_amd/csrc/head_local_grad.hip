@@ -4,14 +4,15 @@
 //   xc = [xf (2048) | segment 0 | ... | segment nseg-1]            K1 = 2048 + S columns, S = sum of the segment widths
 //   h1d = drop1(xc W1^T + b1), h2d = drop2(h1d W2^T + b2)
 //   out_d = xc[:, 2048 + res_d : 2048 + res_d + n_d] + h2d W_d^T + b_d        for each of the ndec decoders
-//   forward:  head_local_pack_kernel (xc, a snapshot of the inputs, and wdec = [W_0; W_1; W_2 | b_0; b_1; b_2] in one launch), then
-//             three products on apg_gemm_kernel (head_grad.hip): fc1, fc2, and ALL decoders as one product of N = sum n_d
-//             columns whose epilogue (APG_EPI_DEC_LOCAL) adds bias and residual and writes every decoder's own output
-//   backward: head_local_pack_gd_kernel (g_delta, R x N, from the per-decoder output gradients), g_h2 = drop2'(g_delta wdec),
-//             g_h1 = drop1'(g_h2 W2), g_xc = g_h1 W1 (segment columns, + features on request); weight gradients g_delta_d^T h2d,
-//             g_h2^T h1d, g_h1^T xc; bias gradients as column sums (two fixed-order passes); head_local_scatter_kernel adds the
-//             residual identity and writes the per-segment gradients; a broadcast (stride-0) segment's rows go to the workspace
-//             and are summed by the same two fixed-order passes.
+// The network itself -- fc1, drop1, fc2, drop2 and the backward chain through them -- is head_mlp.hip's, shared with the two-view
+// head (head_grad.hip); here is what the caller-given layout needs:
+//   forward:  head_local_pack_kernel (xc, a snapshot of the inputs, and wdec = [W_0; W_1; W_2 | b_0; b_1; b_2] in one launch),
+//             apg_head_hidden_fwd, then ALL decoders as one product of N = sum n_d columns on apg_gemm_kernel whose epilogue
+//             (APG_EPI_DEC_LOCAL) adds bias and residual and writes every decoder's own output
+//   backward: head_local_pack_gd_kernel (g_delta, R x N, from the per-decoder output gradients), apg_head_chain_bwd (parameter
+//             gradients and g_xc: segment columns, + features on request); head_local_scatter_kernel adds the residual identity
+//             and writes the per-segment gradients; a broadcast (stride-0) segment's rows go to the workspace and are summed by
+//             the column sums' two fixed-order passes.
 // Every product reduces over K in index order inside one workgroup, no float atomics anywhere: results are bit-reproducible and
 // a row's outputs and input gradients depend only on that row.  Rows are numbered [0, R) for the dropout hash.
 #include "ap_common.h"
@@ -21,8 +22,6 @@
 
 namespace {
 
-constexpr int XF = 2048;                 // trunk features
-constexpr int HID = 1024;
 constexpr int MAX_SEG = APG_HEAD_LOCAL_MAX_SEG, MAX_DEC = APG_HEAD_LOCAL_MAX_DEC;
 
 struct Segs {
@@ -125,28 +124,8 @@ __global__ void __launch_bounds__(256) head_local_scatter_kernel(const float* __
     o[(long long)r * gs.ld[k] + sc - gs.off[k]] = val;
 }
 
-size_t al64(size_t n) { return (n + 63) & ~(size_t)63; }
-
-// workspace layout of apg_head_local_bwd, in floats
-struct BwdLayout {
-    size_t gd, gh2, gh1, gxc, gseg, part, total;
-    int c0;
-};
-
-BwdLayout bwd_layout(int R, int K1, int N, int need_gxf) {
-    const size_t r = (size_t)R, S = (size_t)(K1 - XF);
-    BwdLayout l;
-    l.c0 = need_gxf ? 0 : XF;
-    size_t o = 0;
-    l.gd = o;   o += al64(r * N);
-    l.gh2 = o;  o += al64(r * HID);
-    l.gh1 = o;  o += al64(r * HID);
-    l.gxc = o;  o += al64(r * (K1 - l.c0));
-    l.gseg = o; o += al64(r * S);                            // per-row gradients of the broadcast segments
-    l.part = o; o += al64(((r + APG_CS_ROWS - 1) / APG_CS_ROWS) * HID);
-    l.total = o;
-    return l;
-}
+// workspace of apg_head_local_bwd, in floats: the chain's pieces, then the per-row gradients of the broadcast segments (R x S)
+size_t bwd_floats(const ApgChainLayout& l, int R, int K1) { return l.total + al64((size_t)R * (K1 - XF)); }
 
 // the shared checks of the layout: -> "" or what is wrong; fills off / N / S
 std::string check_layout(int R, int nseg, const int* seg_w, int ndec, const int* dec_n, const int* dec_res, int* seg_off, int* dec_off) {
@@ -204,15 +183,8 @@ int apg_head_local_fwd(int R, const float* xf, int nseg, const void* const* seg,
     if (blocks > 0x7fffffffLL) return apg_fail(APG_EINVAL, "apg_head_local_fwd: too many rows");
     hipLaunchKernelGGL(head_local_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, st, xf, s, d, R, K1, cb, xc, wdec);
     APG_TRY(hipGetLastError());
-    ApgGemmArgs g = apg_gemm_args(xc, K1, 1, W1, 1, K1, R, HID, K1);             // h1 = xc W1^T
-    apg_gemm_set_dropout(g, APG_EPI_HID_FWD, seed, 1, p1);
-    g.bias = b1; g.C = h1d; g.ldc = HID;
-    APG_TRY(apg_gemm_launch(g, st));
-    g = apg_gemm_args(h1d, HID, 1, W2, 1, HID, R, HID, HID);                     // h2 = h1d W2^T
-    apg_gemm_set_dropout(g, APG_EPI_HID_FWD, seed, 2, p2);
-    g.bias = b2; g.C = h2d; g.ldc = HID;
-    APG_TRY(apg_gemm_launch(g, st));
-    g = apg_gemm_args(h2d, HID, 1, wdec, 1, HID, R, N, HID);                     // every decoder: delta = h2d wdec^T
+    if (int rc = apg_head_hidden_fwd(R, K1, xc, W1, b1, W2, b2, seed, p1, p2, h1d, h2d, st)) return rc;
+    ApgGemmArgs g = apg_gemm_args(h2d, HID, 1, wdec, 1, HID, R, N, HID);         // every decoder: delta = h2d wdec^T
     g.epi = APG_EPI_DEC_LOCAL;
     g.bias = wdec + (size_t)N * HID;
     g.base = xc + XF;
@@ -230,7 +202,7 @@ int apg_head_local_fwd(int R, const float* xf, int nseg, const void* const* seg,
 
 int64_t apg_head_local_bwd_workspace_bytes(int R, int K1, int N, int need_gxf) {
     if (R < 1 || K1 <= XF || K1 > XF + MAX_SEG * HID || N < 1 || N > MAX_DEC * HID) return -1;
-    return (int64_t)(bwd_layout(R, K1, N, need_gxf).total * sizeof(float));
+    return (int64_t)(bwd_floats(apg_chain_layout(R, K1, N, need_gxf), R, K1) * sizeof(float));
 }
 
 int apg_head_local_bwd(int R, int nseg, const int* seg_w, const int* seg_bcast, int ndec, const int* dec_n, const int* dec_res,
@@ -245,13 +217,13 @@ int apg_head_local_bwd(int R, int nseg, const int* seg_w, const int* seg_bcast, 
         return apg_fail(APG_EINVAL, "apg_head_local_bwd: bad argument");
     const int S = gs.off[nseg], K1 = XF + S, N = go.off[ndec];
     const int need_gxf = g_xf != nullptr;
-    const BwdLayout l = bwd_layout(R, K1, N, need_gxf);
-    if (workspace_bytes < (int64_t)(l.total * sizeof(float)))
+    const ApgChainLayout l = apg_chain_layout(R, K1, N, need_gxf);
+    if (workspace_bytes < (int64_t)(bwd_floats(l, R, K1) * sizeof(float)))
         return apg_fail(APG_ENOMEM, "apg_head_local_bwd: workspace of " + std::to_string(workspace_bytes) + " bytes, " +
-                                        std::to_string(l.total * sizeof(float)) + " needed");
+                                        std::to_string(bwd_floats(l, R, K1) * sizeof(float)) + " needed");
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
-    float *gd = ws + l.gd, *gh2 = ws + l.gh2, *gh1 = ws + l.gh1, *gxc = ws + l.gxc, *gseg = ws + l.gseg, *part = ws + l.part;
+    float *gd = ws + l.gd, *gxc = ws + l.gxc, *part = ws + l.part, *gseg = ws + l.total;
     go.ndec = ndec;
     for (int e = 0; e < ndec; ++e) {
         go.g[e] = (const float*)g_out[e];
@@ -260,39 +232,6 @@ int apg_head_local_bwd(int R, int nseg, const int* seg_w, const int* seg_bcast, 
     const long long ngd = (long long)R * N;
     hipLaunchKernelGGL(head_local_pack_gd_kernel, dim3((unsigned)((ngd + 255) / 256)), dim3(256), 0, st, go, R, gd);
     APG_TRY(hipGetLastError());
-    // decoders: g_W_d = g_delta_d^T h2d, g_b_d = column sums of g_delta_d
-    for (int e = 0; e < ndec; ++e) {
-        float* gW = (float*)g_param[4 + 2 * e];
-        float* gb = (float*)g_param[5 + 2 * e];
-        if (gW) {
-            ApgGemmArgs g = apg_gemm_args(gd + go.off[e], 1, N, h2d, HID, 1, dec_n[e], HID, R);
-            g.C = gW; g.ldc = HID;
-            APG_TRY(apg_gemm_launch(g, st));
-        }
-        if (gb) APG_TRY(apg_colsum(gd + go.off[e], R, dec_n[e], N, part, gb, st));
-    }
-    // g_h2 = drop2'(g_delta wdec)
-    ApgGemmArgs g = apg_gemm_args(gd, N, 1, wdec, HID, 1, R, HID, N);
-    apg_gemm_set_dropout(g, APG_EPI_HID_BWD, seed, 2, p2);
-    g.C = gh2; g.ldc = HID;
-    APG_TRY(apg_gemm_launch(g, st));
-    if (g_param[2]) {
-        g = apg_gemm_args(gh2, 1, HID, h1d, HID, 1, HID, HID, R);                // g_W2 = g_h2^T h1d
-        g.C = (float*)g_param[2]; g.ldc = HID;
-        APG_TRY(apg_gemm_launch(g, st));
-    }
-    if (g_param[3]) APG_TRY(apg_colsum(gh2, R, HID, HID, part, (float*)g_param[3], st));
-    // g_h1 = drop1'(g_h2 W2)
-    g = apg_gemm_args(gh2, HID, 1, W2, HID, 1, R, HID, HID);
-    apg_gemm_set_dropout(g, APG_EPI_HID_BWD, seed, 1, p1);
-    g.C = gh1; g.ldc = HID;
-    APG_TRY(apg_gemm_launch(g, st));
-    if (g_param[0]) {
-        g = apg_gemm_args(gh1, 1, HID, xc, K1, 1, HID, K1, R);                   // g_W1 = g_h1^T xc
-        g.C = (float*)g_param[0]; g.ldc = K1;
-        APG_TRY(apg_gemm_launch(g, st));
-    }
-    if (g_param[1]) APG_TRY(apg_colsum(gh1, R, HID, HID, part, (float*)g_param[1], st));
     bool any_in = need_gxf;
     gs.nseg = nseg;
     for (int k = 0; k < nseg; ++k) {
@@ -301,11 +240,10 @@ int apg_head_local_bwd(int R, int nseg, const int* seg_w, const int* seg_bcast, 
         if (seg_bcast[k]) { gs.g[k] = gseg + gs.off[k]; gs.ld[k] = S; }          // per-row values, summed below
         else { gs.g[k] = (float*)g_seg[k]; gs.ld[k] = seg_w[k]; }
     }
+    const ApgChainBwd c = {R, K1, N, ndec, go.off, xc, h1d, h2d, wdec, W1, W2, seed, p1, p2, g_param, any_in};
+    if (int rc = apg_head_chain_bwd(c, l, ws, st)) return rc;
     if (any_in) {
         const int nc = K1 - l.c0;
-        g = apg_gemm_args(gh1, HID, 1, W1 + l.c0, K1, 1, R, nc, HID);            // g_xc[:, c0:] = g_h1 W1[:, c0:]
-        g.C = gxc; g.ldc = nc;
-        APG_TRY(apg_gemm_launch(g, st));
         hipLaunchKernelGGL(head_local_scatter_kernel, dim3(R, (nc + 255) / 256), dim3(256), 0, st, gxc, nc, l.c0, K1, g_xf, gs, go);
         APG_TRY(hipGetLastError());
         for (int k = 0; k < nseg; ++k)

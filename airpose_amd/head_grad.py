@@ -10,25 +10,12 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _native as N
+from . import _head_util as U
 from . import _native_grad as G
+from ._head_util import new_seed  # noqa: F401  (the models and tests import it from here)
 
 STATE_W = (3, 3, 6, 126, 10)              # bb, pos, orient, art, shape
 PARAMS = ("fc1", "fc2", "decpose", "decshape")
-
-
-def _rowmajor(t, dev, B, width, name):
-    """fp32 on dev, (1|B, width) with contiguous columns; returned with its row stride (0: one row for the B samples)."""
-    if t.dim() != 2 or t.shape[1] != width or t.shape[0] not in (1, B):
-        raise RuntimeError("%s must be (%d, %d), got %s" % (name, B, width, tuple(t.shape)))
-    if t.device != dev:
-        t = t.to(dev)
-    if t.dtype != torch.float32:
-        t = t.float()
-    if t.shape[0] != B:
-        t = t.expand(B, width)
-    if t.stride(1) != 1 or (t.stride(0) != 0 and t.stride(0) < width):
-        t = t.contiguous()
-    return t
 
 
 class _HeadReg(torch.autograd.Function):
@@ -80,11 +67,6 @@ class _HeadReg(torch.autograd.Function):
         return (None,) + gxf + tuple(gst) + tuple(g_param)
 
 
-def new_seed():
-    """A fresh dropout seed from torch's default CPU generator (torch.manual_seed reproduces a run)."""
-    return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-
-
 def forward_reg(net, xf0, xf1, bb0, bb1, pos0, pos1, orient0, orient1, art0, art1, shape0, shape1, seed=None):
     """One differentiable evaluation of the two-view head -> (pred_pose0, pred_shape0, pred_pose1, pred_shape1)."""
     if not xf0.is_cuda:
@@ -93,27 +75,14 @@ def forward_reg(net, xf0, xf1, bb0, bb1, pos0, pos1, orient0, orient1, art0, art
     B = xf0.shape[0]
     if B < 1 or xf0.dim() != 2 or xf0.shape[1] != 2048 or tuple(xf1.shape) != tuple(xf0.shape):
         raise RuntimeError("forward_reg expects two (B, 2048) feature tensors with B >= 1")
-    params = []
-    for name in PARAMS:
-        m = getattr(net, name)
-        for p in (m.weight, m.bias):
-            if p.device != dev:
-                raise RuntimeError("airpose_amd.copenet: the head's parameters live on %s, the inputs on %s -- call net.to(dev) "
-                                   "first" % (p.device, dev))
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise RuntimeError("airpose_amd.copenet: the head's parameters must be contiguous fp32")
-            params.append(p)
-    xf0 = _rowmajor(xf0, dev, B, 2048, "xf0").contiguous()
-    xf1 = _rowmajor(xf1, dev, B, 2048, "xf1").contiguous()
+    params = U.params(net, PARAMS, dev)
+    xf0 = U.rows(xf0, dev, B, 2048, "xf0", True).contiguous()
+    xf1 = U.rows(xf1, dev, B, 2048, "xf1", True).contiguous()
     names = ("bb", "pred_position", "pred_orient", "pred_art_pose", "pred_shape")
     st = []
     for v, ts in enumerate(((bb0, pos0, orient0, art0, shape0), (bb1, pos1, orient1, art1, shape1))):
-        st += [_rowmajor(t, dev, B, w, "%s%d" % (n, v)) for t, w, n in zip(ts, STATE_W, names)]
-    p1 = float(net.drop1.p) if net.drop1.training else 0.0
-    p2 = float(net.drop2.p) if net.drop2.training else 0.0
-    if seed is None:
-        seed = new_seed()
-    net.last_dropout_seed = seed
+        st += [U.rows(t, dev, B, w, "%s%d" % (n, v), True) for t, w, n in zip(ts, STATE_W, names)]
+    p1, p2, seed = U.dropout(net, seed)
     return _HeadReg.apply((B, seed, p1, p2, dev), xf0, xf1, *st, *params)
 
 

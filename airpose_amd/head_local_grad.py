@@ -16,8 +16,8 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _native as N
+from . import _head_util as U
 from . import _native_grad as G
-from .head_grad import new_seed
 
 # model -> (segments (name, width) in fc1 column order behind the 2048 features, decoders (module, n, residual column))
 LAYOUTS = {
@@ -82,19 +82,6 @@ class _HeadLocal(torch.autograd.Function):
         return (None, g_xf) + tuple(g_seg) + tuple(g_param)
 
 
-def _segment(t, dev, R, width, name):
-    """fp32 on dev, (1|R, width) with contiguous columns (any row stride >= width, or 0)."""
-    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != width or t.shape[0] not in (1, R):
-        raise RuntimeError("%s must be (%d, %d), got %s" % (name, R, width, tuple(getattr(t, "shape", ()))))
-    if t.device != dev:
-        t = t.to(dev)
-    if t.dtype != torch.float32:
-        t = t.float()
-    if t.stride(1) != 1 or (t.stride(0) != 0 and t.stride(0) < width):
-        t = t.contiguous()
-    return t
-
-
 def head(net, model, xf, segments, seed=None):
     """One differentiable evaluation of `net`'s head in the layout LAYOUTS[model] on R = xf.shape[0] rows -> one (R, n_d) tensor
     per decoder.  segments: one (1|R, width) tensor per segment.  The seed is recorded in net.last_dropout_seed."""
@@ -105,25 +92,12 @@ def head(net, model, xf, segments, seed=None):
     if R < 1 or xf.dim() != 2 or xf.shape[1] != 2048:
         raise RuntimeError("the head expects (R, 2048) features with R >= 1")
     K1 = 2048 + sum(w for _, w in seg_l)
-    params = []
-    for name in ("fc1", "fc2") + tuple(d[0] for d in dec_l):
-        m = getattr(net, name)
-        for p in (m.weight, m.bias):
-            if p.device != dev:
-                raise RuntimeError("airpose_amd.copenet: the head's parameters live on %s, the inputs on %s -- call net.to(dev) "
-                                   "first" % (p.device, dev))
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise RuntimeError("airpose_amd.copenet: the head's parameters must be contiguous fp32")
-            params.append(p)
+    params = U.params(net, ("fc1", "fc2") + tuple(d[0] for d in dec_l), dev)
     if tuple(net.fc1.weight.shape) != (1024, K1) or any(tuple(getattr(net, n).weight.shape) != (k, 1024) for n, k, _ in dec_l):
         raise RuntimeError("airpose_amd.copenet: the module's fc1 / decoders do not have the %s layout" % model)
-    xf = _segment(xf, dev, R, 2048, "xf").contiguous()
-    segs = [_segment(t, dev, R, w, n) for t, (n, w) in zip(segments, seg_l)]
-    p1 = float(net.drop1.p) if net.drop1.training else 0.0
-    p2 = float(net.drop2.p) if net.drop2.training else 0.0
-    if seed is None:
-        seed = new_seed()
-    net.last_dropout_seed = seed
+    xf = U.rows(xf, dev, R, 2048, "xf", False).contiguous()
+    segs = [U.rows(t, dev, R, w, n, False) for t, (n, w) in zip(segments, seg_l)]
+    p1, p2, seed = U.dropout(net, seed)
     cfg = (R, int(seed), p1, p2, dev, tuple(w for _, w in seg_l), tuple(n for _, n, _ in dec_l), tuple(r for _, _, r in dec_l))
     return _HeadLocal.apply(cfg, xf, *segs, *params)
 

@@ -103,3 +103,24 @@ def test_workspace_query_and_short_workspace():
     assert _bwd(L, G, 5, *HMR, ws_bytes=need - 1) == APG_ENOMEM
     assert b"workspace" in L.apg_last_error()
     assert _bwd(L, G, 5, *HMR, ws_bytes=0) == APG_ENOMEM
+
+
+def test_workspace_sizes_of_both_heads_are_pinned():
+    """The byte counts are ABI (callers allocate by them): the closed form, a(n) = n rounded up to 64 floats, and the answers of
+    the library before the heads shared their chain."""
+    G, L = _lib()
+    a = lambda n: (n + 63) // 64 * 64
+    part = lambda R: a((R + 31) // 32 * 1024)
+    two = {1: (617984, 634368), 33: (1260288, 1800960), 257: (5756416, 9967104)}
+    for B, want in two.items():
+        R = 2 * B
+        for gxf in (0, 1):
+            form = 4 * (a(145 * R) + a(145 * 1024) + 2 * a(1024 * R) + a(R * (2332 - (0 if gxf else 2048))) + part(R))
+            assert L.apg_head_bwd_workspace_bytes(B, gxf) == form == want[gxf], (B, gxf)
+    local = {(2193, 145): {1: (14592, 22784), 33: (336128, 606464), 65: (658432, 1190912)},
+             (2332, 145): {1: (15616, 23808), 33: (372992, 643328), 65: (730624, 1263104)}}
+    for (K1, N), rows in local.items():
+        for R, want in rows.items():
+            for gxf in (0, 1):
+                form = 4 * (a(R * N) + 2 * a(1024 * R) + a(R * (K1 - (0 if gxf else 2048))) + a(R * (K1 - 2048)) + part(R))
+                assert L.apg_head_local_bwd_workspace_bytes(R, K1, N, gxf) == form == want[gxf], (K1, N, R, gxf)
