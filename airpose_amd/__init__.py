@@ -8,6 +8,7 @@ Public mirrors of the reference interfaces:
   TrainingLoss (loss.py)               <- get_loss of copenet_twoview / copenet_singleview / hmr / muhmr
   RealDataLoss (loss_real.py)          <- get_loss of the copenet_real fine-tune trainers (2-D keypoints + VPoser prior)
   FusedAdam (optim.py)                 <- torch.optim.Adam(..., amsgrad=True) of the trainers' configure_optimizers
+  EvalMetrics (eval_metrics.py)        <- test_epoch_end of the four trainers: MPJPE, MPE, angle error
 The compute lives in libairpose_hip.so (include/airpose_hip.h); nothing here falls back to CPU.
 """
 __version__ = "0.1.0"
@@ -24,4 +25,7 @@ def __getattr__(name):
     if name == "FusedAdam":                                               # likewise (optim.py)
         from .optim import FusedAdam
         return FusedAdam
+    if name == "EvalMetrics":                                             # likewise (eval_metrics.py)
+        from .eval_metrics import EvalMetrics
+        return EvalMetrics
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

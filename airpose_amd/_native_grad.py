@@ -72,6 +72,10 @@ SIGNATURES = {
     "apg_real_loss_fwd_bwd": (_i, [_i] * 6 + [_f, _c.POINTER(_f), _vp, _vpp, _vpp, _vp, _vpp, _vp, _i64, _vp]),
     # the optimizer step (optim.hip)
     "apg_adam_step": (_i, [_i] + [_vpp] * 5 + [_c.POINTER(_i64)] * 2 + [_c.c_double] * 5 + [_vp]),
+    # the evaluation metrics (eval_metrics.hip)
+    "apg_eval_workspace_bytes": (_i64, [_i, _i]),
+    "apg_eval_acc_doubles": (_i64, []),
+    "apg_eval_update": (_i, [_i, _i, _i, _vp, _ip, _vpp] + [_vp] * 6 + [_i64, _vp]),
 }
 PRECISIONS = {"fp32": 0, "bf16": 1}          # include/airpose_grad.h: APG_PREC_*
 

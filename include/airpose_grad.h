@@ -439,6 +439,61 @@ int apg_real_loss_fwd_bwd(int nviews, int cross, int B, int J, int Jg, int depth
                           const void* encoder, const void* const* pred, const void* const* gt, float* terms, void* const* grads,
                           void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Evaluation metrics (eval_metrics.hip): what the reference trainers' test_epoch_end computes from the test_step output dicts
+ * (copenet_twoview.py:539-601, copenet_singleview.py:394-432, muhmr.py:463-517, hmr.py:365-386): the mean per-joint position error
+ * over the 22 body joints (MPJPE), the translation error (MPE) and hmr's angle-axis error, summed into fp64 accumulators that persist
+ * across batches.  Additive under ABI 2: a binding tells a library that has it by looking up apg_eval_update.
+ *
+ * The reference poses SMPL-X four times per batch (ground truth and prediction, two views) with betas = 0 and reads 22 joints of
+ * each.  With betas = 0 those joints depend on the 22 rotations and the rest joints J_regressor v_template alone, so no vertex is
+ * touched here:
+ *   - angle-axis -> matrix is torchgeometry 0.1.2's angle_axis_to_rotation_matrix.  With t2 = r . r and eps = 1e-6: if t2 > eps,
+ *     th = sqrt(t2), w = r / (th + eps) (the epsilon stays in the denominator: the axis is deliberately not unit), c = cos th,
+ *     s = sin th and
+ *       R00 = c + wx^2 (1 - c)       R01 = wx wy (1 - c) - wz s    R02 = wy s + wx wz (1 - c)
+ *       R10 = wz s + wx wy (1 - c)   R11 = c + wy^2 (1 - c)        R12 = -wx s + wy wz (1 - c)
+ *       R20 = -wy s + wx wz (1 - c)  R21 = wx s + wy wz (1 - c)    R22 = c + wz^2 (1 - c)
+ *     otherwise the first-order form I + skew(r), not orthonormal, as tgm leaves it.  (tgm blends the two branches by 0/1 masks and
+ *     neither is ever non-finite; the select here is identical.)
+ *   - the chain is lbs.batch_rigid_transform restricted to joints 0 .. 21: G_0 = R_0, p_0 = J_0; for j >= 1
+ *     G_j = G_parent R_j and p_j = p_parent + G_parent (J_j - J_parent).  parents[j] < j, so the hands and the face never enter.
+ *   - joint_err = |p_pred - p_gt|_2 per joint, trans_err = |t_pred - t_gt|_2, angle_err = |a_pred - a_gt|_2 per joint (hmr's metric:
+ *     only with APG_EVAL_ANGLE_AXIS and gt angles given).
+ *
+ * apg_eval_update, one call per batch:
+ *   flags: APG_EVAL_ANGLE_AXIS (pred_rot is (B, 22, 3) angle-axis vectors) or APG_EVAL_ROTMAT (pred_rot is (B, 22, 3, 3) matrices).
+ *   j_rest: (22, 3) rest joints (device).  parents: HOST array of 22 ints; parents[0] == -1 and 0 <= parents[j] < j.
+ *   per_view: HOST array of APG_EVAL_PER_VIEW * views device pointers; per view gt_orient (B, 1, 3, 3), pred_rot, gt_trans (B, 3),
+ *     pred_trans (B, 3), gt_angles (B, 22, 3).  The last three may be NULL, the translations only as a pair.
+ *   gt_body: (B, 21, 3, 3), shared by the views.
+ *   joint_err (views, B, 22), trans_err (views, B), angle_err (views, B, 22): optional per-sample outputs (NULL = not wanted), each
+ *     written in full; trans_err / angle_err need the translations / the gt angles of every view.
+ *   acc: apg_eval_acc_doubles() = 2 * APG_EVAL_ACC_PER_VIEW doubles (device, 8-byte aligned), ADDED to; the caller zeroes it to start
+ *     or reset.  Per view: [0] samples, [1] sum of joint_err, [2 .. 23] the same per joint, [24] sum of trans_err, [25] sum of
+ *     angle_err, [26] samples that had a translation, [27] samples that had gt angles.  The second view's block is untouched with
+ *     views = 1.  MPJPE = acc[1] / (22 acc[0]), MPE = acc[24] / acc[26], the angle error acc[25] / (22 acc[27]).
+ *   workspace: at least apg_eval_workspace_bytes(B, views) bytes (negative for B < 0 or views outside {1, 2}; positive and
+ *     non-decreasing in B otherwise), 8-byte aligned, else APG_ENOMEM; the workgroups' partial sums.  It carries nothing from call
+ *     to call and needs no initialisation.
+ * All other data is fp32, contiguous, 4-byte aligned.  Determinism: no atomics and no arrival counter; each workgroup sums its
+ * samples in index order in fp64, a second launch adds the workgroups' partials in index order in fp64 and adds the total to acc.
+ * The partition depends on (B, views) alone, so accumulators and per-sample outputs are bit-identical from run to run.  Two
+ * launches, no host synchronisation.  B = 0 is a success without a launch: acc is untouched.
+ * APG_EINVAL before any GPU call, the message naming the argument: B < 0, views outside {1, 2}, flags neither of the two, a NULL
+ * j_rest, parents, per_view, gt_body, acc, workspace, gt_orient or pred_rot, a bad parents table, a pointer that is not 4-byte
+ * (acc, workspace: 8-byte) aligned, a translation given by half, gt_angles with APG_EVAL_ROTMAT, trans_err / angle_err asked for
+ * without their inputs. */
+#define APG_EVAL_ANGLE_AXIS 0
+#define APG_EVAL_ROTMAT 1
+#define APG_EVAL_PER_VIEW 5
+#define APG_EVAL_ACC_PER_VIEW 28
+int64_t apg_eval_workspace_bytes(int B, int views);
+int64_t apg_eval_acc_doubles(void);
+int apg_eval_update(int B, int views, int flags, const float* j_rest, const int* parents, const void* const* per_view,
+                    const float* gt_body, float* joint_err, float* trans_err, float* angle_err, double* acc, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
