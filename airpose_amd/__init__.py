@@ -9,6 +9,7 @@ Public mirrors of the reference interfaces:
   RealDataLoss (loss_real.py)          <- get_loss of the copenet_real fine-tune trainers (2-D keypoints + VPoser prior)
   FusedAdam (optim.py)                 <- torch.optim.Adam(..., amsgrad=True) of the trainers' configure_optimizers
   EvalMetrics (eval_metrics.py)        <- test_epoch_end of the four trainers: MPJPE, MPE, angle error
+  Renderer (renderer.py)               <- utils/renderer.py Renderer: visualize_tb of the trainers' summaries(), without pyrender
 The compute lives in libairpose_hip.so (include/airpose_hip.h); nothing here falls back to CPU.
 """
 __version__ = "0.1.0"
@@ -28,4 +29,7 @@ def __getattr__(name):
     if name == "EvalMetrics":                                             # likewise (eval_metrics.py)
         from .eval_metrics import EvalMetrics
         return EvalMetrics
+    if name == "Renderer":                                                # likewise (renderer.py)
+        from .renderer import Renderer
+        return Renderer
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -76,6 +76,9 @@ SIGNATURES = {
     "apg_eval_workspace_bytes": (_i64, [_i, _i]),
     "apg_eval_acc_doubles": (_i64, []),
     "apg_eval_update": (_i, [_i, _i, _i, _vp, _ip, _vpp] + [_vp] * 6 + [_i64, _vp]),
+    # the mesh overlay renderer (render.hip)
+    "apg_render_workspace_bytes": (_i64, [_i] * 5),
+    "apg_render_overlay": (_i, [_i] * 5 + [_vp] * 4 + [_i, _vp, _vp] + [_f] * 6 + [_vp] + [_f] * 5 + [_vp] * 4 + [_i64, _vp]),
 }
 PRECISIONS = {"fp32": 0, "bf16": 1}          # include/airpose_grad.h: APG_PREC_*
 

@@ -494,6 +494,47 @@ int apg_eval_update(int B, int views, int flags, const float* j_rest, const int*
                     const float* gt_body, float* joint_err, float* trans_err, float* angle_err, double* acc, void* workspace,
                     int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mesh overlay renderer (render.hip): what the reference's utils/renderer.py Renderer draws with pyrender -- n posed meshes over n
+ * background images, for summaries() -- stated as ray casting.  Additive under ABI 2: a binding tells a library that has it by
+ * looking up apg_render_overlay.  pyrender is absent, so the half-pixel convention and the shading are UNPINNED; the geometry is
+ * pinned by this text.
+ *
+ * Camera coordinates are x right, y down, z forward (the reference's 180 degree turn about x only converts to GL's camera and is
+ * absorbed).  A vertex is p = R v + t with the image's R, t.  Pixel (row i, column j) owns the ray
+ * d = ((j + 0.5 - cx) / fx, (i + 0.5 - cy) / fy, 1).  For face f = (p0, p1, p2):
+ *   w0 = d . (p1 x p2), w1 = d . (p2 x p0), w2 = d . (p0 x p1), det = p0 . (p1 x p2)
+ *   the face is drawn iff det < 0 strictly (front-facing for outward counter-clockwise faces; degenerate and repeated-index faces
+ *   drop out) and all its vertices are finite; the ray hits it iff -w0, -w1, -w2 >= 0 (inclusive on all three edges: a shared edge
+ *   may be claimed twice, never left uncovered) and z = det / (w0 + w1 + w2) has znear <= z <= zfar.
+ * The pixel shows the hit with the smallest z and, on exactly equal z, the lowest face index: both are independent of any order, so
+ * every output is bit-identical from run to run.
+ *   out_depth (n, H, W): that z, 0 where nothing is hit.  out_face (n, H, W) int32: the face, -1 where nothing is hit.  Both optional.
+ *   out_rgb (n, 3, H, W): the colour where hit, elsewhere the background's pixel bit for bit (0 with a NULL background).
+ * Shading, a stand-in without pyrender's specular lobe: the vertex normal is the normalised sum of (p1 - p0) x (p2 - p0) over the
+ * vertex's faces with finite vertices in ascending face order (csr_offsets (V + 1), csr_faces (csr_len <= 3 F): the faces of vertex v are
+ * csr_faces[csr_offsets[v] .. csr_offsets[v + 1]), ascending, a face once per distinct vertex; no float atomics).  The normals are
+ * interpolated with b_k = w_k / (w0 + w1 + w2), the hit point's barycentrics (perspective-correct), renormalised to n, and
+ *   colour = min(1, base_rgb * (ambient + diffuse * max(0, -n_z)));   a zero-length normal gives the ambient term only.
+ *
+ * apg_render_overlay: vertices (n, V, 3) f32, faces (F, 3) i32, R (n, 3, 3) row-major or NULL = identity, t (n, 3) or NULL = zero,
+ * background (n, 3, H, W) f32 or NULL = black; it must not be out_rgb.  All device pointers, contiguous, 4-byte aligned.  Face and
+ * CSR entries outside their tables are skipped on the device (such a face is not drawn); the caller should validate them once.
+ * workspace: at least apg_render_workspace_bytes(n, H, W, V, F) bytes (negative outside the limits below; non-decreasing in every
+ * argument), 16-byte aligned (it holds 16-byte records), else APG_ENOMEM; it carries nothing from call to call and needs no
+ * initialisation.
+ * Limits: 0 <= n <= 65535; 1 <= H, W <= 16384; 1 <= V, F <= 2^24; n H W, n V and n F at most 2^36.  n = 0 succeeds without a launch.
+ * APG_EINVAL before any GPU call, the message naming the argument: a size outside the limits, csr_len outside 0 .. 3 F, a NULL
+ * vertices, faces, csr_offsets, csr_faces, out_rgb or workspace, a misaligned pointer (workspace: 16 bytes, the rest 4), fx, fy, znear not positive and finite,
+ * cx, cy not finite, zfar < znear, a negative or non-finite base colour, ambient or diffuse, out_rgb == background.
+ * Five launches on `stream`, no host synchronisation. */
+int64_t apg_render_workspace_bytes(int n, int H, int W, int V, int F);
+int apg_render_overlay(int n, int V, int F, int H, int W, const float* vertices, const int* faces, const int* csr_offsets,
+                       const int* csr_faces, int csr_len, const float* R, const float* t, float fx, float fy, float cx, float cy,
+                       float znear, float zfar, const float* background, float base_r, float base_g, float base_b, float ambient,
+                       float diffuse, float* out_rgb, float* out_depth, int* out_face, void* workspace, int64_t workspace_bytes,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
