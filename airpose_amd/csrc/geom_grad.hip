@@ -13,22 +13,7 @@ namespace {
 
 thread_local std::string g_err;
 
-constexpr int GT = 256;                  // threads per body
-
-// fixed-order tree over the GT threads of NV values each (s: GT * NV floats of LDS); result in s[0..NV)
-template <int NV>
-__device__ __forceinline__ void block_reduce(float* s, const float* v) {
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) s[k * GT + t] = v[k];
-    __syncthreads();
-    for (int h = GT / 2; h > 0; h >>= 1) {
-        if (t < h)
-#pragma unroll
-            for (int k = 0; k < NV; ++k) s[k * GT + t] += s[k * GT + t + h];
-        __syncthreads();
-    }
-}
+#include "loss_common.inc"               // LT (threads per body) and block_reduce; result k in s[k * LT]
 
 __device__ __forceinline__ void normalize_bwd(const float* a, const float* b, float nrm, bool clamped, const float* gb, float* ga) {
     // b = a / max(|a|, eps):  g_a = (g_b - b (b . g_b)) / |a|, or g_b / eps below the clamp
@@ -83,19 +68,19 @@ __global__ void __launch_bounds__(256) rot6d_bwd_kernel(const float* __restrict_
 }
 
 // out = (fx X / Z + cx, fy Y / Z + cy), [X Y Z] = R p + t
-__global__ void __launch_bounds__(GT) projection_bwd_kernel(const float* __restrict__ pts, int P, const float* __restrict__ R,
+__global__ void __launch_bounds__(LT) projection_bwd_kernel(const float* __restrict__ pts, int P, const float* __restrict__ R,
                                                             const float* __restrict__ tr, float fx, float fy,
                                                             const float* __restrict__ gout, float* __restrict__ gpts,
                                                             float* __restrict__ gR, float* __restrict__ gt,
                                                             float* __restrict__ gc) {
-    __shared__ float s[14 * GT];
+    __shared__ float s[14 * LT];
     const int b = blockIdx.x;
     float r[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
     if (R)
         for (int k = 0; k < 9; ++k) r[k] = R[(size_t)b * 9 + k];
     float acc[14];                                        // g_R (9) | g_t (3) | g_c (2)
     for (int k = 0; k < 14; ++k) acc[k] = 0.f;
-    for (int p = threadIdx.x; p < P; p += GT) {
+    for (int p = threadIdx.x; p < P; p += LT) {
         const size_t i = (size_t)b * P + p;
         const float x = pts[i * 3], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
         float X = r[0] * x + r[1] * y + r[2] * z, Y = r[3] * x + r[4] * y + r[5] * z, Z = r[6] * x + r[7] * y + r[8] * z;
@@ -117,22 +102,22 @@ __global__ void __launch_bounds__(GT) projection_bwd_kernel(const float* __restr
     }
     block_reduce<14>(s, acc);
     const int t = threadIdx.x;
-    if (t < 9 && gR) gR[(size_t)b * 9 + t] = s[t * GT];
-    if (t >= 9 && t < 12 && gt) gt[(size_t)b * 3 + t - 9] = s[t * GT];
-    if (t >= 12 && t < 14 && gc) gc[(size_t)b * 2 + t - 12] = s[t * GT];
+    if (t < 9 && gR) gR[(size_t)b * 9 + t] = s[t * LT];
+    if (t >= 9 && t < 12 && gt) gt[(size_t)b * 3 + t - 9] = s[t * LT];
+    if (t >= 12 && t < 14 && gc) gc[(size_t)b * 2 + t - 12] = s[t * LT];
 }
 
 // out = M[:, :3] p + M[:, 3]
-__global__ void __launch_bounds__(GT) transform_bwd_kernel(const float* __restrict__ rt, const float* __restrict__ pts, int P,
+__global__ void __launch_bounds__(LT) transform_bwd_kernel(const float* __restrict__ rt, const float* __restrict__ pts, int P,
                                                            const float* __restrict__ gout, float* __restrict__ grt,
                                                            float* __restrict__ gpts) {
-    __shared__ float s[12 * GT];
+    __shared__ float s[12 * LT];
     const int b = blockIdx.x;
     float m[12];
     for (int k = 0; k < 12; ++k) m[k] = rt[(size_t)b * 12 + k];
     float acc[12];
     for (int k = 0; k < 12; ++k) acc[k] = 0.f;
-    for (int p = threadIdx.x; p < P; p += GT) {
+    for (int p = threadIdx.x; p < P; p += LT) {
         const size_t i = (size_t)b * P + p;
         const float pv[3] = {pts[i * 3], pts[i * 3 + 1], pts[i * 3 + 2]};
         const float g[3] = {gout[i * 3], gout[i * 3 + 1], gout[i * 3 + 2]};
@@ -145,7 +130,7 @@ __global__ void __launch_bounds__(GT) transform_bwd_kernel(const float* __restri
     }
     if (!grt) return;                                     // uniform over the workgroup
     block_reduce<12>(s, acc);
-    if (threadIdx.x < 12) grt[(size_t)b * 12 + threadIdx.x] = s[threadIdx.x * GT];
+    if (threadIdx.x < 12) grt[(size_t)b * 12 + threadIdx.x] = s[threadIdx.x * LT];
 }
 
 }  // namespace
@@ -178,7 +163,7 @@ int apg_perspective_projection_bwd(const float* pts, int B, int P, const float* 
                                    float fy, const float* g_out, float* g_pts, float* g_rotation, float* g_translation,
                                    float* g_center, void* stream) {
     if (!pts || !g_out || B <= 0 || P <= 0) return apg_fail(APG_EINVAL, "apg_perspective_projection_bwd: bad argument");
-    hipLaunchKernelGGL(projection_bwd_kernel, dim3(B), dim3(GT), 0, (hipStream_t)stream, pts, P, rotation, translation, fx, fy,
+    hipLaunchKernelGGL(projection_bwd_kernel, dim3(B), dim3(LT), 0, (hipStream_t)stream, pts, P, rotation, translation, fx, fy,
                        g_out, g_pts, g_rotation, g_translation, g_center);
     APG_CHECK_LAUNCH("projection_bwd_kernel");
     return APG_OK;
@@ -187,7 +172,7 @@ int apg_perspective_projection_bwd(const float* pts, int B, int P, const float* 
 int apg_transform_points_bwd(const float* rt, const float* pts, int B, int P, const float* g_out, float* g_rt, float* g_pts,
                              void* stream) {
     if (!rt || !pts || !g_out || B <= 0 || P <= 0) return apg_fail(APG_EINVAL, "apg_transform_points_bwd: bad argument");
-    hipLaunchKernelGGL(transform_bwd_kernel, dim3(B), dim3(GT), 0, (hipStream_t)stream, rt, pts, P, g_out, g_rt, g_pts);
+    hipLaunchKernelGGL(transform_bwd_kernel, dim3(B), dim3(LT), 0, (hipStream_t)stream, rt, pts, P, g_out, g_rt, g_pts);
     APG_CHECK_LAUNCH("transform_bwd_kernel");
     return APG_OK;
 }

@@ -23,10 +23,10 @@
 
 namespace {
 
-constexpr int LT = 256;                  // threads per workgroup
+#include "loss_common.inc"               // LT, NJ, block_reduce, limb_weight
+
 constexpr int LOSS_EPB = 4096;           // vertex-stream floats per workgroup: 256 threads x 4 quads of 4
 constexpr int LOSS_SB = 4;               // bodies per small-term workgroup
-constexpr int NJ = 22;                   // joints the loss reads
 
 // partial sums of a small-term workgroup
 enum { S_TRANS0, S_TRANS1, S_KP0, S_KP1, S_KP3D, S_ROOT0, S_ROOT1, S_POSE, S_BET0, S_BET1, S_BETC, S_CAM0, S_CAM1, S_COUNT };
@@ -61,21 +61,6 @@ struct CombineArgs {
     int has_trans, has_cam;
     float* terms;
 };
-
-// fixed-order tree over the LT threads of NV values each (s: LT * NV floats of LDS); result k in s[k * LT]
-template <int NV>
-__device__ __forceinline__ void block_reduce(float* s, const float* v) {
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) s[k * LT + t] = v[k];
-    __syncthreads();
-    for (int h = LT / 2; h > 0; h >>= 1) {
-        if (t < h)
-#pragma unroll
-            for (int k = 0; k < NV; ++k) s[k * LT + t] += s[k * LT + t + h];
-        __syncthreads();
-    }
-}
 
 template <bool ALIGNED>
 __device__ __forceinline__ void load4(const float* p, float* v) {
@@ -146,14 +131,6 @@ __device__ __forceinline__ void verts_block(const LossArgs& a, long long blk, fl
     }
     block_reduce<V_COUNT>(s, acc);
     if (threadIdx.x < V_COUNT) a.vpart[blk * V_COUNT + threadIdx.x] = s[threadIdx.x * LT];
-}
-
-// limb weight of 3-D joint j: {4, 5, 18, 19} -> l, {7, 8, 20, 21} -> l^2.  The pose term asks with j = its own index + 1 (the root
-// is not among its 21 rotations), which gives the reference's {3, 4, 17, 18} and {6, 7, 19, 20}.
-__device__ __forceinline__ float limb_weight(int j, float l, float l2) {
-    if (j == 4 || j == 5 || j == 18 || j == 19) return l;
-    if (j == 7 || j == 8 || j == 20 || j == 21) return l2;
-    return 1.f;
 }
 
 __device__ __forceinline__ void small_block(const LossArgs& a, int blk, float* s) {

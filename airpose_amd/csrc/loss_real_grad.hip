@@ -23,16 +23,17 @@
 // the two-output h loop into v_pk_fma_f32 on LDS-read operands (65 of them), the family of code that gave wrong lanes in
 // smplx_prep_kernel while another kernel's waves shared the SIMD.  With the flag the device code holds no packed fp32 math.
 //
-// aa_fwd / aa_bwd are a COPY of fitting.hip's (lines 58-114 there), not a shared include: fitting.hip belongs to libairpose_hip.so,
-// whose objects stay byte-identical; the hidden vector stays in LDS between the two halves.
+// aa_fwd / aa_bwd are the fitter's, shared with fitting.hip (libairpose_hip.so) through rot_aa.inc; the tree, limb_weight, LT and NJ
+// are shared with loss_grad.hip and geom_grad.hip through loss_common.inc.  The hidden vector stays in LDS between the two halves.
 #include "grad_internal.h"
 
 #include <string>
 
 namespace {
 
-constexpr int LT = 256;                  // threads per workgroup
-constexpr int NJ = 22;                   // joints the loss reads
+#include "loss_common.inc"
+#include "rot_aa.inc"
+
 constexpr int NR = 21;                   // body rotations behind the prior
 constexpr int NIN = 63, NH = 512, NO = 64, NZ = 32;
 constexpr int SEG = NH / 4;              // k segment of the two long dot products
@@ -66,74 +67,6 @@ struct RealCombineArgs {
     float n_kp, n_vp, n_pose, n_beta, n_depth;               // the means' denominators
     float* terms;
 };
-
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 v3(float x, float y, float z) { V3 r; r.x = x; r.y = y; r.z = z; return r; }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ V3 operator*(float s, V3 a) { return v3(s * a.x, s * a.y, s * a.z); }
-
-// rotation matrix (row-major r[9]) -> axis-angle, tgm 0.1.2, keeping what the adjoint needs
-struct AA { V3 aa; float q[4], t, s, w, x, y, z; int br; };
-__device__ __forceinline__ AA aa_fwd(const float* r) {
-    AA a;
-    const float t00 = r[0], t10 = r[1], t20 = r[2], t01 = r[3], t11 = r[4], t21 = r[5], t02 = r[6], t12 = r[7], t22 = r[8];
-    if (t22 < 1e-6f) {
-        if (t00 > t11) { a.br = 0; a.t = 1 + t00 - t11 - t22; a.q[0] = t12 - t21; a.q[1] = a.t; a.q[2] = t01 + t10; a.q[3] = t20 + t02; }
-        else           { a.br = 1; a.t = 1 - t00 + t11 - t22; a.q[0] = t20 - t02; a.q[1] = t01 + t10; a.q[2] = a.t; a.q[3] = t12 + t21; }
-    } else {
-        if (t00 < -t11) { a.br = 2; a.t = 1 - t00 - t11 + t22; a.q[0] = t01 - t10; a.q[1] = t20 + t02; a.q[2] = t12 + t21; a.q[3] = a.t; }
-        else            { a.br = 3; a.t = 1 + t00 + t11 + t22; a.q[0] = a.t; a.q[1] = t12 - t21; a.q[2] = t20 - t02; a.q[3] = t01 - t10; }
-    }
-    a.s = 0.5f / sqrtf(a.t);
-    a.w = a.q[0] * a.s; a.x = a.q[1] * a.s; a.y = a.q[2] * a.s; a.z = a.q[3] * a.s;
-    const float ss = a.x * a.x + a.y * a.y + a.z * a.z, sn = sqrtf(ss);
-    const float two_theta = 2.0f * (a.w < 0.f ? atan2f(-sn, -a.w) : atan2f(sn, a.w));
-    const float k = ss > 0.f ? two_theta / sn : 2.0f;
-    a.aa = v3(a.x * k, a.y * k, a.z * k);
-    return a;
-}
-// d(loss)/d(aa) -> d(loss)/d(R) (row-major dr[9], overwritten)
-__device__ __forceinline__ void aa_bwd(const AA& a, V3 daa, float* dr) {
-    const float ss = a.x * a.x + a.y * a.y + a.z * a.z, sn = sqrtf(ss);
-    float dw = 0.f;
-    V3 dxyz;
-    if (ss > 0.f) {
-        const float T = 2.0f * (a.w < 0.f ? atan2f(-sn, -a.w) : atan2f(sn, a.w)), k = T / sn;
-        const float dk = daa.x * a.x + daa.y * a.y + daa.z * a.z;
-        dxyz = k * daa;
-        const float dT = dk / sn;
-        float dsn = -dk * T / ss;
-        const float den = ss + a.w * a.w;
-        dsn += 2.f * dT * a.w / den;
-        dw = -2.f * dT * sn / den;
-        const float dss = dsn / (2.f * sn);
-        dxyz = dxyz + (2.f * dss) * v3(a.x, a.y, a.z);
-    } else {
-        dxyz = 2.f * daa;
-    }
-    const float dq[4] = {dw * a.s, dxyz.x * a.s, dxyz.y * a.s, dxyz.z * a.s};
-    const float ds = dw * a.q[0] + dxyz.x * a.q[1] + dxyz.y * a.q[2] + dxyz.z * a.q[3];
-    float dt = -ds * a.s / (2.f * a.t);
-    float d00 = 0, d10 = 0, d20 = 0, d01 = 0, d11 = 0, d21 = 0, d02 = 0, d12 = 0, d22 = 0;   // d/d t_ab
-    switch (a.br) {
-        case 0: dt += dq[1]; d12 += dq[0]; d21 -= dq[0]; d01 += dq[2]; d10 += dq[2]; d20 += dq[3]; d02 += dq[3];
-                d00 += dt; d11 -= dt; d22 -= dt; break;
-        case 1: dt += dq[2]; d20 += dq[0]; d02 -= dq[0]; d01 += dq[1]; d10 += dq[1]; d12 += dq[3]; d21 += dq[3];
-                d00 -= dt; d11 += dt; d22 -= dt; break;
-        case 2: dt += dq[3]; d01 += dq[0]; d10 -= dq[0]; d20 += dq[1]; d02 += dq[1]; d12 += dq[2]; d21 += dq[2];
-                d00 -= dt; d11 -= dt; d22 += dt; break;
-        default: dt += dq[0]; d12 += dq[1]; d21 -= dq[1]; d20 += dq[2]; d02 -= dq[2]; d01 += dq[3]; d10 -= dq[3];
-                d00 += dt; d11 += dt; d22 += dt; break;
-    }
-    dr[0] = d00; dr[1] = d10; dr[2] = d20; dr[3] = d01; dr[4] = d11; dr[5] = d21; dr[6] = d02; dr[7] = d12; dr[8] = d22;
-}
-
-// limb weight of 2-D joint j: {4, 5, 18, 19} -> l, {7, 8, 20, 21} -> l^2
-__device__ __forceinline__ float limb_weight(int j, float l, float l2) {
-    if (j == 4 || j == 5 || j == 18 || j == 19) return l;
-    if (j == 7 || j == 8 || j == 20 || j == 21) return l2;
-    return 1.f;
-}
 
 // the four k segments of thread t's output, in order
 __device__ __forceinline__ float seg_sum(const float* sp, int o) { return ((sp[o] + sp[64 + o]) + sp[128 + o]) + sp[192 + o]; }
@@ -279,6 +212,8 @@ __global__ void __launch_bounds__(LT) real_main_kernel(const RealArgs a) {
         }
         if (a.g_depth[v]) a.g_depth[v][o] = g;
     }
+    // the keypoint tree: block_reduce<1>'s order, written out because sred[t] is stored above, ahead of the betas and depth work,
+    // and moving that store down to the call changes the kernel's code
     __syncthreads();
     for (int h = LT / 2; h > 0; h >>= 1) {
         if (t < h) sred[t] += sred[t + h];
@@ -311,15 +246,7 @@ __global__ void __launch_bounds__(LT) real_combine_kernel(const RealCombineArgs 
                 const float x = a.part[((size_t)v * a.B + b) * R_COUNT + k];
                 if (v == 0) acc[k] += x; else acc[R_COUNT + k] += x;
             }
-#pragma unroll
-    for (int k = 0; k < NV; ++k) s[k * LT + t] = acc[k];
-    __syncthreads();
-    for (int h = LT / 2; h > 0; h >>= 1) {
-        if (t < h)
-#pragma unroll
-            for (int k = 0; k < NV; ++k) s[k * LT + t] += s[k * LT + t + h];
-        __syncthreads();
-    }
+    block_reduce<NV>(s, acc);
     if (t != 0) return;
     const bool two = a.nviews == 2;
     auto S = [&](int v, int k) { return s[(v * R_COUNT + k) * LT]; };

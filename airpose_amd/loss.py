@@ -9,10 +9,10 @@ two launches (and one copy of the loss into storage of its own) instead of about
 import ctypes
 
 import torch
-from torch.autograd.function import once_differentiable
 
 from . import _native as N
 from . import _native_grad as G
+from . import _seeded_loss as S
 
 KINDS = ("twoview", "singleview", "hmr", "muhmr")
 # include/airpose_grad.h: APG_LOSS_CROSS_*
@@ -50,18 +50,8 @@ PRED_NAMES = ("trans", "rotmat", "betas", "joints", "verts", "j2d", "cam")
 
 
 def _pred(t, dev, shape, name):
-    """fp32, contiguous, on dev, of `shape` (None = any extent); anything else is refused by name"""
-    if not torch.is_tensor(t):
-        raise RuntimeError("TrainingLoss: %s must be a tensor, got %s" % (name, type(t).__name__))
-    if t.device != dev:
-        raise RuntimeError("TrainingLoss: %s lives on %s, the predictions on %s" % (name, t.device, dev))
-    if t.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, t.shape)):
-        raise RuntimeError("TrainingLoss: %s must be %s, got %s" % (name, tuple("*" if s is None else s for s in shape), tuple(t.shape)))
-    if t.dtype != torch.float32:
-        if not t.is_floating_point():
-            raise RuntimeError("TrainingLoss: %s must be a floating-point tensor, got %s" % (name, t.dtype))
-        t = t.float()
-    return t.contiguous()
+    """fp32 (another floating-point type is cast), contiguous, on dev, of `shape`; anything else is refused by name"""
+    return S.check_tensor("TrainingLoss", t, dev, shape, name, cast=True)
 
 
 def _joints_vertices(out, name):
@@ -73,48 +63,7 @@ def _joints_vertices(out, name):
     raise RuntimeError("TrainingLoss: %s must have .joints and .vertices, or be a (joints, vertices) pair" % name)
 
 
-class _Loss(torch.autograd.Function):
-    """(cfg, gt table, 7 predictions per view) -> (the 0-d loss in storage of its own, the (9,) terms: not differentiable)"""
-
-    @staticmethod
-    def forward(ctx, cfg, gts, *preds):
-        nviews, cross, B, J, Jg, V, weights, dev = cfg["nviews"], cfg["cross"], cfg["B"], cfg["J"], cfg["Jg"], cfg["V"], cfg["weights"], cfg["dev"]
-        # (needs_input_grad follows requires_grad alone; under no_grad nothing will call backward, so nothing is asked for)
-        need = ctx.needs_input_grad[2:] if cfg["grad"] else (False,) * len(preds)
-        # every seed is a slice of ONE flat buffer (each slice starts on a 16-byte boundary), so that backward scales them in one launch
-        offs, total = [], 0
-        for k, p in enumerate(preds):
-            offs.append(total if (p is not None and need[k]) else None)
-            if offs[-1] is not None:
-                total += (p.numel() + 3) // 4 * 4
-        flat = torch.empty(total, device=dev, dtype=torch.float32) if total else None
-        grads = [None if o is None else flat[o:o + p.numel()].view(p.shape) for o, p in zip(offs, preds)]
-        terms = torch.empty(len(TERM_NAMES), device=dev, dtype=torch.float32)
-        L = G.lib()
-        nbytes = L.apg_loss_workspace_bytes(B, V)
-        if nbytes < 0:
-            raise RuntimeError("TrainingLoss: no workspace for B = %d, V = %d" % (B, V))
-        ws = torch.empty((nbytes + 3) // 4, device=dev, dtype=torch.float32)
-        w = (ctypes.c_float * len(weights))(*weights)
-        with torch.cuda.device(dev):
-            G.check(L.apg_loss_fwd_bwd(nviews, cross, B, J, Jg, V, w, G.ptrs(preds), G.ptrs(gts), N.dptr(terms),
-                                       G.ptrs(grads) if total else None,      # all NULL: forward only
-                                       N.dptr(ws), nbytes, N.stream_ptr(dev)), "apg_loss_fwd_bwd")
-        ctx.flat, ctx.offs, ctx.shapes = flat, offs, [None if p is None else p.shape for p in preds]     # this call's own buffer
-        loss = terms[0].clone()                                  # its own element: in-place work on terms cannot reach the loss
-        ctx.mark_non_differentiable(terms)
-        return loss, terms
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g, _g_terms):
-        if ctx.flat is None:
-            return (None, None) + (None,) * len(ctx.offs)
-        scaled = ctx.flat * g                                    # the padding between slices is never read
-        return (None, None) + tuple(None if o is None else scaled[o:o + s.numel()].view(s) for o, s in zip(ctx.offs, ctx.shapes))
-
-
-class TrainingLoss(torch.nn.Module):
+class TrainingLoss(S.SeededLossModule):
     """get_loss of one of the four reference trainers on libairpose_grad.so.  No parameters.
 
     kind: "twoview", "singleview", "hmr" or "muhmr"; **weights: the reference's hparams names (WEIGHT_NAMES), defaulting to that
@@ -131,30 +80,17 @@ class TrainingLoss(torch.nn.Module):
     (absent terms 0); self.losses(terms) makes the reference's `losses` dict with one host copy.
     """
 
-    def __init__(self, kind, **weights):
-        super().__init__()
-        if kind not in KINDS:
-            raise ValueError("TrainingLoss: kind must be one of %s, got %r" % (", ".join(KINDS), kind))
-        unknown = sorted(set(weights) - set(DEFAULTS[kind]))
-        if unknown:
-            raise ValueError("TrainingLoss: unknown weight(s) %s; the names are %s" % (unknown, sorted(DEFAULTS[kind])))
-        self.kind = kind
-        self.weights = dict(DEFAULTS[kind])
-        self.weights.update({k: float(v) for k, v in weights.items()})
+    _owner, _kinds, _defaults, _term_names = "TrainingLoss", KINDS, DEFAULTS, TERM_NAMES
+    # what losses() leaves out (its one device-to-host copy stands for the reference's eight)
+    _skip = {k: ("loss_cam",) if _HAS_TRANS[k] else ("loss_cam", "loss_regr_trans") for k in KINDS}
 
-    def extra_repr(self):
-        return "kind=%r, %s" % (self.kind, ", ".join("%s=%g" % kv for kv in sorted(self.weights.items())))
+    def __init__(self, kind, **weights):
+        super().__init__(kind, weights, "TrainingLoss")
 
     def weight_vector(self):
         """the 11 floats of apg_loss_fwd_bwd's weights"""
         w = [CAM_COEFFICIENT if k == 7 else LOSS_SCALE if k == 10 else self.weights[n] for k, n in enumerate(WEIGHT_NAMES)]
         return w
-
-    def losses(self, terms):
-        """the reference's `losses` dict of this kind from forward's terms: ONE device-to-host copy (the reference does eight)"""
-        host = terms.detach().cpu().tolist()
-        skip = ("loss_cam",) if _HAS_TRANS[self.kind] else ("loss_cam", "loss_regr_trans")
-        return {n: v for n, v in zip(TERM_NAMES, host) if n not in skip}
 
     def _views(self, args):
         """-> per view a dict of PRED_NAMES (absent entries None), from the kind's positional arguments"""
@@ -179,9 +115,7 @@ class TrainingLoss(torch.nn.Module):
         nviews = len(views)
         crop = "" if _HAS_TRANS[self.kind] else "_crop"              # hmr / muhmr compare in the crop's pixels
         first = views[0]["rotmat"]
-        if not torch.is_tensor(first) or not first.is_cuda:
-            raise RuntimeError("TrainingLoss: predictions must be CUDA (ROCm) tensors; there is no CPU path")
-        dev = first.device
+        dev = self._device_of(first)
         B = first.shape[0]
         preds = []
         J = V = None
@@ -215,6 +149,17 @@ class TrainingLoss(torch.nn.Module):
                     gt("smpltrans_rel%d" % v, (B, 3)) if _HAS_TRANS[self.kind] else None]
         if Jg < 22:
             raise RuntimeError("TrainingLoss: input_batch['smpl_joints'] must have at least 22 joints, got %d" % Jg)
-        cfg = dict(nviews=nviews, cross=_CROSS[self.kind], B=B, J=J, Jg=Jg, V=V, weights=self.weight_vector(), dev=dev,
-                   grad=torch.is_grad_enabled())
-        return _Loss.apply(cfg, gts, *preds)
+        cross, weights = _CROSS[self.kind], self.weight_vector()
+
+        def launch(terms, grads):
+            L = G.lib()
+            nbytes = L.apg_loss_workspace_bytes(B, V)
+            if nbytes < 0:
+                raise RuntimeError("TrainingLoss: no workspace for B = %d, V = %d" % (B, V))
+            ws = torch.empty((nbytes + 3) // 4, device=dev, dtype=torch.float32)
+            w = (ctypes.c_float * len(weights))(*weights)
+            G.check(L.apg_loss_fwd_bwd(nviews, cross, B, J, Jg, V, w, G.ptrs(preds), G.ptrs(gts), N.dptr(terms),
+                                       G.ptrs(grads) if grads else None,      # all NULL: forward only
+                                       N.dptr(ws), nbytes, N.stream_ptr(dev)), "apg_loss_fwd_bwd")
+
+        return S.SeededLoss.apply(dev, len(TERM_NAMES), torch.is_grad_enabled(), launch, *preds)

@@ -17,10 +17,10 @@ LeakyReLU, folded here once in fp64 (fold_encoder) and packed once on the device
 import ctypes
 
 import torch
-from torch.autograd.function import once_differentiable
 
 from . import _native as N
 from . import _native_grad as G
+from . import _seeded_loss as S
 
 KINDS = ("twoview", "twoview_sep", "hmr", "hmr_camswap", "spin")
 CROSS_POSE, CROSS_BETAS = 4, 8                                # include/airpose_grad.h: APG_LOSS_CROSS_*
@@ -102,61 +102,11 @@ def fold_encoder(state_dict):
 
 
 def _pred(t, dev, shape, name):
-    """fp32, contiguous, on dev, of `shape` (None = any extent); anything else is refused by name"""
-    if not torch.is_tensor(t):
-        raise RuntimeError("RealDataLoss: %s must be a tensor, got %s" % (name, type(t).__name__))
-    if t.device != dev:
-        raise RuntimeError("RealDataLoss: %s lives on %s, the predictions on %s" % (name, t.device, dev))
-    if t.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, t.shape)):
-        raise RuntimeError("RealDataLoss: %s must be %s, got %s" % (name, tuple("*" if s is None else s for s in shape), tuple(t.shape)))
-    if t.dtype != torch.float32:
-        raise RuntimeError("RealDataLoss: %s must be float32, got %s" % (name, t.dtype))
-    return t.contiguous()
+    """fp32 (nothing is cast), contiguous, on dev, of `shape` (None = any extent); anything else is refused by name"""
+    return S.check_tensor("RealDataLoss", t, dev, shape, name, cast=False)
 
 
-class _RealLoss(torch.autograd.Function):
-    """(cfg, gt table, 4 predictions per view) -> (the 0-d loss in storage of its own, the (6,) terms: not differentiable)"""
-
-    @staticmethod
-    def forward(ctx, cfg, gts, *preds):
-        dev, B = cfg["dev"], cfg["B"]
-        # (needs_input_grad follows requires_grad alone; under no_grad nothing will call backward, so nothing is asked for)
-        need = ctx.needs_input_grad[2:] if cfg["grad"] else (False,) * len(preds)
-        # every seed is a slice of ONE flat buffer, so that backward scales them in one launch
-        offs, total = [], 0
-        for k, p in enumerate(preds):
-            offs.append(total if need[k] else None)
-            if need[k]:
-                total += (p.numel() + 3) // 4 * 4
-        flat = torch.empty(total, device=dev, dtype=torch.float32) if total else None
-        grads = [None if o is None else flat[o:o + p.numel()].view(p.shape) for o, p in zip(offs, preds)]
-        terms = torch.empty(len(TERM_NAMES), device=dev, dtype=torch.float32)
-        L = G.lib()
-        nbytes = L.apg_real_loss_workspace_bytes(B)
-        if nbytes < 0:
-            raise RuntimeError("RealDataLoss: no workspace for B = %d" % B)
-        ws = torch.empty((nbytes + 3) // 4, device=dev, dtype=torch.float32)
-        w = (ctypes.c_float * len(cfg["weights"]))(*cfg["weights"])
-        with torch.cuda.device(dev):
-            G.check(L.apg_real_loss_fwd_bwd(cfg["nviews"], cfg["cross"], B, cfg["J"], cfg["Jg"], cfg["col"], cfg["gain"], w,
-                                            N.dptr(cfg["encoder"]), G.ptrs(preds), G.ptrs(gts), N.dptr(terms),
-                                            G.ptrs(grads) if total else None,      # all NULL: forward only
-                                            N.dptr(ws), nbytes, N.stream_ptr(dev)), "apg_real_loss_fwd_bwd")
-        ctx.flat, ctx.offs, ctx.shapes = flat, offs, [p.shape for p in preds]
-        loss = terms[0].clone()                                  # its own element: in-place work on terms cannot reach the loss
-        ctx.mark_non_differentiable(terms)
-        return loss, terms
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g, _g_terms):
-        if ctx.flat is None:
-            return (None, None) + (None,) * len(ctx.offs)
-        scaled = ctx.flat * g                                    # the padding between slices is never read
-        return (None, None) + tuple(None if o is None else scaled[o:o + s.numel()].view(s) for o, s in zip(ctx.offs, ctx.shapes))
-
-
-class RealDataLoss(torch.nn.Module):
+class RealDataLoss(S.SeededLossModule):
     """get_loss of one of the five copenet_real trainers on libairpose_grad.so.  No parameters (the encoder is a frozen buffer).
 
     kind: "twoview", "twoview_sep", "hmr", "hmr_camswap" or "spin".
@@ -177,39 +127,20 @@ class RealDataLoss(torch.nn.Module):
     self.losses(terms) makes the reference's `losses` dict with one host copy.
     """
 
+    _owner, _kinds, _defaults, _required, _term_names = "RealDataLoss", KINDS, DEFAULTS, REQUIRED, TERM_NAMES
+    _skip = {k: ("loss_depth",) if _TWO[k] else ("loss_depth", "loss_regr_pose") for k in KINDS}
+
     def __init__(self, kind, vposer, **weights):
-        super().__init__()
-        if kind not in KINDS:
-            raise ValueError("RealDataLoss: kind must be one of %s, got %r" % (", ".join(KINDS), kind))
-        names = set(DEFAULTS[kind]) | set(REQUIRED[kind])
-        unknown = sorted(set(weights) - names)
-        if unknown:
-            raise ValueError("RealDataLoss(%s): unknown weight(s) %s; the names are %s" % (kind, unknown, sorted(names)))
-        missing = [n for n in REQUIRED[kind] if n not in weights]
-        if missing:
-            raise ValueError("RealDataLoss(%s): %s must be given: the reference trainer reads them and declares no default"
-                             % (kind, ", ".join(missing)))
-        self.kind = kind
-        self.weights = dict(DEFAULTS[kind])
-        self.weights.update({k: float(v) for k, v in weights.items()})
+        super().__init__(kind, weights, "RealDataLoss(%s)" % kind)
         W1, b1, W2, b2 = fold_encoder(vposer)                    # fp64, once
         self._folded = [t.float().contiguous() for t in (W1, b1, W2, b2)]
         self._packed = None
-
-    def extra_repr(self):
-        return "kind=%r, %s" % (self.kind, ", ".join("%s=%g" % kv for kv in sorted(self.weights.items())))
 
     def weight_vector(self):
         """the 6 floats of apg_real_loss_fwd_bwd's weights"""
         d = dict(pose_loss_weight=0.0, limbs2d_loss_weight=1.0)  # what a kind without the term / the limb weights amounts to
         d.update(self.weights)
         return [LOSS_SCALE if n is None else d[n] for n in WEIGHT_NAMES]
-
-    def losses(self, terms):
-        """the reference's `losses` dict of this kind from forward's terms: ONE device-to-host copy"""
-        host = terms.detach().cpu().tolist()
-        skip = ("loss_depth",) if _TWO[self.kind] else ("loss_depth", "loss_regr_pose")
-        return {n: v for n, v in zip(TERM_NAMES, host) if n not in skip}
 
     def encoder(self, dev):
         """the packed encoder table on dev (packed on first use, again if the device changes)"""
@@ -241,9 +172,7 @@ class RealDataLoss(torch.nn.Module):
         views = self._views(args)
         nviews = len(views)
         first = views[0]["rotmat"]
-        if not torch.is_tensor(first) or not first.is_cuda:
-            raise RuntimeError("RealDataLoss: predictions must be CUDA (ROCm) tensors; there is no CPU path")
-        dev = first.device
+        dev = self._device_of(first)
         B = first.shape[0]
         j2d0 = views[0]["j2d"]
         if not torch.is_tensor(j2d0) or j2d0.dim() != 3:
@@ -277,6 +206,17 @@ class RealDataLoss(torch.nn.Module):
         if Jg < 22:
             raise RuntimeError("RealDataLoss: the 2-D ground truth must have at least 22 joints, got %d" % Jg)
         col, gain = _DEPTH[self.kind]
-        cfg = dict(nviews=nviews, cross=(CROSS_POSE | CROSS_BETAS) if _TWO[self.kind] else 0, B=B, J=J, Jg=Jg, col=col, gain=gain,
-                   weights=self.weight_vector(), encoder=self.encoder(dev), dev=dev, grad=torch.is_grad_enabled())
-        return _RealLoss.apply(cfg, gts, *preds)
+        cross, weights, encoder = (CROSS_POSE | CROSS_BETAS) if _TWO[self.kind] else 0, self.weight_vector(), self.encoder(dev)
+
+        def launch(terms, grads):
+            L = G.lib()
+            nbytes = L.apg_real_loss_workspace_bytes(B)
+            if nbytes < 0:
+                raise RuntimeError("RealDataLoss: no workspace for B = %d" % B)
+            ws = torch.empty((nbytes + 3) // 4, device=dev, dtype=torch.float32)
+            w = (ctypes.c_float * len(weights))(*weights)
+            G.check(L.apg_real_loss_fwd_bwd(nviews, cross, B, J, Jg, col, gain, w, N.dptr(encoder), G.ptrs(preds), G.ptrs(gts),
+                                            N.dptr(terms), G.ptrs(grads) if grads else None,      # all NULL: forward only
+                                            N.dptr(ws), nbytes, N.stream_ptr(dev)), "apg_real_loss_fwd_bwd")
+
+        return S.SeededLoss.apply(dev, len(TERM_NAMES), torch.is_grad_enabled(), launch, *preds)

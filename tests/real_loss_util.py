@@ -1,5 +1,5 @@
-"""Shared by the test_real_loss_* files: a seeded VPoser encoder under the published state-dict keys (and the dev / packed fixtures
-of the GPU tests), the literal layer chain, the
+"""Shared by the test_real_loss_* files: a seeded VPoser encoder under the published state-dict keys (and the packed fixture
+of the GPU tests, on loss_util's dev), the literal layer chain, the
 copenet_real trainers' get_loss restated from torch ops (any dtype, any device; gradients by autograd), and seeded cases whose
 rotations keep clear of the axis-angle conversion's branch boundaries and singularities."""
 import ctypes
@@ -112,12 +112,6 @@ def folded(sd=SD, bn_eps=None):
         return loss_real.fold_encoder(sd)
     finally:
         loss_real.BN_EPS = keep
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return torch.device("cuda", 0)
 
 
 @pytest.fixture(scope="module")

@@ -52,10 +52,11 @@ import ctypes
 import pytest
 import torch
 
+from loss_util import GUARD, LT, U32, Buf, bit_equal, dev, run_twice  # noqa: F401  (dev is a fixture)
+from loss_util import place as _place, strided_sum as _strided_sum, tree as _tree
 from test_stem_pool_fp64 import evaluate
 
-U32 = 2.0 ** -24
-LT, EPB, SB, NJ = 256, 4096, 4, 22                       # loss_grad.hip: LT, LOSS_EPB, LOSS_SB, NJ
+EPB, SB, NJ = 4096, 4, 22                                # loss_grad.hip: LOSS_EPB, LOSS_SB; loss_common.inc: NJ
 PRED = ("trans", "rotmat", "betas", "joints", "verts", "j2d", "cam")
 TERMS = ("loss", "trans", "keypoints", "keypoints_3d", "shape", "rootrot", "pose", "betas", "cam")
 W_NAMES = ("trans", "kp2d", "kp3d", "shape", "root", "pose", "beta", "cam", "limbs3d", "limbstheta", "scale")
@@ -232,28 +233,6 @@ def verify(c, ref, terms, grads, what, ratios=None, skip=()):
 
 
 # ------------------------------------------------------------------------------------------------ fp32 emulation in the kernel's order
-def _tree(s):
-    s = s.clone()
-    h = LT // 2
-    while h:
-        s[..., :h] = s[..., :h] + s[..., h:2 * h]
-        h //= 2
-    return s[..., 0]
-
-
-def _strided_sum(vals):
-    """a workgroup's sum of a list in loop order: thread t adds elements t, t + 256, .. in order, then the tree"""
-    n = vals.numel()
-    ch = max(1, -(-n // LT))
-    x = torch.zeros(ch * LT, dtype=vals.dtype)
-    x[:n] = vals
-    x = x.view(ch, LT)
-    acc = torch.zeros(LT, dtype=vals.dtype)
-    for i in range(ch):
-        acc = acc + x[i]
-    return _tree(acc)
-
-
 def _stream_sum(sq):
     """the vertex stream's sum of the flat squares: per workgroup 256 threads x (4 quads x 4) in order, tree; partials strided + tree"""
     n = sq.numel()
@@ -438,35 +417,6 @@ def test_cpu_aliased_views_have_no_cross_share():
 
 
 # ------------------------------------------------------------------------------------------------ the C ABI on the GPU
-GUARD = 512
-
-
-class Buf(object):
-    """n floats in a NaN-filled device buffer with NaN guard bands, `off` floats past a 16-byte boundary"""
-
-    def __init__(self, dev, n, off=0):
-        self.n, self.off = n, off
-        self.buf = torch.full((n + 2 * GUARD + 4,), float("nan"), dtype=torch.float32, device=dev)
-        assert self.buf.data_ptr() % 16 == 0
-        self.out = self.buf[GUARD + off:GUARD + off + n]
-
-    def values(self, shape, what):
-        lo, hi = GUARD + self.off, GUARD + self.off + self.n
-        assert torch.isnan(self.buf[:lo]).all() and torch.isnan(self.buf[hi:]).all(), (what, "a guard band was written")
-        assert not torch.isnan(self.out).any(), (what, "%d elements never written" % int(torch.isnan(self.out).sum()))
-        return self.out.view(*shape).cpu()
-
-
-def _place(t, dev, off=0):
-    """a device copy of t starting `off` floats past a 16-byte boundary"""
-    if t is None:
-        return None
-    buf = torch.empty(t.numel() + 4, dtype=torch.float32, device=dev)
-    out = buf[off:off + t.numel()]
-    out.copy_(t.reshape(-1))
-    return out
-
-
 def run(c, dev, want=None, voff=(0, 0, 0, 0, 0), aliased=False):
     """one apg_loss_fwd_bwd call -> (terms (9,) cpu, grads per view (cpu tensors / None)).  want: set of (view, name) gradients to ask
     for (None = all that exist; empty = the grads table itself NULL).  voff: float offsets of verts0, verts1, gt_verts, g_verts0,
@@ -508,34 +458,14 @@ def run(c, dev, want=None, voff=(0, 0, 0, 0, 0), aliased=False):
     return terms.values((len(TERMS),), "terms"), grads
 
 
-def bit_equal(a, b):
-    ta, ga = a
-    tb, gb = b
-    if not torch.equal(ta.view(torch.int32), tb.view(torch.int32)):
-        return False
-    for x, y in zip(ga, gb):
-        for n in PRED:
-            if (x[n] is None) != (y[n] is None) or (x[n] is not None and not torch.equal(x[n].view(torch.int32), y[n].view(torch.int32))):
-                return False
-    return True
-
-
 def run_twice_and_verify(c, dev, what, **kw):
-    got = run(c, dev, **kw)
-    again = run(c, dev, **kw)
-    assert bit_equal(got, again), (what, "two runs differ")
+    got = run_twice(lambda: run(c, dev, **kw), what)
     ref = reference(c)
     ratios = {}
     fails = verify(c, ref, got[0], got[1], what, ratios)
     print("%-44s worst err / bound: %s" % (what, "  ".join("%s %.3f" % kv for kv in ratios.items())))
     assert not fails, fails
     return got, ref
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return torch.device("cuda", 0)
 
 
 GRID = [(1, 1, 22, 23), (2, 3, 23, 22), (3, 24, 127, 144), (5, 1025, 127, 22)]

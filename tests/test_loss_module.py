@@ -12,17 +12,12 @@ import pytest
 import torch
 
 from conftest import rel_err
+from loss_util import dev  # noqa: F401  (a fixture)
 from test_head_grad import PNAMES, TOL_GRAD, _inputs, _net, _sd64
 from test_loss_fp64 import KINDS, PRED, WEIGHTS, loss_terms, make_case, reference, run, verify
 
 pytestmark = pytest.mark.gpu
 KIND_NAMES = sorted(KINDS)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    return torch.device("cuda", 0)
 
 
 def _batch(c, dev):

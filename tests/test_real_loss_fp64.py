@@ -51,12 +51,12 @@ import pytest
 import torch
 
 import grad_shapes_util as GS
-from real_loss_util import (FORMS, LIMB1, LIMB2, NJ, NR, NZ, PRED, SD, SD64, TERMS, X_BETAS, X_POSE, axis_angle, branch_of, dev,  # noqa: F401
-                            folded, limb_vec, loss_terms, make_case, packed)  # noqa: F401  (dev and packed are fixtures)
-from test_loss_fp64 import GUARD, U32, Buf, _place, _strided_sum
+from loss_util import GUARD, LT, U32, Buf, bit_equal, dev, run_twice  # noqa: F401  (dev is a fixture)
+from loss_util import place as _place, strided_sum as _strided_sum
+from real_loss_util import (FORMS, LIMB1, LIMB2, NJ, NR, NZ, PRED, SD, SD64, TERMS, X_BETAS, X_POSE, axis_angle, branch_of,
+                            folded, limb_vec, loss_terms, make_case, packed)  # noqa: F401  (packed is a fixture)
 from test_stem_pool_fp64 import evaluate
 
-LT = 256                                                      # loss_real_grad.hip: LT
 SEG = 128
 MUTATIONS = ("dropped_confidence", "limb_sets_shifted", "softplus_as_exp", "eps_dropped", "bn_wrong_eps", "vposer_overwrites_pose",
              "bn_unfolded")
@@ -414,20 +414,8 @@ def run(c, dev, packed, want=None, off=0):
     return terms.values((len(TERMS),), "terms"), grads
 
 
-def bit_equal(a, b):
-    if not torch.equal(a[0].view(torch.int32), b[0].view(torch.int32)):
-        return False
-    for x, y in zip(a[1], b[1]):
-        for n in PRED:
-            if (x[n] is None) != (y[n] is None) or (x[n] is not None and not torch.equal(x[n].view(torch.int32), y[n].view(torch.int32))):
-                return False
-    return True
-
-
 def run_twice_and_verify(c, dev, packed, what, **kw):
-    got = run(c, dev, packed, **kw)
-    again = run(c, dev, packed, **kw)
-    assert bit_equal(got, again), (what, "two runs differ")
+    got = run_twice(lambda: run(c, dev, packed, **kw), what)
     ratios = {}
     fails = verify(c, reference(c), got[0], got[1], what, ratios)
     show(what, ratios)

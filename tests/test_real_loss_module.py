@@ -12,7 +12,8 @@ import pytest
 import torch
 
 from conftest import rel_err
-from real_loss_util import NJ, NZ, PRED, SD, SD64, WEIGHTS, dev, draw_rot6d, loss_terms, make_case, packed  # noqa: F401  (dev, packed: fixtures)
+from loss_util import dev  # noqa: F401  (a fixture)
+from real_loss_util import NJ, NZ, PRED, SD, SD64, WEIGHTS, draw_rot6d, loss_terms, make_case, packed  # noqa: F401  (packed: a fixture)
 from test_head_grad import TOL_GRAD
 from test_optim_module import Drift
 from test_real_loss_fp64 import reference, run, verify
