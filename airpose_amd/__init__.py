@@ -10,6 +10,7 @@ Public mirrors of the reference interfaces:
   FusedAdam (optim.py)                 <- torch.optim.Adam(..., amsgrad=True) of the trainers' configure_optimizers
   EvalMetrics (eval_metrics.py)        <- test_epoch_end of the four trainers: MPJPE, MPE, angle error
   Renderer (renderer.py)               <- utils/renderer.py Renderer: visualize_tb of the trainers' summaries(), without pyrender
+  MeshMetrics (mesh_metrics.py)        <- no counterpart in the reference: MPJPE / PVE, absolute, root- and Procrustes-aligned
 The compute lives in libairpose_hip.so (include/airpose_hip.h); nothing here falls back to CPU.
 """
 __version__ = "0.1.0"
@@ -32,4 +33,7 @@ def __getattr__(name):
     if name == "Renderer":                                                # likewise (renderer.py)
         from .renderer import Renderer
         return Renderer
+    if name == "MeshMetrics":                                             # likewise (mesh_metrics.py)
+        from .mesh_metrics import MeshMetrics
+        return MeshMetrics
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

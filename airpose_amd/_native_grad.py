@@ -79,6 +79,10 @@ SIGNATURES = {
     # the mesh overlay renderer (render.hip)
     "apg_render_workspace_bytes": (_i64, [_i] * 5),
     "apg_render_overlay": (_i, [_i] * 5 + [_vp] * 4 + [_i, _vp, _vp] + [_f] * 6 + [_vp] + [_f] * 5 + [_vp] * 4 + [_i64, _vp]),
+    # the mesh metrics (eval_align.hip)
+    "apg_align_workspace_bytes": (_i64, [_i, _i, _i]),
+    "apg_align_acc_doubles": (_i64, []),
+    "apg_align_update": (_i, [_i, _i, _i] + [_i64] * 4 + [_vpp] + [_vp] * 4 + [_i64, _vp]),
 }
 PRECISIONS = {"fp32": 0, "bf16": 1}          # include/airpose_grad.h: APG_PREC_*
 

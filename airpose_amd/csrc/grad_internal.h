@@ -1,5 +1,5 @@
 // Internal helpers shared by the sources of libairpose_grad.so (head_mlp.hip, head_grad.hip, head_local_grad.hip, geom_grad.hip,
-// trunk_grad.hip, trunk_grad_bf16.hip, loss_grad.hip, loss_real_grad.hip, optim.hip, eval_metrics.hip, render.hip).
+// trunk_grad.hip, trunk_grad_bf16.hip, loss_grad.hip, loss_real_grad.hip, optim.hip, eval_metrics.hip, render.hip, eval_align.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

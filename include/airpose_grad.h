@@ -535,6 +535,49 @@ int apg_render_overlay(int n, int V, int F, int H, int W, const float* vertices,
                        float diffuse, float* out_rgb, float* out_depth, int* out_face, void* workspace, int64_t workspace_bytes,
                        void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mesh metrics (eval_align.hip): the error between a predicted and a ground-truth point set as it stands, after root alignment and
+ * after Procrustes alignment -- MPJPE / PVE, their root-aligned forms and PA-MPJPE / PA-PVE, the numbers mesh-recovery papers
+ * tabulate.  The reference computes none of them.  Additive under ABI 2: a binding tells a library that has it by looking up
+ * apg_align_update.
+ *
+ * For a prediction P and a ground truth Q, (B, N, 3) fp32 each, per sample, all sums over the N points:
+ *   abs  = mean_i |p_i - q_i|
+ *   root = mean_i |(p_i - r_p) - (q_i - r_q)| with the root points r_p, r_q given separately (3 floats per sample each)
+ *   pa   = mean_i |s R (p_i - mu_p) + mu_q - q_i| with mu the sets' means and (s, R) the least-squares similarity (Umeyama / Kabsch
+ *          with the reflection fix): K = sum (q_i - mu_q)(p_i - mu_p)^T = U S V^T, D = diag(1, 1, sign(det U det V)), R = U D V^T
+ *          (det R = +1 always), s = tr(S D) / sum |p_i - mu_p|^2.  If sum |p_i - mu_p|^2 = 0 (N = 1 included): s = 0, R = I and the
+ *          error is |mu_q - q_i|.  For collinear points (rank K < 2) the rotation is not unique: the outputs are finite and det R = +1.
+ * The moments and the 3 x 3 problem are taken in fp64 about a pivot (point 0 of each set), so a body of 0.5 m extent 10 m from the
+ * camera keeps its covariance; each residual is formed in fp64, rounded to float once per component, its norm taken in fp32.
+ *
+ * apg_align_update, one call per batch and point set:
+ *   pred_stride, gt_stride: floats from one sample to the next, at least 3 N (an array may hold more than N points per sample).
+ *   per_view: HOST array of APG_ALIGN_PER_VIEW * views device pointers; per view pred, gt, pred_root, gt_root.  The roots may be
+ *     NULL, only as a pair: root is then neither computed nor counted for that view.  pred_root_stride, gt_root_stride: floats from
+ *     one sample's root to the next, at least 3 (read only where roots are given).
+ *   err (views, B, 3): optional per-sample abs, root, pa (root = 0 where no roots are given).  transform (views, B, 13): optional
+ *     per-sample s, R row-major (9), t = mu_q - s R mu_p (3), so that s R p + t lies on q.  Each written in full.
+ *   acc: apg_align_acc_doubles() = 2 * APG_ALIGN_ACC_PER_VIEW doubles (device, 8-byte aligned), ADDED to; the caller zeroes it to
+ *     start or reset.  Per view: [0] samples, [1] sum of abs, [2] sum of root, [3] sum of pa, [4] samples that had roots.  The second
+ *     view's block is untouched with views = 1.  The batch means are acc[1] / acc[0], acc[2] / acc[4], acc[3] / acc[0].
+ *   workspace: at least apg_align_workspace_bytes(B, views, N) bytes (negative outside the limits below), 8-byte aligned, else
+ *     APG_ENOMEM; the samples' means.  It carries nothing from call to call and needs no initialisation.
+ * All other data is fp32, 4-byte aligned, a sample's points contiguous.  Limits: 1 <= B <= 2^22, 1 <= N <= 2^24.
+ * Determinism: no atomics and no arrival counter; a workgroup owns one (view, sample) and sums in a fixed order in fp64 (thread,
+ * wave, workgroup), a second launch adds the samples' means in sample order in fp64 and adds the total to acc.  The partition depends
+ * on N alone, so every output is bit-identical from run to run.  Two launches, no host synchronisation.
+ * APG_EINVAL before any GPU call, the message naming the argument: B or N outside the limits, views outside {1, 2}, a stride below
+ * 3 N (roots: 3), a NULL per_view, pred, gt, acc or workspace, a root given by half, a pointer that is not 4-byte (acc, workspace:
+ * 8-byte) aligned. */
+#define APG_ALIGN_PER_VIEW 4
+#define APG_ALIGN_ACC_PER_VIEW 5
+int64_t apg_align_workspace_bytes(int B, int views, int N);
+int64_t apg_align_acc_doubles(void);
+int apg_align_update(int B, int views, int N, int64_t pred_stride, int64_t gt_stride, int64_t pred_root_stride,
+                     int64_t gt_root_stride, const void* const* per_view, float* err, float* transform, double* acc, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
