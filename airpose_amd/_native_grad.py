@@ -129,10 +129,20 @@ def ints(values):
     return (_c.c_int * len(values))(*values)
 
 
+def vp(t):
+    """a tensor's device pointer (None -> NULL)"""
+    return _c.c_void_p(None if t is None else t.data_ptr())
+
+
+def stream(device):
+    """the current stream of `device`, as the entry points take it"""
+    return _c.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
 def dropout_mask(seed, layer, rows, cols, p, device):
     """(rows, cols) uint8 on `device`: exactly the keep mask of (seed, layer) the head kernels apply (1 = kept)."""
     out = torch.empty(rows, cols, device=device, dtype=torch.uint8)
     with torch.cuda.device(device):
-        check(lib().apg_dropout_mask(int(seed), int(layer), int(rows), int(cols), float(p), _c.c_void_p(out.data_ptr()),
-                                     _c.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "apg_dropout_mask")
+        check(lib().apg_dropout_mask(int(seed), int(layer), int(rows), int(cols), float(p), vp(out), stream(device)),
+              "apg_dropout_mask")
     return out

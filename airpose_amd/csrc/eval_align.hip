@@ -20,7 +20,7 @@
 //       rounded to float once per component: d_abs = p - q, d_root = (p - r_p) - (q - r_q), d_pa = scale (R (p - mu_p)) + (mu_q - q);
 //       each norm is sqrtf(fmaf(d2, d2, fmaf(d1, d1, d0 * d0))) in fp32, added in fp64 in the order of phase 1.  The sample's three
 //       means (sum / N in fp64) go to the workspace, rounded to float to `err`.
-//   align_combine_kernel    one workgroup: the samples' means added in sample order, in fp64, then ONE add into the accumulator.
+//   metric_combine_kernel   (metric_common.inc) one workgroup: the samples' means added in sample order, in fp64, ONE add into the accumulator.
 //
 // A point is 12 bytes and a sample's base only 4-byte aligned, so a lane loads its point as three dwords (a wave covers 768
 // contiguous bytes).  pred == gt bit for bit gives d_abs = 0 and (with equal roots) d_root = 0 exactly.
@@ -58,14 +58,9 @@ struct AlignArgs {
     double* part;                                        // [view][sample][3]
 };
 
-struct AlignCombineArgs {
-    int B, views;
-    int has_root[2];
-    const double* part;
-    double* acc;
-};
+#include "metric_common.inc"
 
-__device__ __forceinline__ float norm3(float d0, float d1, float d2) { return sqrtf(fmaf(d2, d2, fmaf(d1, d1, d0 * d0))); }
+static_assert(2 * (3 + 1) <= COMBINE_NT && 3 + 1 <= ACC, "metric_combine_kernel: a thread per (view, sum) and one per view");
 
 // v[k] summed over the workgroup in a fixed order; every thread returns with the totals in tot[0 .. NV)
 template <int NT, int NV>
@@ -281,21 +276,8 @@ __global__ void __launch_bounds__(NT) align_main_kernel(const AlignArgs a) {
     }
 }
 
-// accumulator of one view: [0] samples, [1] sum of abs, [2] sum of root, [3] sum of pa, [4] samples that had roots
-__global__ void __launch_bounds__(64) align_combine_kernel(const AlignCombineArgs c) {
-    const int t = threadIdx.x;
-    if (t < c.views * 3) {
-        const int v = t / 3, k = t - v * 3;
-        if (k == 1 && !c.has_root[v]) return;
-        double sum = 0.0;
-        for (int b = 0; b < c.B; ++b) sum += c.part[((size_t)v * c.B + b) * 3 + k];     // samples in index order
-        c.acc[v * ACC + 1 + k] += sum;
-    } else if (t < c.views * 3 + c.views) {
-        const int v = t - c.views * 3;
-        c.acc[v * ACC] += (double)c.B;
-        if (c.has_root[v]) c.acc[v * ACC + 4] += (double)c.B;
-    }
-}
+// accumulator of one view: [0] samples, [1] sum of abs, [2] sum of root, [3] sum of pa, [4] samples that had roots:
+// metric_combine_kernel over the samples' means; the root sum of a view without roots is left alone
 
 constexpr int MAX_B = 1 << 22, MAX_N = 1 << 24;
 
@@ -314,44 +296,41 @@ int apg_align_update(int B, int views, int N, int64_t pred_stride, int64_t gt_st
                      int64_t gt_root_stride, const void* const* per_view, float* err, float* transform, double* acc, void* workspace,
                      int64_t workspace_bytes, void* stream) {
     const std::string f = "apg_align_update: ";
+    static const char* const name[APG_ALIGN_PER_VIEW] = {"pred", "gt", "pred_root", "gt_root"};
+    const MetricChecks m = {f, views, per_view, APG_ALIGN_PER_VIEW, 2, name, acc, workspace, workspace_bytes,
+                            apg_align_workspace_bytes(B, views, N), "apg_align_workspace_bytes"};
     if (B < 1 || B > MAX_B) return apg_fail(APG_EINVAL, f + "B must be in 1 .. " + std::to_string(MAX_B));
-    if (views != 1 && views != 2) return apg_fail(APG_EINVAL, f + "views must be 1 or 2");
+    if (int rc = m.views_ok()) return rc;
     if (N < 1 || N > MAX_N) return apg_fail(APG_EINVAL, f + "N must be in 1 .. " + std::to_string(MAX_N));
     if (pred_stride < 3 * (int64_t)N) return apg_fail(APG_EINVAL, f + "pred_stride must be at least 3 N floats");
     if (gt_stride < 3 * (int64_t)N) return apg_fail(APG_EINVAL, f + "gt_stride must be at least 3 N floats");
-    if (!per_view) return apg_fail(APG_EINVAL, f + "the per_view table is NULL");
-    if (!acc) return apg_fail(APG_EINVAL, f + "acc is NULL");
-    if (!workspace) return apg_fail(APG_EINVAL, f + "workspace is NULL");
-    static const char* const name[APG_ALIGN_PER_VIEW] = {"pred", "gt", "pred_root", "gt_root"};
+    if (int rc = m.table_ok()) return rc;
+    if (int rc = m.sinks_ok()) return rc;
     AlignArgs a = {};
-    AlignCombineArgs c = {};
+    CombineArgs c = {};
     for (int v = 0; v < views; ++v) {
         const void* const* q = per_view + v * APG_ALIGN_PER_VIEW;
         const std::string at = " of view " + std::to_string(v);
-        for (int k = 0; k < APG_ALIGN_PER_VIEW; ++k) {
-            if (k < 2 && !q[k]) return apg_fail(APG_EINVAL, f + name[k] + at + " is NULL");
-            if ((uintptr_t)q[k] & 3) return apg_fail(APG_EINVAL, f + name[k] + at + " is not 4-byte aligned");
-        }
+        if (int rc = m.view_ok(v)) return rc;
         if (q[2] && !q[3]) return apg_fail(APG_EINVAL, f + "pred_root" + at + " is given without gt_root");
         if (q[3] && !q[2]) return apg_fail(APG_EINVAL, f + "gt_root" + at + " is given without pred_root");
         if (q[2] && pred_root_stride < 3) return apg_fail(APG_EINVAL, f + "pred_root_stride must be at least 3 floats");
         if (q[2] && gt_root_stride < 3) return apg_fail(APG_EINVAL, f + "gt_root_stride must be at least 3 floats");
         a.pred[v] = (const float*)q[0], a.gt[v] = (const float*)q[1];
         a.pred_root[v] = (const float*)q[2], a.gt_root[v] = (const float*)q[3];
-        c.has_root[v] = q[2] != nullptr;
+        c.count_on[v][0] = 1, c.count_on[v][1] = q[2] != nullptr;
+        c.skip[v] = q[2] ? 0u : 1u << 1;                 // sum 1 is the root sum
     }
     if ((uintptr_t)err & 3) return apg_fail(APG_EINVAL, f + "err is not 4-byte aligned");
     if ((uintptr_t)transform & 3) return apg_fail(APG_EINVAL, f + "transform is not 4-byte aligned");
-    if ((uintptr_t)acc & 7) return apg_fail(APG_EINVAL, f + "acc is not 8-byte aligned");
-    if ((uintptr_t)workspace & 7) return apg_fail(APG_EINVAL, f + "workspace is not 8-byte aligned");
-    if (workspace_bytes < apg_align_workspace_bytes(B, views, N))
-        return apg_fail(APG_ENOMEM, f + "workspace of " + std::to_string(workspace_bytes) + " bytes, apg_align_workspace_bytes asks for " +
-                                        std::to_string(apg_align_workspace_bytes(B, views, N)));
+    if (int rc = m.sizes_ok()) return rc;
 
     a.B = B, a.views = views, a.N = N;
     a.sp = pred_stride, a.sq = gt_stride, a.srp = pred_root_stride, a.srq = gt_root_stride;
     a.err = err, a.transform = transform, a.part = (double*)workspace;
-    c.B = B, c.views = views, c.part = (const double*)workspace, c.acc = acc;
+    c.n = B, c.views = views, c.B = B, c.nsum = 3, c.pitch = ACC, c.part = (const double*)workspace, c.acc = acc;
+    c.stride = 3, c.view_stride = 3 * (long long)B;      // part[view][sample][3]
+    c.count_slot[0] = 0, c.count_slot[1] = 4;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)B * (unsigned)views);
     if (N <= NT_SMALL)
@@ -359,7 +338,7 @@ int apg_align_update(int B, int views, int N, int64_t pred_stride, int64_t gt_st
     else
         hipLaunchKernelGGL((align_main_kernel<NT_BIG, ALIGN_KEEP ? KEEP_PTS : 0>), grid, dim3(NT_BIG), 0, st, a);
     APG_TRY(hipGetLastError());
-    hipLaunchKernelGGL(align_combine_kernel, dim3(1), dim3(64), 0, st, c);
+    hipLaunchKernelGGL(metric_combine_kernel, dim3(1), dim3(COMBINE_NT), 0, st, c);
     APG_TRY(hipGetLastError());
     return APG_OK;
 }

@@ -12,7 +12,7 @@
 //     the walk.  The prediction's lane gets the ground truth's position by __shfl_xor(.., 1) and forms the distance.
 //     Then the workgroup's 25 sums per view (all joints, each joint, translation, angle) are taken over its samples in index order,
 //     in fp64, by one thread each, out of the per-sample values parked in the same LDS, and written to the workspace.
-//   eval_combine_kernel   one workgroup: each sum's partials added in workgroup order, in fp64, then ONE add into the accumulator.
+//   metric_combine_kernel (metric_common.inc) one workgroup: each sum's partials added in workgroup order, in fp64, ONE add into the accumulator.
 //
 // Per chain, with `#pragma clang fp contract(off)` so that every fused product below is an fmaf call and nothing else is fused:
 //   angle-axis r = (x, y, z) -> R (torchgeometry 0.1.2, angle_axis_to_rotation_matrix):
@@ -59,14 +59,9 @@ struct EvalArgs {
     double* part;                                      // [workgroup][view][NSUM]
 };
 
-struct CombineArgs {
-    int nwg, views, B;
-    int has_trans[2], has_angles[2];
-    const double* part;
-    double* acc;
-};
+#include "metric_common.inc"
 
-__device__ __forceinline__ float norm3(float d0, float d1, float d2) { return sqrtf(fmaf(d2, d2, fmaf(d1, d1, d0 * d0))); }
+static_assert(2 * (NSUM + 1) <= COMBINE_NT && NSUM + 1 <= ACC, "metric_combine_kernel: a thread per (view, sum) and one per view");
 
 __device__ __forceinline__ void aa_to_rotmat(float x, float y, float z, float* R) {
     const float t2 = fmaf(z, z, fmaf(y, y, x * x));
@@ -209,21 +204,7 @@ __global__ void __launch_bounds__(ET) eval_main_kernel(const EvalArgs a) {
 }
 
 // accumulator of one view: [0] samples, [1] sum of joint_err, [2 .. 23] per joint, [24] sum of trans_err, [25] sum of angle_err,
-// [26] samples with a translation, [27] samples with gt angles
-__global__ void __launch_bounds__(ET) eval_combine_kernel(const CombineArgs c) {
-    const int t = threadIdx.x;
-    if (t < c.views * NSUM) {
-        const int v = t / NSUM, q = t - v * NSUM;
-        double sum = 0.0;
-        for (int w = 0; w < c.nwg; ++w) sum += c.part[((size_t)w * c.views + v) * NSUM + q];
-        c.acc[v * ACC + 1 + q] += sum;
-    } else if (t < c.views * NSUM + c.views) {
-        const int v = t - c.views * NSUM;
-        c.acc[v * ACC] += (double)c.B;
-        if (c.has_trans[v]) c.acc[v * ACC + 26] += (double)c.B;
-        if (c.has_angles[v]) c.acc[v * ACC + 27] += (double)c.B;
-    }
-}
+// [26] samples with a translation, [27] samples with gt angles: metric_combine_kernel over the workgroups' partials, no sum skipped
 
 inline int64_t eval_nwg(int B, int views) {
     const int spw = ITEMS / views;
@@ -246,29 +227,27 @@ int apg_eval_update(int B, int views, int flags, const float* j_rest, const int*
                     const float* gt_body, float* joint_err, float* trans_err, float* angle_err, double* acc, void* workspace,
                     int64_t workspace_bytes, void* stream) {
     const std::string f = "apg_eval_update: ";
+    static const char* const name[APG_EVAL_PER_VIEW] = {"gt_orient", "pred_rot", "gt_trans", "pred_trans", "gt_angles"};
+    const MetricChecks m = {f, views, per_view, APG_EVAL_PER_VIEW, 2, name, acc, workspace, workspace_bytes,
+                            apg_eval_workspace_bytes(B, views), "apg_eval_workspace_bytes"};
     if (B < 0) return apg_fail(APG_EINVAL, f + "B must be >= 0");
-    if (views != 1 && views != 2) return apg_fail(APG_EINVAL, f + "views must be 1 or 2");
+    if (int rc = m.views_ok()) return rc;
     if (flags != APG_EVAL_ANGLE_AXIS && flags != APG_EVAL_ROTMAT) return apg_fail(APG_EINVAL, f + "flags must be APG_EVAL_ANGLE_AXIS or APG_EVAL_ROTMAT");
     if (!j_rest) return apg_fail(APG_EINVAL, f + "j_rest is NULL");
     if (!parents) return apg_fail(APG_EINVAL, f + "parents is NULL");
-    if (!per_view) return apg_fail(APG_EINVAL, f + "the per_view table is NULL");
+    if (int rc = m.table_ok()) return rc;
     if (!gt_body) return apg_fail(APG_EINVAL, f + "gt_body is NULL");
-    if (!acc) return apg_fail(APG_EINVAL, f + "acc is NULL");
-    if (!workspace) return apg_fail(APG_EINVAL, f + "workspace is NULL");
+    if (int rc = m.sinks_ok()) return rc;
     if (parents[0] != -1) return apg_fail(APG_EINVAL, f + "parents[0] must be -1");
     for (int j = 1; j < NJ; ++j)
         if (parents[j] < 0 || parents[j] >= j)
             return apg_fail(APG_EINVAL, f + "parents[" + std::to_string(j) + "] must be in 0 .. " + std::to_string(j - 1));
-    static const char* const name[APG_EVAL_PER_VIEW] = {"gt_orient", "pred_rot", "gt_trans", "pred_trans", "gt_angles"};
     EvalArgs a = {};
     CombineArgs c = {};
     for (int v = 0; v < views; ++v) {
         const void* const* q = per_view + v * APG_EVAL_PER_VIEW;
         const std::string at = " of view " + std::to_string(v);
-        for (int k = 0; k < APG_EVAL_PER_VIEW; ++k) {
-            if (k < 2 && !q[k]) return apg_fail(APG_EINVAL, f + name[k] + at + " is NULL");
-            if ((uintptr_t)q[k] & 3) return apg_fail(APG_EINVAL, f + name[k] + at + " is not 4-byte aligned");
-        }
+        if (int rc = m.view_ok(v)) return rc;
         if (q[3] && !q[2]) return apg_fail(APG_EINVAL, f + "pred_trans" + at + " is given without gt_trans");
         if (q[2] && !q[3]) return apg_fail(APG_EINVAL, f + "gt_trans" + at + " is given without pred_trans");
         if (q[4] && flags != APG_EVAL_ANGLE_AXIS)
@@ -277,17 +256,13 @@ int apg_eval_update(int B, int views, int flags, const float* j_rest, const int*
         if (angle_err && !q[4]) return apg_fail(APG_EINVAL, f + "angle_err is asked for but gt_angles" + at + " is NULL");
         a.gt_orient[v] = (const float*)q[0], a.pred_rot[v] = (const float*)q[1], a.gt_trans[v] = (const float*)q[2];
         a.pred_trans[v] = (const float*)q[3], a.gt_angles[v] = (const float*)q[4];
-        c.has_trans[v] = q[3] != nullptr, c.has_angles[v] = q[4] != nullptr;
+        c.count_on[v][0] = 1, c.count_on[v][1] = q[3] != nullptr, c.count_on[v][2] = q[4] != nullptr;
     }
     const void* p4[5] = {j_rest, gt_body, joint_err, trans_err, angle_err};
     static const char* const n4[5] = {"j_rest", "gt_body", "joint_err", "trans_err", "angle_err"};
     for (int k = 0; k < 5; ++k)
         if ((uintptr_t)p4[k] & 3) return apg_fail(APG_EINVAL, f + n4[k] + " is not 4-byte aligned");
-    if ((uintptr_t)acc & 7) return apg_fail(APG_EINVAL, f + "acc is not 8-byte aligned");
-    if ((uintptr_t)workspace & 7) return apg_fail(APG_EINVAL, f + "workspace is not 8-byte aligned");
-    if (workspace_bytes < apg_eval_workspace_bytes(B, views))
-        return apg_fail(APG_ENOMEM, f + "workspace of " + std::to_string(workspace_bytes) + " bytes, apg_eval_workspace_bytes asks for " +
-                                        std::to_string(apg_eval_workspace_bytes(B, views)));
+    if (int rc = m.sizes_ok()) return rc;
     if (B == 0) return APG_OK;                            // nothing to add: no launch, the accumulator stays as it is
 
     const int64_t nwg = eval_nwg(B, views);
@@ -296,11 +271,13 @@ int apg_eval_update(int B, int views, int flags, const float* j_rest, const int*
     a.j_rest = j_rest, a.gt_body = gt_body;
     a.joint_err = joint_err, a.trans_err = trans_err, a.angle_err = angle_err;
     a.part = (double*)workspace;
-    c.nwg = (int)nwg, c.views = views, c.B = B, c.part = (const double*)workspace, c.acc = acc;
+    c.n = (int)nwg, c.views = views, c.B = B, c.nsum = NSUM, c.pitch = ACC, c.part = (const double*)workspace, c.acc = acc;
+    c.stride = views * NSUM, c.view_stride = NSUM;       // part[workgroup][view][NSUM]
+    c.count_slot[0] = 0, c.count_slot[1] = 26, c.count_slot[2] = 27;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(eval_main_kernel, dim3((unsigned)nwg), dim3(ET), 0, st, a);
     APG_TRY(hipGetLastError());
-    hipLaunchKernelGGL(eval_combine_kernel, dim3(1), dim3(ET), 0, st, c);
+    hipLaunchKernelGGL(metric_combine_kernel, dim3(1), dim3(COMBINE_NT), 0, st, c);
     APG_TRY(hipGetLastError());
     return APG_OK;
 }

@@ -20,40 +20,18 @@ The reference's print labels mix its two loaders: copenet_twoview.py:596 prints 
 "test_mpe1", and the view-1 errors it computed are never printed.  That is not reproduced: here index 0 / 1 is always the view, and
 one EvalMetrics scores one stream of batches (use two objects for two loaders).
 """
-import ctypes
-
 import torch
 
 from . import _native_grad as G
+from . import _stream_metric as S
+from ._stream_metric import KINDS  # noqa: F401  (importable from here as before)
 
-KINDS = ("twoview", "singleview", "hmr", "muhmr")
-_VIEWS = {"twoview": 2, "singleview": 1, "hmr": 1, "muhmr": 2}
 NJ = 22
 ANGLE_AXIS, ROTMAT = 0, 1                # include/airpose_grad.h: APG_EVAL_ANGLE_AXIS, APG_EVAL_ROTMAT
 PER_VIEW = 5                             # APG_EVAL_PER_VIEW: gt_orient, pred_rot, gt_trans, pred_trans, gt_angles
 ACC = 28                                 # APG_EVAL_ACC_PER_VIEW
 # one view's accumulator (include/airpose_grad.h)
 A_COUNT, A_JOINT, A_PER_JOINT, A_TRANS, A_ANGLE, A_NTRANS, A_NANGLE = 0, 1, 2, 24, 25, 26, 27
-
-
-def _tensor(t, dev, shape, name):
-    """fp32, contiguous, on dev, of `shape`; anything else is refused by name (TrainingLoss._pred's rules).  dev = None: shape and
-    dtype only"""
-    if not torch.is_tensor(t):
-        raise RuntimeError("EvalMetrics: %s must be a tensor, got %s" % (name, type(t).__name__))
-    if tuple(t.shape) != tuple(shape):
-        raise RuntimeError("EvalMetrics: %s must be %s, got %s" % (name, tuple(shape), tuple(t.shape)))
-    if not t.is_floating_point():
-        raise RuntimeError("EvalMetrics: %s must be a floating-point tensor, got %s" % (name, t.dtype))
-    if dev is None:
-        return t
-    if not t.is_cuda:
-        raise RuntimeError("EvalMetrics: %s lives on %s; it must be a CUDA (ROCm) tensor, there is no CPU path" % (name, t.device))
-    if t.device != dev:
-        raise RuntimeError("EvalMetrics: %s lives on %s, the metrics on %s" % (name, t.device, dev))
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.detach().contiguous()
 
 
 def rest_joints(model):
@@ -73,7 +51,7 @@ def rest_joints(model):
     return j.float().contiguous(), parents
 
 
-class EvalMetrics(object):
+class EvalMetrics(S.StreamMetric):
     """MPJPE, MPE and the angle-axis error of a stream of test_step output dicts, on libairpose_grad.so.
 
     EvalMetrics(smplx_or_model_dict, kind="twoview" | "singleview" | "hmr" | "muhmr", device=None, per_sample=False)
@@ -97,19 +75,14 @@ class EvalMetrics(object):
     of include/airpose_grad.h) so that ranks or shards can add them; no collective is part of this class.
     """
 
+    NAME, ACC_SHAPE = "EvalMetrics", (2, ACC)
+
     def __init__(self, model, kind="twoview", device=None, per_sample=False):
-        if kind not in KINDS:
-            raise ValueError("EvalMetrics: kind must be one of %s, got %r" % (", ".join(KINDS), kind))
-        self.kind, self.views, self.per_sample = kind, _VIEWS[kind], bool(per_sample)
+        S.StreamMetric.__init__(self, kind, device, per_sample, model)
+
+    def _configure(self, model):
         self._j_host, self.parents = rest_joints(model)
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device()
-                                                                                   if torch.cuda.is_available() else 0)
-        if self.device.type != "cuda":
-            raise RuntimeError("EvalMetrics: device must be a CUDA (ROCm) device, got %s; there is no CPU path" % (self.device,))
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
-        self._host = torch.zeros(2, ACC, dtype=torch.float64)     # the sums while they are not on the device
-        self._acc = self._j = self._ws = None
+        self._j = None
         self._cparents = G.ints(self.parents)
 
     # ---------------------------------------------------------------------------------------- the dict
@@ -125,20 +98,7 @@ class EvalMetrics(object):
         """-> (mode, gt_body, per view a dict gt_orient / pred_rot / gt_trans / pred_trans / gt_angles of (key, tensor) or None):
         which entries of output / batch an update would read.  Refuses a missing required key and a translation without its
         ground truth, by name; looks at no tensor."""
-        def find(keys):
-            for src in (output, batch):
-                if src is None:
-                    continue
-                for k in keys:
-                    if k in src and src[k] is not None:
-                        return k, src[k]
-            return None
-
-        def need(keys, what):
-            hit = find(keys)
-            if hit is None:
-                raise RuntimeError("EvalMetrics(%s): neither output nor batch has %s (%s)" % (self.kind, " / ".join(keys), what))
-            return hit
+        find, need = self._lookup(output, batch)
         body = need(["smplpose_rotmat"], "the ground-truth body pose")
         views, mode = [], None
         for v in range(self.views):
@@ -168,18 +128,12 @@ class EvalMetrics(object):
     def update(self, output, batch=None):
         mode, body, views = self.gather(output, batch)
         dev = self.device
-        first = views[0]["pred_rot"][1]
-        if not torch.is_tensor(first) or first.dim() < 1:
-            raise RuntimeError("EvalMetrics: %s must be a tensor with a batch dimension" % views[0]["pred_rot"][0])
-        B = first.shape[0]
+        B = self._batch_size(views[0]["pred_rot"])
         shapes = {"gt_orient": (B, 1, 3, 3), "pred_rot": (B, NJ, 3) if mode == ANGLE_AXIS else (B, NJ, 3, 3), "gt_trans": (B, 3),
                   "pred_trans": (B, 3), "gt_angles": (B, NJ, 3)}
         order = ("gt_orient", "pred_rot", "gt_trans", "pred_trans", "gt_angles")
         entries = [None if d[n] is None else (d[n][1], shapes[n], d[n][0]) for d in views for n in order] + [(body[1], (B, 21, 3, 3), body[0])]
-        for e in entries:                                        # what every tensor must be first, then where it must live
-            if e is not None:
-                _tensor(e[0], None, e[1], e[2])
-        table = [None if e is None else _tensor(e[0], dev, e[1], e[2]) for e in entries]
+        table = S.place(self.NAME, entries, dev)
         gt_body = table.pop()
         has_trans = all(d["pred_trans"] is not None for d in views)
         has_angles = all(d["gt_angles"] is not None for d in views)
@@ -187,44 +141,18 @@ class EvalMetrics(object):
         with torch.cuda.device(dev):
             if self._j is None:
                 self._j = self._j_host.to(dev)
-            if self._acc is None:
-                self._acc = self._host.to(dev)
-            nbytes = L.apg_eval_workspace_bytes(B, self.views)
-            if self._ws is None or self._ws.numel() * 8 < nbytes:
-                self._ws = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.float64)
+            acc, ws = self._buffers(L.apg_eval_workspace_bytes(B, self.views))
             je = te = ae = None
             if self.per_sample:
                 je = torch.empty(self.views, B, NJ, device=dev, dtype=torch.float32)
                 te = torch.empty(self.views, B, device=dev, dtype=torch.float32) if has_trans else None
                 ae = torch.empty(self.views, B, NJ, device=dev, dtype=torch.float32) if has_angles else None
-            vp = lambda t: ctypes.c_void_p(None if t is None else t.data_ptr())
+            vp = G.vp
             G.check(L.apg_eval_update(B, self.views, mode, vp(self._j), self._cparents, G.ptrs(table), vp(gt_body), vp(je), vp(te),
-                                      vp(ae), vp(self._acc), vp(self._ws), self._ws.numel() * 8,
-                                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "apg_eval_update")
+                                      vp(ae), vp(acc), vp(ws), ws.numel() * 8, G.stream(dev)), "apg_eval_update")
         return (je, te, ae) if self.per_sample else None
 
-    def reset(self):
-        self._host = torch.zeros(2, ACC, dtype=torch.float64)
-        if self._acc is not None:
-            self._acc.zero_()
-
-    def state(self):
-        """{"kind", "acc": (2, 28) float64 host tensor: per view the raw sums and counts}; one host synchronisation"""
-        acc = self._acc.cpu() if self._acc is not None else self._host.clone()
-        return {"kind": self.kind, "acc": acc}
-
-    def load_state(self, state):
-        acc = torch.as_tensor(state["acc"])
-        if state.get("kind", self.kind) != self.kind:
-            raise RuntimeError("EvalMetrics: the state is of kind %r, this object of kind %r" % (state.get("kind"), self.kind))
-        if tuple(acc.shape) != (2, ACC) or acc.dtype != torch.float64:
-            raise RuntimeError("EvalMetrics: state['acc'] must be (2, %d) float64, got %s %s" % (ACC, tuple(acc.shape), acc.dtype))
-        self._host = acc.detach().cpu().clone()
-        if self._acc is not None:
-            self._acc.copy_(self._host)
-
-    def compute(self):
-        return summarise(self.state()["acc"], self.views)
+    summarise = staticmethod(lambda acc, views: summarise(acc, views))
 
 
 def summarise(acc, views):
@@ -244,12 +172,7 @@ def summarise(acc, views):
 
 
 def evaluate(pipe, batches, metrics):
-    """Score a stream of batches behind TwoViewInference.submit: for each batch, submit(batch, want_angles=True), make the current
-    stream wait for the Pending and update the metrics with (its outputs, the batch); ONE host synchronisation, in compute() after
-    the last batch (and those submit itself makes when more than its DEPTH batches are in flight).  `batches` yields dicts with
-    submit's inputs and the ground truth (smplorient_rel0/1, smplpose_rotmat, optionally smpltrans_rel0/1) on the GPU."""
-    for batch in batches:
-        pend = pipe.submit(batch, want_angles=True)
-        out = pend.wait(torch.cuda.current_stream(metrics.device))
-        metrics.update(out, batch)
-    return metrics.compute()
+    """Score a stream of batches behind TwoViewInference.submit with ONE metric object (_stream_metric.evaluate's loop) -> its
+    compute() dict.  `batches` yields dicts with submit's inputs and the ground truth (smplorient_rel0/1, smplpose_rotmat, optionally
+    smpltrans_rel0/1) on the GPU."""
+    return S.evaluate(pipe, batches, [metrics])[0]

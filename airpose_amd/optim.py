@@ -202,7 +202,6 @@ class FusedAdam(torch.optim.Optimizer):
             beta1, beta2 = group["betas"]
             with torch.cuda.device(dev):
                 rc = L.apg_adam_step(n, e["P"], e["G"], e["M"], e["V"], e["X"], e["numel"], e["step"], float(group["lr"]), float(beta1),
-                                     float(beta2), float(group["eps"]), float(group["weight_decay"]),
-                                     ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                                     float(beta2), float(group["eps"]), float(group["weight_decay"]), G.stream(dev))
             G.check(rc, "apg_adam_step")
         return loss

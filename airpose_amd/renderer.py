@@ -12,13 +12,13 @@ its centre, GL's convention) and the shading, which is a stand-in without pyrend
 3 (1 - 0.2) / pi of Lambert term (three unit directional lights along the view axis on a material of metallic factor 0.2).  The
 geometry -- which face a pixel shows, at which depth -- is pinned by the contract in include/airpose_grad.h.
 """
-import ctypes
 import math
 
 import numpy as np
 import torch
 
 from . import _native_grad as G
+from . import _stream_metric as S
 
 AMBIENT = 0.5
 DIFFUSE = 3.0 * (1.0 - 0.2) / math.pi
@@ -54,25 +54,6 @@ def make_grid(images, nrow=8, padding=2):
         y, x = divmod(k, xmaps)
         grid[:, y * h + padding:y * h + padding + H, x * w + padding:x * w + padding + W] = images[k]
     return grid
-
-
-def _check(t, shape, name):
-    """what a tensor must be, wherever it lives"""
-    if not torch.is_tensor(t):
-        raise RuntimeError("Renderer: %s must be a tensor, got %s" % (name, type(t).__name__))
-    if tuple(t.shape) != tuple(shape):
-        raise RuntimeError("Renderer: %s must be %s, got %s" % (name, tuple(shape), tuple(t.shape)))
-    if not t.is_floating_point():
-        raise RuntimeError("Renderer: %s must be a floating-point tensor, got %s" % (name, t.dtype))
-
-
-def _device(t, name, dev):
-    """fp32, contiguous, on dev (None: any CUDA device)"""
-    if not t.is_cuda:
-        raise RuntimeError("Renderer: %s lives on %s; it must be a CUDA (ROCm) tensor, there is no CPU path" % (name, t.device))
-    if dev is not None and t.device != dev:
-        raise RuntimeError("Renderer: %s lives on %s, the vertices on %s" % (name, t.device, dev))
-    return t.detach().float().contiguous()
 
 
 class Renderer(object):
@@ -135,10 +116,10 @@ class Renderer(object):
                  (camera_rotation, (n, 3, 3), "camera_rotation"), (images, (n, 3, H, W), "images")]
         for x, shape, name in given:                     # what every tensor must be first, then where it must live
             if x is not None:
-                _check(x, shape, name)
-        v = _device(vertices, "vertices", None)
+                S.check_what("Renderer", x, shape, name)
+        v = S.check_where("Renderer", vertices, None, "vertices", "the vertices")
         dev = v.device
-        t, R, bg = (None if x is None else _device(x, name, dev) for x, _, name in given[1:])
+        t, R, bg = (None if x is None else S.check_where("Renderer", x, dev, name, "the vertices") for x, _, name in given[1:])
         L = G.lib()
         with torch.cuda.device(dev):
             faces, off, ent = self._table(dev, V)
@@ -152,13 +133,12 @@ class Renderer(object):
             ws = self._ws.get((dev, n, V))
             if ws is None or ws.numel() * 8 < nbytes:
                 ws = self._ws[(dev, n, V)] = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
-            vp = lambda x: ctypes.c_void_p(None if x is None else x.data_ptr())
+            vp = G.vp
             G.check(L.apg_render_overlay(n, V, F, H, W, vp(v), vp(faces), vp(off), vp(ent), ent.numel(), vp(R), vp(t),
                                          self.focal_length[0], self.focal_length[1], float(self.camera_center[0]),
                                          float(self.camera_center[1]), ZNEAR, ZFAR, vp(bg), float(color[0]), float(color[1]),
                                          float(color[2]), float(ambient), float(diffuse), vp(rgb), vp(depth), vp(face), vp(ws),
-                                         ws.numel() * 8, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                    "apg_render_overlay")
+                                         ws.numel() * 8, G.stream(dev)), "apg_render_overlay")
         return rgb, depth, face
 
     def visualize_tb(self, vertices, camera_translation, camera_rotation, images, nrow=5, color=(0.8, 0.3, 0.3, 1.0), padding=2):

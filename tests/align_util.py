@@ -2,12 +2,10 @@
 (airpose_amd/csrc/eval_align.hip) on numpy.linalg.svd, the fp64 host emulation of the kernel's sequence (pivoted moments, Horn's
 4 x 4 matrix, fixed-sweep Jacobi), the error bars counted from that sequence, the cases and the GPU call.  The derivation of the bars
 is in test_align_fp64.py's docstring."""
-import ctypes
-
 import numpy as np
 import torch
 
-from eval_util import Arena
+from eval_util import GuardedCall
 
 U = 2.0 ** -24
 U64 = 2.0 ** -53
@@ -383,42 +381,21 @@ def run_gpu(case, dev, roots=(True, True), acc_init=None, per_sample=True, skew=
     """one apg_align_update into fresh guarded buffers -> dict(err, transform, acc (2, 5), guards_ok, inputs_ok), numpy on the host.
     roots[v]: whether view v's roots are passed.  skew: every input starts one float past a 16-byte boundary"""
     from airpose_amd import _native_grad as G
-    L = G.lib()
+    L, vp = G.lib(), G.vp
     B, views, N = case["B"], case["views"], case["N"]
     total = sum(int(np.prod(case["view"][v][k].shape)) + 80 for v in range(views) for k in ("pred", "gt", "pred_root", "gt_root"))
-    ar = Arena(dev, 8192 + total + views * B * 16 * 2)
-    ins = []
-
-    def put(x):
-        t = torch.from_numpy(x)
-        if skew:
-            g = ar.take((t.numel() + 1,))
-            ar.mask[g.data_ptr() // 4 - ar.buf.data_ptr() // 4] = True      # the skipped float stays a guard
-            g = g[1:].view(t.shape)
-            g.copy_(t)
-        else:
-            g = ar.take(t.shape, t)
-        ins.append((g, t))
-        return g
+    gc = GuardedCall(dev, 8192 + total + views * B * 16 * 2)
+    put = lambda x: gc.put(torch.from_numpy(x), skew)
     table = []
     for v in range(views):
         d = case["view"][v]
         table += [put(d["pred"]), put(d["gt"])] + ([put(d["pred_root"]), put(d["gt_root"])] if roots[v] else [None, None])
-    err = ar.take((views, B, 3)) if per_sample else None
-    tr = ar.take((views, B, 13)) if per_sample else None
-    acc = ar.take((2, ACC), torch.zeros(2, ACC, dtype=torch.float64) if acc_init is None else torch.as_tensor(acc_init),
-                  dtype=torch.float64)
+    err = gc.ar.take((views, B, 3)) if per_sample else None
+    tr = gc.ar.take((views, B, 13)) if per_sample else None
     nbytes = L.apg_align_workspace_bytes(B, views, N)
     assert nbytes == B * views * 24
-    ws = ar.take((nbytes // 8,), dtype=torch.float64)
-    vp = lambda t: ctypes.c_void_p(None if t is None else t.data_ptr())
-    with torch.cuda.device(dev):
-        rc = L.apg_align_update(B, views, N, case["stride_p"], case["stride_q"], case["stride_rp"], case["stride_rq"], G.ptrs(table),
-                                vp(err), vp(tr), vp(acc), vp(ws), nbytes, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        G.check(rc, "apg_align_update")
-        torch.cuda.synchronize(dev)
+    acc, ws = gc.sums(ACC, acc_init, nbytes)
     host = lambda t: None if t is None else t.cpu().numpy().copy()
-    res = dict(err=host(err), transform=host(tr), acc=host(acc))
-    res["inputs_ok"] = all(torch.equal(g.cpu(), t) for g, t in ins)
-    res["guards_ok"] = ar.guards_intact()
-    return res
+    return gc.run(G, lambda: L.apg_align_update(B, views, N, case["stride_p"], case["stride_q"], case["stride_rp"], case["stride_rq"],
+                                                G.ptrs(table), vp(err), vp(tr), vp(acc), vp(ws), nbytes, G.stream(dev)),
+                  "apg_align_update", lambda: dict(err=host(err), transform=host(tr), acc=host(acc)))

@@ -1,7 +1,6 @@
 """Shared by test_eval_fp64.py and test_eval_module.py: the fp64 restatement of apg_eval_update (airpose_amd/csrc/eval_metrics.hip),
 the fp32 emulation of the kernel's instruction sequence, the error bars counted from that sequence, the cases and the GPU call.
 The derivation of the bars is in test_eval_fp64.py's docstring."""
-import ctypes
 import math
 
 import torch
@@ -326,44 +325,62 @@ class Arena(object):
         return bool(torch.isnan(self.buf[self.mask]).all())
 
 
+class GuardedCall(object):
+    """the scaffolding of ONE call of a metric entry point into fresh guarded buffers: the arena, the inputs put into it (tracked,
+    so that the call is seen to leave them alone), the accumulator, a workspace of exactly the queried size, the call itself and
+    what the arena looks like afterwards"""
+
+    def __init__(self, dev, floats):
+        self.dev, self.ar, self.ins = dev, Arena(dev, floats), []
+
+    def put(self, t, skew=False):
+        """host tensor (None stays None) -> its copy in the arena; skew: the copy starts one float past a 16-byte boundary"""
+        if t is None:
+            return None
+        if skew:
+            g = self.ar.take((t.numel() + 1,))
+            self.ar.mask[g.data_ptr() // 4 - self.ar.buf.data_ptr() // 4] = True      # the skipped float stays a guard
+            g = g[1:].view(t.shape)
+            g.copy_(t)
+        else:
+            g = self.ar.take(t.shape, t)
+        self.ins.append((g, t))
+        return g
+
+    def sums(self, per_view, acc_init, nbytes):
+        """-> (the (2, per_view) accumulator holding acc_init (None: zeros), a workspace of exactly nbytes)"""
+        init = torch.zeros(2, per_view, dtype=torch.float64) if acc_init is None else torch.as_tensor(acc_init)
+        return self.ar.take((2, per_view), init, dtype=torch.float64), self.ar.take(((nbytes + 7) // 8,), dtype=torch.float64)
+
+    def run(self, G, call, what, res):
+        """call() (-> the entry point's status) on dev, checked and synchronised; res gains inputs_ok and guards_ok"""
+        with torch.cuda.device(self.dev):
+            G.check(call(), what)
+            torch.cuda.synchronize(self.dev)
+        res = res()
+        res["inputs_ok"] = all(torch.equal(g.cpu(), t) for g, t in self.ins)
+        res["guards_ok"] = self.ar.guards_intact()
+        return res
+
+
 def run_gpu(case, dev, acc_init=None, per_sample=True):
     """one apg_eval_update into fresh guarded buffers -> dict(joint_err, trans_err, angle_err, acc (2, 28), guards_ok, inputs_ok),
     everything on the host"""
     from airpose_amd import _native_grad as G
-    L = G.lib()
+    L, vp = G.lib(), G.vp
     B, views = case["B"], case["views"]
-    ar = Arena(dev, 4096 + B * views * (NJ * 9 + 9 + 6 + 2 * NJ * 3 + 2 * NJ + 1 + 8 * GUARD) + B * 21 * 9 + 64 * 1024)
-    ins = []
-
-    def put(t):
-        if t is None:
-            return None
-        g = ar.take(t.shape, t)
-        ins.append((g, t))
-        return g
-    j = put(case["j_rest"])
-    body = put(case["gt_body"])
-    table = []
-    for d in case["view"]:
-        table += [put(d["gt_orient"]), put(d["pred"]), put(d["gt_trans"]), put(d["pred_trans"]), put(d["gt_angles"])]
+    gc = GuardedCall(dev, 4096 + B * views * (NJ * 9 + 9 + 6 + 2 * NJ * 3 + 2 * NJ + 1 + 8 * GUARD) + B * 21 * 9 + 64 * 1024)
+    j, body = gc.put(case["j_rest"]), gc.put(case["gt_body"])
+    table = [gc.put(d[k]) for d in case["view"] for k in ("gt_orient", "pred", "gt_trans", "pred_trans", "gt_angles")]
     has_t = all(d["pred_trans"] is not None for d in case["view"])
     has_a = all(d["gt_angles"] is not None for d in case["view"])
-    je = ar.take((views, B, NJ)) if per_sample else None
-    te = ar.take((views, B)) if per_sample and has_t else None
-    ae = ar.take((views, B, NJ)) if per_sample and has_a else None
-    acc = ar.take((2, ACC), torch.zeros(2, ACC, dtype=torch.float64) if acc_init is None else acc_init, dtype=torch.float64)
+    je = gc.ar.take((views, B, NJ)) if per_sample else None
+    te = gc.ar.take((views, B)) if per_sample and has_t else None
+    ae = gc.ar.take((views, B, NJ)) if per_sample and has_a else None
     nbytes = L.apg_eval_workspace_bytes(B, views)
     assert nbytes > 0
-    ws = ar.take(((nbytes + 7) // 8,), dtype=torch.float64)
-    vp = lambda t: ctypes.c_void_p(None if t is None else t.data_ptr())
-    with torch.cuda.device(dev):
-        rc = L.apg_eval_update(B, views, 0 if case["mode"] == "aa" else 1, vp(j), G.ints(case["parents"]), G.ptrs(table), vp(body),
-                               vp(je), vp(te), vp(ae), vp(acc), vp(ws), nbytes,
-                               ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        G.check(rc, "apg_eval_update")
-        torch.cuda.synchronize(dev)
+    acc, ws = gc.sums(ACC, acc_init, nbytes)
     host = lambda t: None if t is None else t.cpu().clone()
-    res = dict(joint_err=host(je), trans_err=host(te), angle_err=host(ae), acc=acc.cpu().clone())
-    res["inputs_ok"] = all(torch.equal(g.cpu(), t) for g, t in ins)
-    res["guards_ok"] = ar.guards_intact()
-    return res
+    return gc.run(G, lambda: L.apg_eval_update(B, views, 0 if case["mode"] == "aa" else 1, vp(j), G.ints(case["parents"]), G.ptrs(table),
+                                               vp(body), vp(je), vp(te), vp(ae), vp(acc), vp(ws), nbytes, G.stream(dev)),
+                  "apg_eval_update", lambda: dict(joint_err=host(je), trans_err=host(te), angle_err=host(ae), acc=host(acc)))

@@ -37,7 +37,6 @@ face f has z_f + zbar_f < z_g - zbar_g and the colour is within cbar of g's fp64
 sure face, its depth is 0, its face -1 and its colour the background's bits.  scan() also counts, per pixel, how many answers judge()
 would accept; the tests cap the pixels with more than one at 1 %.
 """
-import ctypes
 import functools
 import math
 
@@ -538,12 +537,12 @@ def gpu_once(case, dev, want_depth=True, want_face=True):
     nbytes = L.apg_render_workspace_bytes(n, H, W, V, F)
     assert nbytes > 0 and nbytes % 8 == 0
     ws_b, ws = _guarded(nbytes // 8, torch.int64, 0x5a5a5a5a5a5a5a5a, dev)
-    vp = lambda x: ctypes.c_void_p(None if x is None else x.data_ptr())
+    vp = G.vp
     with torch.cuda.device(dev):
         G.check(L.apg_render_overlay(n, V, F, H, W, vp(ins["verts"]), vp(ins["faces"]), vp(ins["off"]), vp(ins["ent"]), len(ff), vp(ins["R"]),
                                      vp(ins["t"]), case["fx"], case["fy"], case["cx"], case["cy"], ZNEAR, ZFAR, vp(ins["bg"]),
                                      case["color"][0], case["color"][1], case["color"][2], AMBIENT, DIFFUSE, vp(rgb), vp(dep), vp(fac),
-                                     vp(ws), nbytes, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "apg_render_overlay")
+                                     vp(ws), nbytes, G.stream(dev)), "apg_render_overlay")
         torch.cuda.synchronize(dev)
     assert _guards_intact(rgb_b, rgb.numel(), nan), "rgb guard bands"
     assert dep is None or _guards_intact(dep_b, dep.numel(), nan), "depth guard bands"
