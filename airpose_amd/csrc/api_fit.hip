@@ -31,7 +31,7 @@ int ap_fit_create(ap_fit** out, const ap_smplx* body, const float* w1, const flo
 void ap_fit_destroy(ap_fit* h) {
     if (!h) return;
     for (DevBuf* b : {&h->w1t, &h->w2t, &h->w3t, &h->w1, &h->w2, &h->w3, &h->b1, &h->b2, &h->b3, &h->H1, &h->H2, &h->O, &h->dO,
-                      &h->dH2, &h->dH1, &h->dz, &h->aa, &h->dphi, &h->dtau, &h->dbeta, &h->loss, &h->adam_m, &h->adam_v, &h->robust})
+                      &h->aa, &h->dphi, &h->dtau, &h->dbeta, &h->loss, &h->adam_m, &h->adam_v, &h->robust})
         b->release();
     delete h;
 }
@@ -45,8 +45,7 @@ int ap_fit_run(ap_fit* h, int L, float* z, float* phi, float* tau, float* beta, 
     const int nprm = L * 32 + 2 * L * 9 + 10;
     HIP_TRY(h->H1.reserve((size_t)L * 512 * 4)); HIP_TRY(h->H2.reserve((size_t)L * 512 * 4));
     HIP_TRY(h->O.reserve((size_t)L * 128 * 4)); HIP_TRY(h->dO.reserve((size_t)L * 128 * 4));
-    HIP_TRY(h->dH2.reserve((size_t)L * 512 * 4)); HIP_TRY(h->dH1.reserve((size_t)L * 512 * 4));
-    HIP_TRY(h->dz.reserve((size_t)L * 32 * 4)); HIP_TRY(h->aa.reserve((size_t)L * 63 * 4));
+    HIP_TRY(h->aa.reserve((size_t)L * 63 * 4));
     HIP_TRY(h->dphi.reserve((size_t)2 * L * 6 * 4)); HIP_TRY(h->dtau.reserve((size_t)2 * L * 3 * 4));
     HIP_TRY(h->dbeta.reserve((size_t)L * 10 * 4)); HIP_TRY(h->loss.reserve((size_t)L * 4 * 4));
     HIP_TRY(h->adam_m.reserve((size_t)nprm * 4)); HIP_TRY(h->adam_v.reserve((size_t)nprm * 4));
@@ -55,7 +54,7 @@ int ap_fit_run(ap_fit* h, int L, float* z, float* phi, float* tau, float* beta, 
     FitArgs a{};
     a.L = L;
     a.O = h->O.as<float>(); a.dO = h->dO.as<float>(); a.ldo = 128; a.aa_all = h->aa.as<float>();
-    a.z = z; a.phi = phi; a.tau = tau; a.beta = beta; a.dz = h->dz.as<float>(); a.ldz = 32;
+    a.z = z; a.phi = phi; a.tau = tau; a.beta = beta;
     a.dphi = h->dphi.as<float>(); a.dtau = h->dtau.as<float>(); a.dbeta_part = h->dbeta.as<float>();
     a.loss_part = h->loss.as<float>();
     a.j_template = h->body->m.j_template; a.j_shapedirs = h->body->m.j_shapedirs; a.jsd_ld = 20;
@@ -73,20 +72,20 @@ int ap_fit_run(ap_fit* h, int L, float* z, float* phi, float* tau, float* beta, 
     };
     bool decoded = false;
     for (int j = first_iter; j < first_iter + n_iters; ++j) {
-        const bool with_z = j >= switch_iter;
+        const bool after_switch = j >= switch_iter;
         if (j == first_iter || j == switch_iter) {          // a new torch.optim.Adam starts with empty state (:279-295)
             HIP_TRY(hipMemsetAsync(h->adam_m.p, 0, (size_t)nprm * 4, st));
             HIP_TRY(hipMemsetAsync(h->adam_v.p, 0, (size_t)nprm * 4, st));
         }
-        if (with_z || !decoded) { HIP_TRY(decode()); decoded = true; }      // z is constant before the switch
+        if (after_switch || !decoded) { HIP_TRY(decode()); decoded = true; }      // z is constant before the switch
         if (loss_hist) a.loss_part = loss_hist + (size_t)(j - first_iter) * L * 4;      // the frame kernel writes the history row
         HIP_TRY(ap_launch_fit_frame(a, j, st));
         const int step = j < switch_iter ? j - first_iter + 1 : j - std::max(switch_iter, first_iter) + 1;
-        if (with_z)                                          // decoder backward dO -> dz and Adam on everything, one launch
+        if (after_switch)                                          // decoder backward dO -> dz and Adam on everything, one launch
             HIP_TRY(ap_launch_fit_backprop_adam(a, h->w3.as<float>(), h->w2.as<float>(), h->w1.as<float>(), h->H1.as<float>(),
                                                 h->H2.as<float>(), step, st));
         else
-            HIP_TRY(ap_launch_fit_adam(a, step, 0, st));
+            HIP_TRY(ap_launch_fit_adam(a, step, st));
     }
     return AP_OK;
 }

@@ -294,5 +294,5 @@ struct ap_fit {                   // AirPose+ fitting loop state (fitting.hip)
     int device = 0;
     const ap_smplx* body = nullptr;
     DevBuf w1t, w2t, w3t, w1, w2, w3, b1, b2, b3;     // VPoser decoder: k-major transposes (forward) / as stored (backward)
-    DevBuf H1, H2, O, dO, dH2, dH1, dz, aa, dphi, dtau, dbeta, loss, adam_m, adam_v, robust;
+    DevBuf H1, H2, O, dO, aa, dphi, dtau, dbeta, loss, adam_m, adam_v, robust;
 };

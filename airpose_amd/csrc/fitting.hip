@@ -5,14 +5,17 @@
 // two detectors (:344-347) + VPoser prior (:355) + temporal smoothness (:360-365).  Only the posed JOINTS enter the
 // loss (smplx_out.Jtr, :325-334), so the backward pass runs through the kinematic chain and the joint regressor's shape
 // directions -- not through skinning.  Every adjoint below is written by hand (no autograd on the product path):
-//   VPoser decoder MLP (three small GEMMs, fit_linear_kernel) -> Gram-Schmidt 6-D -> rotation matrix -> axis-angle
+//   VPoser decoder MLP (32 -> 512 -> 512 -> 126, fused into fit_decode_kernel / fit_backprop_adam_kernel) -> Gram-Schmidt
+//   6-D -> rotation matrix -> axis-angle
 //   (tgm 0.1.2 rotation_matrix_to_angle_axis, the decoder's matrot2aa) -> lbs.batch_rodrigues -> kinematic chain ->
 //   rigid transform (pytorch3d rotation_6d_to_matrix) -> camera -> projection -> Geman-McClure.
 // Script quirks reproduced (see oracle/fitting_ref.py): sigma = 30, hip confidences halved on every iteration,
 // loss_beta without gradient, two Adam instances switching at iteration 100.
-// One wave per frame runs the whole geometric forward + backward (fit_frame_kernel); per iteration:
-//   fit_decode_kernel (decoder + matrot2aa), fit_frame_kernel, fit_backprop_adam_kernel (decoder backward + Adam);
-// before the switch to the second optimiser only fit_frame_kernel + fit_adam_kernel.
+// One wave per frame runs the whole geometric forward + backward (fit_frame_kernel).  Launches of ap_fit_run per iteration:
+//   from the switch to the second optimiser on: fit_decode_kernel (decoder + matrot2aa), fit_frame_kernel,
+//     fit_backprop_adam_kernel (decoder backward dO -> dz + Adam on z, phi, tau, beta);
+//   before the switch (z is constant): fit_frame_kernel + fit_adam_kernel (Adam on phi, tau, beta), after ONE
+//     fit_decode_kernel in front of the call's first iteration.
 #include "ap_common.h"
 #include "kernels.h"
 
@@ -96,56 +99,6 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Y[L][N] = act(X[L][K] Wt[K][ldw(:N)] + b) (* (G > 0 ? 1 : 0.01) if G): the decoder's layers and their transposes.
-// ACT: 0 none, 1 LeakyReLU(0.01).  16 rows x 64 columns per workgroup, weights k-major (coalesced over the output).
-template <int ACT>
-__global__ void __launch_bounds__(256) fit_linear_kernel(const float* __restrict__ X, int ldx, int K, const float* __restrict__ Wt,
-                                                         int ldw, const float* __restrict__ bias, const float* __restrict__ G, int ldg,
-                                                         float* __restrict__ Y, int ldy, int L, int N) {
-    __shared__ float xs[16][65];
-    const int c = blockIdx.x * 64 + (threadIdx.x & 63), rq = threadIdx.x >> 6, r0 = blockIdx.y * 16;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int k0 = 0; k0 < K; k0 += 64) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < 16 * 64; i += 256) {
-            const int r = i >> 6, k = i & 63;
-            xs[r][k] = (r0 + r < L && k0 + k < K) ? X[(size_t)(r0 + r) * ldx + k0 + k] : 0.f;
-        }
-        __syncthreads();
-        if (c < N) {
-            const int kn = K - k0 < 64 ? K - k0 : 64;
-            for (int k = 0; k < kn; ++k) {
-                const float w = Wt[(size_t)(k0 + k) * ldw + c];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j] = fmaf(w, xs[rq * 4 + j][k], acc[j]);
-            }
-        }
-    }
-    if (c >= N) return;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int r = r0 + rq * 4 + j;
-        if (r >= L) continue;
-        float v = acc[j] + (bias ? bias[c] : 0.f);
-        if (ACT == 1) v = v > 0.f ? v : 0.01f * v;
-        if (G) v *= G[(size_t)r * ldg + c] > 0.f ? 1.f : 0.01f;
-        Y[(size_t)r * ldy + c] = v;
-    }
-}
-
-// decoder output -> pose_body axis-angle (needed from the NEIGHBOUR frames by the temporal term)
-__global__ void fit_aa_kernel(const float* __restrict__ O, int ldo, float* __restrict__ aa_out, int L) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= L * NB) return;
-    const int f = i / NB, j = i - f * NB;
-    const float* o = O + (size_t)f * ldo + 6 * j;
-    const GS g = gs_fwd(v3(o[0], o[2], o[4]), v3(o[1], o[3], o[5]));
-    const float R[9] = {g.b1.x, g.b2.x, g.b3.x, g.b1.y, g.b2.y, g.b3.y, g.b1.z, g.b2.z, g.b3.z};
-    const AA a = aa_fwd(R);
-    aa_out[(size_t)i * 3 + 0] = a.aa.x; aa_out[(size_t)i * 3 + 1] = a.aa.y; aa_out[(size_t)i * 3 + 2] = a.aa.z;
 }
 
 __global__ void __launch_bounds__(64) fit_frame_kernel(const FitArgs a, int it) {
@@ -396,17 +349,23 @@ __global__ void __launch_bounds__(64) fit_frame_kernel(const FitArgs a, int it) 
     (void)red;
 }
 
-// Adam (torch.optim.Adam, lr 0.01, betas 0.9 / 0.999, eps 1e-8) over [z | phi | tau | beta]; z joins at the switch.
-__global__ void fit_adam_kernel(const FitArgs a, int step, int with_z) {
+// The two bias corrections of an Adam step, formed on the host in double: ss = lr / (1 - 0.9^step), rb = 1 / sqrt(1 - 0.999^step).
+// In fp32, 1 - 0.999f^step keeps the rounding of 0.999f (1.3e-8) against a difference of 1e-3 step: the first steps came out 6e-6 of
+// their length too short, a hundred times fp32's own error, and the next gradient saw it (tests/test_fit_fp64.py).
+struct AdamScales { float ss, rb; };
+static AdamScales adam_scales(float lr, int step) {
+    return AdamScales{(float)((double)lr / (1.0 - pow(0.9, (double)step))), (float)(1.0 / sqrt(1.0 - pow(0.999, (double)step)))};
+}
+
+// Adam (torch.optim.Adam, lr 0.01, betas 0.9 / 0.999, eps 1e-8) over [phi | tau | beta] of the vector [z | phi | tau | beta]: the
+// optimiser before the switch.  z joins at the switch, from where fit_backprop_adam_kernel takes the step.
+__global__ void fit_adam_kernel(const FitArgs a, const AdamScales sc) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int L = a.L, nz = L * 32, nphi = 2 * L * 6, ntau = 2 * L * 3, total = nz + nphi + ntau + 10;
     if (i >= total) return;
     float* p; float gr;
-    if (i < nz) {
-        if (!with_z) return;
-        p = a.z + i;
-        gr = a.dz[(size_t)(i / 32) * a.ldz + (i & 31)] + a.w_vposer * 2.f * a.z[i] / (float)nz;     // + VPoser prior mean(z^2)
-    } else if (i < nz + nphi) { p = a.phi + (i - nz); gr = a.dphi[i - nz]; }
+    if (i < nz) return;
+    if (i < nz + nphi) { p = a.phi + (i - nz); gr = a.dphi[i - nz]; }
     else if (i < nz + nphi + ntau) { p = a.tau + (i - nz - nphi); gr = a.dtau[i - nz - nphi]; }
     else {
         const int k = i - nz - nphi - ntau;
@@ -424,8 +383,7 @@ __global__ void fit_adam_kernel(const FitArgs a, int step, int with_z) {
     m = 0.9f * m + 0.1f * gr;
     v = 0.999f * v + 0.001f * gr * gr;
     a.adam_m[i] = m; a.adam_v[i] = v;
-    const float bc1 = 1.f - powf(0.9f, (float)step), bc2 = 1.f - powf(0.999f, (float)step);
-    *p -= (a.lr / bc1) * m / (sqrtf(v) / sqrtf(bc2) + 1e-8f);
+    *p -= sc.ss * m / (sqrtf(v) * sc.rb + 1e-8f);
     if (a.grad_out) a.grad_out[i] = gr;
 }
 
@@ -516,7 +474,7 @@ __global__ void __launch_bounds__(1024) fit_decode_kernel(const float* __restric
         if (r0 + r < L) O[(size_t)(r0 + r) * 128 + o] = v;
     }
     __syncthreads();
-    if (t < DR * NB) {                                       // matrot2aa of the Gram-Schmidt rotations (fit_aa_kernel)
+    if (t < DR * NB) {                                       // matrot2aa of the Gram-Schmidt rotations
         const int r = t / NB, j = t - r * NB;
         if (r0 + r < L) {
             const float* o = os + r * 128 + 6 * j;
@@ -529,17 +487,17 @@ __global__ void __launch_bounds__(1024) fit_decode_kernel(const float* __restric
     }
 }
 
-// dO -> dH2 -> dH1 -> dz, then Adam on every optimised quantity of the workgroup's rows (and beta in workgroup 0).
+// dO -> d2 -> d1 -> dz (d2, d1: the gradients at the two hidden layers H2, H1), then Adam on every optimised quantity of the workgroup's rows (and beta in workgroup 0).
 // Weights as torch stores them ([out][in]) ARE k-major for the transposed products.
 __global__ void __launch_bounds__(1024) fit_backprop_adam_kernel(const FitArgs a, const float* __restrict__ w3, const float* __restrict__ w2,
                                                                  const float* __restrict__ w1, const float* __restrict__ H1,
-                                                                 const float* __restrict__ H2, int step) {
+                                                                 const float* __restrict__ H2, const AdamScales sc) {
     extern __shared__ float lds[];
     float* red = lds; float* dzs = red + 16384; float* d2 = dzs + DR * 32; float* d1 = d2 + DR * 512; float* dos = d1 + DR * 512;
     const int t = threadIdx.x, r0 = blockIdx.x * DR, L = a.L;
     if (t < DR * 128) { const int r = t >> 7, c = t & 127; dos[r * 128 + c] = (r0 + r < L && c < 126) ? a.dO[(size_t)(r0 + r) * a.ldo + c] : 0.f; }
     __syncthreads();
-    layer_partial<512, 128, 128>(w3, dos, red, 126);         // dH2 = (dO W3) * lrelu'(H2)
+    layer_partial<512, 128, 128>(w3, dos, red, 126);         // d2 = (dO W3) * lrelu'(H2)
     __syncthreads();
     for (int i = t; i < DR * 512; i += 1024) {
         const int r = i >> 9, o = i & 511;
@@ -547,7 +505,7 @@ __global__ void __launch_bounds__(1024) fit_backprop_adam_kernel(const FitArgs a
         d2[r * 512 + o] = layer_sum<512>(red, r, o) * (hact > 0.f ? 1.f : 0.01f);
     }
     __syncthreads();
-    layer_partial<512, 512, 512>(w2, d2, red, 512);          // dH1 = (dH2 W2) * lrelu'(H1)
+    layer_partial<512, 512, 512>(w2, d2, red, 512);          // d1 = (d2 W2) * lrelu'(H1)
     __syncthreads();
     for (int i = t; i < DR * 512; i += 1024) {
         const int r = i >> 9, o = i & 511;
@@ -555,7 +513,7 @@ __global__ void __launch_bounds__(1024) fit_backprop_adam_kernel(const FitArgs a
         d1[r * 512 + o] = layer_sum<512>(red, r, o) * (hact > 0.f ? 1.f : 0.01f);
     }
     __syncthreads();
-    layer_partial<32, 512, 512>(w1, d1, red, 512);           // dz = dH1 W1
+    layer_partial<32, 512, 512>(w1, d1, red, 512);           // dz = d1 W1
     __syncthreads();
     if (t < DR * 32) { const int r = t >> 5, c = t & 31; dzs[r * 32 + c] = layer_sum<32>(red, r, c); }
     __syncthreads();
@@ -587,32 +545,20 @@ __global__ void __launch_bounds__(1024) fit_backprop_adam_kernel(const FitArgs a
         m = 0.9f * m + 0.1f * gr;
         v = 0.999f * v + 0.001f * gr * gr;
         a.adam_m[i] = m; a.adam_v[i] = v;
-        const float bc1 = 1.f - powf(0.9f, (float)step), bc2 = 1.f - powf(0.999f, (float)step);
-        *p -= (a.lr / bc1) * m / (sqrtf(v) / sqrtf(bc2) + 1e-8f);
+        *p -= sc.ss * m / (sqrtf(v) * sc.rb + 1e-8f);
         if (a.grad_out) a.grad_out[i] = gr;
     }
 }
 
 }  // namespace
 
-hipError_t ap_launch_fit_linear(const float* X, int ldx, int K, const float* Wt, int ldw, const float* bias, const float* G,
-                                int ldg, float* Y, int ldy, int L, int N, int act, hipStream_t st) {
-    const dim3 grid((N + 63) / 64, (L + 15) / 16);
-    if (act) hipLaunchKernelGGL(fit_linear_kernel<1>, grid, dim3(256), 0, st, X, ldx, K, Wt, ldw, bias, G, ldg, Y, ldy, L, N);
-    else hipLaunchKernelGGL(fit_linear_kernel<0>, grid, dim3(256), 0, st, X, ldx, K, Wt, ldw, bias, G, ldg, Y, ldy, L, N);
-    return hipGetLastError();
-}
-hipError_t ap_launch_fit_aa(const float* O, int ldo, float* aa, int L, hipStream_t st) {
-    hipLaunchKernelGGL(fit_aa_kernel, dim3((L * NB + 127) / 128), dim3(128), 0, st, O, ldo, aa, L);
-    return hipGetLastError();
-}
 hipError_t ap_launch_fit_frame(const FitArgs& a, int it, hipStream_t st) {
     hipLaunchKernelGGL(fit_frame_kernel, dim3(a.L), dim3(64), 0, st, a, it);
     return hipGetLastError();
 }
-hipError_t ap_launch_fit_adam(const FitArgs& a, int step, int with_z, hipStream_t st) {
+hipError_t ap_launch_fit_adam(const FitArgs& a, int step, hipStream_t st) {
     const int total = a.L * 32 + 2 * a.L * 9 + 10;
-    hipLaunchKernelGGL(fit_adam_kernel, dim3((total + 255) / 256), dim3(256), 0, st, a, step, with_z);
+    hipLaunchKernelGGL(fit_adam_kernel, dim3((total + 255) / 256), dim3(256), 0, st, a, adam_scales(a.lr, step));
     return hipGetLastError();
 }
 
@@ -627,6 +573,6 @@ hipError_t ap_launch_fit_backprop_adam(const FitArgs& a, const float* w3, const 
                                        const float* H2, int step, hipStream_t st) {
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(fit_backprop_adam_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, FIT_LDS_FLOATS * 4);
     if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(fit_backprop_adam_kernel, dim3((a.L + DR - 1) / DR), dim3(1024), FIT_LDS_FLOATS * 4, st, a, w3, w2, w1, H1, H2, step);
+    hipLaunchKernelGGL(fit_backprop_adam_kernel, dim3((a.L + DR - 1) / DR), dim3(1024), FIT_LDS_FLOATS * 4, st, a, w3, w2, w1, H1, H2, adam_scales(a.lr, step));
     return hipGetLastError();
 }

@@ -305,9 +305,8 @@ struct FitArgs {
     // VPoser decoder output / its gradient, [L][ldo] (126 used), and pose_body of every frame [L][21][3]
     const float* O; float* dO; int ldo;
     const float* aa_all;
-    // optimised state: z [L][32], phi [2][L][6], tau [2][L][3], beta [10]; gradients alongside
+    // optimised state: z [L][32], phi [2][L][6], tau [2][L][3], beta [10]; gradients alongside (dz stays inside the decoder backward)
     float *z, *phi, *tau, *beta;
-    const float* dz; int ldz;
     float *dphi, *dtau, *dbeta_part;   // dbeta_part [L][10] (summed by the Adam kernel)
     float* loss_part;             // [L][4]: 2-D | temporal(pose_body) | temporal(phi, tau) | -
     // body model: rest joints J = j_template + j_shapedirs beta (first 24 chain joints)
@@ -319,11 +318,8 @@ struct FitArgs {
     float *adam_m, *adam_v;       // [L*32 + 2*L*9 + 10]
     float* grad_out;              // optional copy of the gradient vector (tests)
 };
-hipError_t ap_launch_fit_linear(const float* X, int ldx, int K, const float* Wt, int ldw, const float* bias, const float* G,
-                                int ldg, float* Y, int ldy, int L, int N, int act, hipStream_t st);
-hipError_t ap_launch_fit_aa(const float* O, int ldo, float* aa, int L, hipStream_t st);
 hipError_t ap_launch_fit_frame(const FitArgs& a, int it, hipStream_t st);
-hipError_t ap_launch_fit_adam(const FitArgs& a, int step, int with_z, hipStream_t st);
+hipError_t ap_launch_fit_adam(const FitArgs& a, int step, hipStream_t st);     // phi, tau, beta (before the switch)
 // fused decoder passes: one launch for z -> H1, H2, O, pose_body; one for dO -> dz followed by Adam on every quantity
 hipError_t ap_launch_fit_decode(const float* z, int L, const float* w1t, const float* b1, const float* w2t, const float* b2,
                                 const float* w3t, const float* b3, float* H1, float* H2, float* O, float* aa, hipStream_t st);
