@@ -11,6 +11,7 @@ Public mirrors of the reference interfaces:
   EvalMetrics (eval_metrics.py)        <- test_epoch_end of the four trainers: MPJPE, MPE, angle error
   Renderer (renderer.py)               <- utils/renderer.py Renderer: visualize_tb of the trainers' summaries(), without pyrender
   MeshMetrics (mesh_metrics.py)        <- no counterpart in the reference: MPJPE / PVE, absolute, root- and Procrustes-aligned
+  AirPosePlusSequence (sequence.py)    <- copenet_real_data/scripts/bundle_adj.py around its loop: network outputs in, fitted bodies out
 The compute lives in libairpose_hip.so (include/airpose_hip.h); nothing here falls back to CPU.
 """
 __version__ = "0.1.0"
@@ -36,4 +37,7 @@ def __getattr__(name):
     if name == "MeshMetrics":                                             # likewise (mesh_metrics.py)
         from .mesh_metrics import MeshMetrics
         return MeshMetrics
+    if name == "AirPosePlusSequence":                                     # likewise (sequence.py)
+        from .sequence import AirPosePlusSequence
+        return AirPosePlusSequence
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

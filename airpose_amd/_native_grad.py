@@ -83,7 +83,11 @@ SIGNATURES = {
     "apg_align_workspace_bytes": (_i64, [_i, _i, _i]),
     "apg_align_acc_doubles": (_i64, []),
     "apg_align_update": (_i, [_i, _i, _i] + [_i64] * 4 + [_vpp] + [_vp] * 4 + [_i64, _vp]),
+    # AirPose+ on a whole sequence (seq_fit.hip)
+    "apg_seq_init": (_i, [_i] + [_vp] * 9 + [_f, _f] + [_vp] * 5 + [_vp]),
+    "apg_seq_export": (_i, [_i] + [_vp] * 13 + [_vp]),
 }
+SEQ_ROWS = 4             # include/airpose_grad.h: APG_SEQ_ROWS
 PRECISIONS = {"fp32": 0, "bf16": 1}          # include/airpose_grad.h: APG_PREC_*
 
 ABI_VERSION = 2          # include/airpose_grad.h: APG_ABI_VERSION

@@ -578,6 +578,47 @@ int apg_align_update(int B, int views, int N, int64_t pred_stride, int64_t gt_st
                      int64_t gt_root_stride, const void* const* per_view, float* err, float* transform, double* acc, void* workspace,
                      int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * AirPose+ on a whole sequence (seq_fit.hip): the per-frame work on either side of the fitting loop (ap_fit_run of
+ * libairpose_hip.so) -- the loop's initial state and filtered detections from the network's outputs (bundle_adj.py:176-200,
+ * copenet_real.py:105-106) and the fitted bodies under the names the rest of the package reads (bundle_adj.py:404-412, 510-516).
+ * Additive under ABI 2: a binding tells a library that has it by looking up apg_seq_init.  Two stateless entry points, no workspace;
+ * all pointers are device pointers to contiguous fp32 (robust: int32), 4-byte aligned unless stated.  1 <= L <= 2^22.
+ *
+ * apg_seq_init, per frame l:
+ *   angles0, angles1 (L, 22, 3): axis-angle, joint 0 the root.  trans0, trans1 (L, 3).
+ *   det (2 views, L, 2 detectors, 24, 3) = x, y, confidence; detector 0 is OpenPose, detector 1 AlphaPose.
+ *   W1 (512, 63), b1 (512), Wmu (32, 512; 16-byte aligned), bmu (32): VPoser's encoder in eval mode folded into two affine maps
+ *     (mu rows only).
+ *   z (L, 32)      = Wmu leaky_0.01(W1 angles0[l, 1:22] + b1) + bmu: the posterior mean of view 0's body pose.
+ *   phi (2, L, 6)  = the first two ROWS of R(angles_v[l, 0]), row-major (pytorch3d matrix_to_rotation_6d), with R pytorch3d 0.3.0's
+ *     axis_angle_to_matrix: q = (cos(t / 2), r sin(t / 2) / t), t = |r|, sin(t / 2) / t replaced by 1/2 - t^2 / 48 for t < 1e-6,
+ *     then quaternion_to_matrix with two_s = 2 / |q|^2.  r = 0 gives the identity exactly.
+ *   tau (2, L, 3)  = trans_v, bit for bit.
+ *   j2d (2, L, 2, 24, 3) = det with the confidence of BOTH detectors set to 0 where sqrt(dx^2 + dy^2) > agreement_px between the two
+ *     detectors' positions of that view, frame and joint (strict); x and y bit for bit.  j2d must not be det.
+ *   robust (L) int32 = 1 iff the filtered AlphaPose confidences, added in the order view 0 joint 0 .. 23, view 1 joint 0 .. 23 in
+ *     fp32, are > robust_conf (strict), else 0.
+ * apg_seq_export, per frame l:
+ *   z (L, 32), phi (2, L, 6), tau (2, L, 3) as the fitter returns them; w1 (512, 32), b1, w2 (512, 512), b2, w3 (126, 512), b3: the
+ *     VPoser decoder's Linear layers as torch stores them (w1, w2, w3: 16-byte aligned).
+ *   thetas (L, 63)          = decode(z)["pose_body"]: the MLP (LeakyReLU 0.01), Gram-Schmidt on the (21, 3, 2) reshape, tgm 0.1.2's
+ *     rotation_matrix_to_angle_axis -- the formulae of the fitter's own decoder.
+ *   root_rot (2, L, 3, 3)   = pytorch3d rotation_6d_to_matrix(phi): rows b1, b2, b1 x b2.
+ *   smpl_wrt_cam (2, L, 4, 4) = [root_rot | tau; 0 0 0 1].
+ *   cam1_wrt_cam0 (L, 4, 4) = smpl_wrt_cam0 smpl_wrt_cam1^-1, the inverse formed as the rigid [R^T | -R^T t].
+ * APG_SEQ_ROWS frames share a workgroup; every sum has a fixed order and there is no atomic, so every output is bit-identical from
+ * run to run.  One launch each on `stream`, no host synchronisation.
+ * APG_EINVAL before any GPU call, the message naming the argument: L outside the limits, a NULL or misaligned pointer,
+ * agreement_px negative or not finite, robust_conf not finite, j2d == det. */
+#define APG_SEQ_ROWS 4
+int apg_seq_init(int L, const float* angles0, const float* angles1, const float* trans0, const float* trans1, const float* det,
+                 const float* W1, const float* b1, const float* Wmu, const float* bmu, float agreement_px, float robust_conf, float* z,
+                 float* phi, float* tau, float* j2d, int* robust, void* stream);
+int apg_seq_export(int L, const float* z, const float* phi, const float* tau, const float* w1, const float* b1, const float* w2,
+                   const float* b2, const float* w3, const float* b3, float* thetas, float* root_rot, float* smpl_wrt_cam,
+                   float* cam1_wrt_cam0, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
