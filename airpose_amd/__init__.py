@@ -12,6 +12,8 @@ Public mirrors of the reference interfaces:
   Renderer (renderer.py)               <- utils/renderer.py Renderer: visualize_tb of the trainers' summaries(), without pyrender
   MeshMetrics (mesh_metrics.py)        <- no counterpart in the reference: MPJPE / PVE, absolute, root- and Procrustes-aligned
   AirPosePlusSequence (sequence.py)    <- copenet_real_data/scripts/bundle_adj.py around its loop: network outputs in, fitted bodies out
+  RealSequenceBatches (real_batches.py) <- copenet_real/dsets/copenet_real.py __getitem__ and its agreement filter: frames and raw
+                                          detections in, the batch dict of TwoViewInference / RealDataLoss out, boxes kept on the device
 The compute lives in libairpose_hip.so (include/airpose_hip.h); nothing here falls back to CPU.
 """
 __version__ = "0.1.0"
@@ -40,4 +42,7 @@ def __getattr__(name):
     if name == "AirPosePlusSequence":                                     # likewise (sequence.py)
         from .sequence import AirPosePlusSequence
         return AirPosePlusSequence
+    if name == "RealSequenceBatches":                                     # likewise (real_batches.py)
+        from .real_batches import RealSequenceBatches
+        return RealSequenceBatches
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

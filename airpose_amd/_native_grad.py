@@ -86,8 +86,12 @@ SIGNATURES = {
     # AirPose+ on a whole sequence (seq_fit.hip)
     "apg_seq_init": (_i, [_i] + [_vp] * 9 + [_f, _f] + [_vp] * 5 + [_vp]),
     "apg_seq_export": (_i, [_i] + [_vp] * 13 + [_vp]),
+    # real-data batches (seq_batch.hip); principal and size are HOST arrays
+    "apg_real_batch": (_i, [_i, _i, _i, _vp, _c.POINTER(_f), _ip, _f, _i] + [_vp] * 6 + [_vp]),
 }
 SEQ_ROWS = 4             # include/airpose_grad.h: APG_SEQ_ROWS
+BATCH_WAVES = 4          # include/airpose_grad.h: APG_BATCH_WAVES
+BATCH_FALLBACK, BATCH_CLAMPED, BATCH_WIDENED = 1, 2, 4       # include/airpose_grad.h: APG_BATCH_*, the bits of status
 PRECISIONS = {"fp32": 0, "bf16": 1}          # include/airpose_grad.h: APG_PREC_*
 
 ABI_VERSION = 2          # include/airpose_grad.h: APG_ABI_VERSION

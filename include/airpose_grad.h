@@ -619,6 +619,49 @@ int apg_seq_export(int L, const float* z, const float* phi, const float* tau, co
                    const float* b2, const float* w3, const float* b3, float* thetas, float* root_rot, float* smpl_wrt_cam,
                    float* cam1_wrt_cam0, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Real-data batches (seq_batch.hip): what copenet_real.__getitem__ (copenet_real/dsets/copenet_real.py:162-258) and the agreement
+ * filter of its __init__ (:105-106) compute between the raw detections and the network's inputs, for frames [a, a + n) of an
+ * L-frame sequence and both views, in ONE launch: the filtered detections, the crop box round the surviving OpenPose keypoints, bb,
+ * and the keypoints in crop coordinates.  The boxes stay on the device: ap_preprocess_crops (libairpose_hip.so) reads `crops` as it
+ * is, and nobody validates them on the host, so THE KERNEL guarantees the box invariant below for any bit pattern in det.
+ * Additive under ABI 2: a binding tells a library that has it by looking up apg_real_batch.  Stateless, no workspace; all pointers are
+ * device pointers to contiguous arrays, 4-byte aligned; size and principal are HOST arrays read during the call.
+ *
+ *   det (2 views, L, 2 detectors, 24, 3) fp32 = x, y, confidence, as apg_seq_init takes it; detector 0 is OpenPose, detector 1 AlphaPose.
+ *   principal: HOST (2, 2) = cx, cy per view (K[0, 2], K[1, 2]), > 0 and finite.  size: HOST (2, 2) int = H_v, W_v per view, >= 1.
+ *   agreement_px >= 0 and finite (the reference: 100); border: whole pixels, 0 .. 2^20 (the reference: 50).
+ * per (view v, frame a + i), i < n -- every output is written for every (v, i):
+ *   j2d (2, n, 2, 24, 3)      = det with the confidence of BOTH detectors set to 0 where sqrt(dx^2 + dy^2) > agreement_px (strict); x and
+ *     y bit for bit.  The same arithmetic as apg_seq_init: for the same frames the two j2d are bit-equal.
+ *   crops (2, n, 4) int32     = y0, y1, x0, x1, the layout ap_preprocess_crops reads; crop_info (2, n, 2, 2) int32 = [[y0, x0], [y1, x1]].
+ *     From the filtered OpenPose keypoints with confidence != 0: x0 = max(trunc(min x - border), 0), x1 = min(trunc(max x + border), W),
+ *     y likewise with H; trunc is Python's int(), towards zero, never to nearest (where the clamps leave its operand
+ *     it is >= 0, so floor says the same; min x - border < 0 gives 0 through the clamp).  The sums are formed in fp64, as the
+ *     reference forms them, so they are exact for every fp32 x.  With no such keypoint the set is {0} on both axes (the reference's fallback).
+ *   bb (2, n, 3)              = ((x0 + x1) / 2 / cx - 1, (y0 + y1) / 2 / cy - 1, scale), each operation rounded to fp32 in that order
+ *     (no fused multiply-add); scale = (float)(224.0 / (double)max(y1 - y0, x1 - x0)), the expression of ap_preprocess_crops: the
+ *     two scales are bit-equal.
+ *   j2d_crop (2, n, 2, 24, 3) = for both detectors xy' = scale * (xy - (bb_xy + 1) * c), confidence copied (the filtered one); each
+ *     operation rounded to fp32, no pad offset (the reference applies none).
+ *   status (2, n) int32: bit 0 (APG_BATCH_FALLBACK) no keypoint was used, the fallback box was taken; bit 1 (APG_BATCH_CLAMPED) at
+ *     least one otherwise usable keypoint was non-finite or outside [0, W] x [0, H]; bit 2 (APG_BATCH_WIDENED) the box was empty
+ *     along an axis and was widened to one pixel.
+ * The box invariant, for ANY det: 0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H.  Three rules give it, each the identity wherever the
+ * reference itself works: a keypoint with a non-finite x or y is treated as absent; a finite keypoint outside the frame is clamped
+ * to [0, W] x [0, H] before the minimum and maximum are taken; an axis left with x1 <= x0 (border = 0 on one point, a fallback box
+ * with border = 0) becomes the one pixel [min(x0, W - 1), min(x0, W - 1) + 1).
+ * One wave64 per (view, frame), APG_BATCH_WAVES waves per workgroup, no LDS, no atomic: bit-identical from run to run.  One launch
+ * on `stream`, no host synchronisation.
+ * APG_EINVAL before any GPU call, the message naming the argument: a NULL or misaligned pointer, L outside 1 .. 2^22, n < 1, a < 0, a + n > L, a
+ * frame size < 1 or > 2^20, a principal point not positive and finite, agreement_px negative or not finite, border outside 0 .. 2^20, j2d == det. */
+#define APG_BATCH_WAVES 4
+#define APG_BATCH_FALLBACK 1
+#define APG_BATCH_CLAMPED 2
+#define APG_BATCH_WIDENED 4
+int apg_real_batch(int L, int a, int n, const float* det, const float* principal, const int* size, float agreement_px, int border,
+                  float* j2d, int* crops, int* crop_info, float* bb, float* j2d_crop, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
