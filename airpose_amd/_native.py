@@ -67,6 +67,8 @@ SIGNATURES = {
     "ap_set_conv_config": (_i, [_i]),
     "ap_abi_version": (_i, []),
     "ap_debug_set_trace": (_i, [_vp]),
+    "ap_debug_set_range_hook": (_i, [_i]),
+    "ap_debug_range_status": (_i, [_i, _vp, _i]),
     "ap_net_enable_timing": (_i, [_vp, _i]),
     "ap_net_timing": (_i, [_vp, _c.POINTER(_c.c_double), _i64p, _i]),
     "ap_net_set_chunk": (_i, [_vp, _i]),
@@ -136,7 +138,7 @@ SIGNATURES = {
     "ap_perspective_projection": (_i, [_vp, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp]),
 }
 
-ABI_VERSION = 11         # include/airpose_hip.h: AP_ABI_VERSION
+ABI_VERSION = 12        # include/airpose_hip.h: AP_ABI_VERSION
 _lib = None
 _lib_lock = threading.Lock()
 

@@ -68,7 +68,10 @@ __device__ __forceinline__ float ap_relu(float x) {
 // (Checking only the pooled features at the end of the trunk is not enough: the NaNs an inf turns into downstream carry a set
 // sign bit on this hardware and every ReLU clears them -- measured, tests/test_gpu_parity.py::test_f16_activation_overflow_is_reported.)
 // Use: `uint32_t rng = 0u;` per thread, ap_rng_note(rng, packed_dword) at every store of packed values, ap_rng_flush(flag, rng)
-// at the end of the kernel.  All three compile to nothing in the bf16 translation units.
+// at EVERY exit of the kernel.  What is noted is what is stored (or kept in LDS for the next stage of a fused kernel): a value computed
+// for a masked row or channel of a ragged tile, a halo / padding lane or a padding work unit must not reach the maximum -- note under
+// the store's mask, or keep such lanes' maxima apart and leave them out at the flush (tests/test_range_sentinel.py holds every
+// kernel to both directions).  All three compile to nothing in the bf16 translation units.
 #ifdef AP_F16
 __device__ __forceinline__ void ap_rng_note(uint32_t& m, uint32_t packed) {
     asm("v_pk_max_i16 %0, %0, %1" : "+v"(m) : "v"(packed));

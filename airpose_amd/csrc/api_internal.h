@@ -168,6 +168,9 @@ void pack_stem(const float* w, int prec, StemPack& p, bool* f16_overflow);      
 
 // api_trunk.hip
 extern unsigned long long* g_conv_dbg;   // phase-stamp buffer (ap_debug_set_trace)
+// the library's own host-mapped range word while ap_debug_set_range_hook is on and `prec` is AP_PREC_F16, NULL otherwise: what the
+// stand-alone operator entries (api_ops.hip) hand their kernels as range_flag
+int* ops_range_word(int prec);
 hipError_t zero_line(const void** out);
 hipError_t device_cus(int* n);
 hipError_t dispatch_conv(ConvArgs& a, int prec /* AP_PREC_* */, hipStream_t st);

@@ -5,8 +5,9 @@
 namespace {
 // what the two bottleneck64 entry points fill alike (the zero line is the caller's: its failure is the caller's error)
 BneckArgs bneck_args(const void* x, const void* w1, const float* s1, const float* h1, const void* w2, const float* s2, const float* h2,
-                     const void* w3, const float* s3, const float* h3, void* y, int N, int H, int W) {
+                     const void* w3, const float* s3, const float* h3, void* y, int N, int H, int W, int precision) {
     BneckArgs a{};
+    a.range_flag = ops_range_word(precision);
     a.x = x; a.y = y; a.w1 = w1; a.w2 = w2; a.w3 = w3;
     a.s1 = s1; a.h1 = h1; a.s2 = s2; a.h2 = h2; a.s3 = s3; a.h3 = h3;
     a.N = N; a.H = H; a.W = W; a.dbg = g_conv_dbg;
@@ -35,6 +36,7 @@ int ap_conv2d_nhwc(int precision, const void* x, const void* w, const float* sca
     a.Cout = Cout; a.KH = a.KW = ksize; a.stride = stride; a.pad = pad;
     a.M = N * a.Ho * a.Wo;
     a.ldx = Cin; a.ldy = Cout; a.ldr = Cout; a.wld = ksize * ksize * Cin; a.relu = relu;
+    a.range_flag = ops_range_word(precision);
     HIP_TRY(dispatch_conv(a, precision, (hipStream_t)stream));
     return AP_OK;
 }
@@ -46,7 +48,7 @@ int ap_bottleneck64_nhwc(int precision, const void* x, const void* w1, const flo
         return fail(AP_EINVAL, "ap_bottleneck64_nhwc: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16)");
     if (H <= 0 || W <= 0 || H % 14 || W % 14 || !((Cin == 256 && !downsample) || (Cin == 64 && downsample)))
         return fail(AP_ESHAPE, "ap_bottleneck64_nhwc: H, W multiples of 14; Cin 256 (identity) or 64 (downsample)");
-    BneckArgs a = bneck_args(x, w1, s1, h1, w2, s2, h2, w3, s3, h3, y, N, H, W);
+    BneckArgs a = bneck_args(x, w1, s1, h1, w2, s2, h2, w3, s3, h3, y, N, H, W, precision);
     HIP_TRY(zero_line(&a.zero));
     HIP_TRY(H16(precision, ap_launch_bneck2)(a, downsample ? 1 : 0, (hipStream_t)stream));
     return AP_OK;
@@ -60,7 +62,7 @@ int ap_bottleneck64_tail_nhwc(int precision, const void* x, const void* w1, cons
         !t1n || N <= 0)
         return fail(AP_EINVAL, "ap_bottleneck64_tail_nhwc: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16)");
     if (H <= 0 || W <= 0 || H % 14 || W % 14) return fail(AP_ESHAPE, "ap_bottleneck64_tail_nhwc: H, W multiples of 14");
-    BneckArgs a = bneck_args(x, w1, s1, h1, w2, s2, h2, w3, s3, h3, y, N, H, W);
+    BneckArgs a = bneck_args(x, w1, s1, h1, w2, s2, h2, w3, s3, h3, y, N, H, W, precision);
     a.w1n = w1n; a.s1n = s1n; a.h1n = h1n; a.t1n = t1n; a.y_even = y_even != 0;
     HIP_TRY(zero_line(&a.zero));
     HIP_TRY(H16(precision, ap_launch_bneck2)(a, 0, (hipStream_t)stream));
@@ -86,6 +88,7 @@ int ap_conv_pw_nhwc(int precision, const void* x, const void* wstream, const flo
         return fail(AP_ESHAPE, "ap_conv_pw_nhwc: M must be a multiple of 196, Cin of 128 (>= 256), Cout of 256");
     PwArgs p{};
     p.x = x; p.y = y; p.res = res; p.wfrag = wstream; p.scale = scale; p.shift = shift; p.M = M; p.Cin = Cin; p.Cout = Cout; p.relu = 1;
+    p.range_flag = ops_range_word(precision);
     HIP_TRY(H16(precision, ap_launch_conv_pw)(p, (hipStream_t)stream));
     return AP_OK;
 }
@@ -97,6 +100,7 @@ int ap_conv_pw_ds_nhwc(int precision, const void* t2, const void* x, const void*
     PwArgs p{};
     p.x = t2; p.y = y; p.wfrag = wstream; p.scale = scale; p.shift = shift; p.M = N * Ho * Ho; p.Cin = Cin; p.Cout = Cout; p.relu = 1;
     p.x2 = x; p.Cin2 = Cin2; p.Ho = p.Wo = Ho; p.H2 = p.W2 = Ho * stride; p.stride2 = stride;
+    p.range_flag = ops_range_word(precision);
     if (!k_bf16::ap_conv_pw_ds_supported(p))
         return fail(AP_ESHAPE, "ap_conv_pw_ds_nhwc: N Ho Ho a multiple of 196 with Ho Ho | 196, Cin and Cin2 multiples of 64 (sum: of 128), Cout of 256");
     HIP_TRY(H16(precision, ap_launch_conv_pw)(p, (hipStream_t)stream));
@@ -110,6 +114,7 @@ int ap_conv_pw_k3s2_nhwc(int precision, const void* x, const void* wstream, cons
     PwArgs p{};
     p.k3 = 1; p.Ho = p.Wo = H / 2; p.H2 = p.W2 = H; p.stride2 = 2; p.M = N * p.Ho * p.Wo; p.Cin = Cin; p.Cout = Cout; p.relu = 1;
     p.x = x; p.y = y; p.wfrag = wstream; p.scale = scale; p.shift = shift;
+    p.range_flag = ops_range_word(precision);
     if ((H & 1) || !k_bf16::ap_conv_pw_k3_supported(p))
         return fail(AP_ESHAPE, "ap_conv_pw_k3s2_nhwc: H even with (H / 2)^2 | 196 (14 or 28), N (H / 2)^2 a multiple of 196, Cin / 64 a power of two >= 2, Cout a multiple of 256");
     HIP_TRY(H16(precision, ap_launch_conv_pw)(p, (hipStream_t)stream));
@@ -131,7 +136,7 @@ int ap_block_img_nhwc(int precision, const void* x, const void* wstream, const f
         return fail(AP_EINVAL, "ap_block_img_nhwc: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16)");
     BlkImgArgs a{};
     a.x = x; a.y = y; a.wfrag = wstream; a.s1 = s1; a.h1 = h1; a.s2 = s2; a.h2 = h2; a.s3 = s3; a.h3 = h3; a.N = N;
-    a.dbg = g_conv_dbg;
+    a.dbg = g_conv_dbg; a.range_flag = ops_range_word(precision);
     HIP_TRY(H16(precision, ap_launch_block_img)(a, (hipStream_t)stream));
     return AP_OK;
 }
@@ -152,6 +157,7 @@ int ap_conv_s2p_nhwc(int precision, const void* x, const void* wstream, const fl
         return fail(AP_EINVAL, "ap_conv_s2p_nhwc: bad argument");
     ConvS2pArgs a{};
     a.x = x; a.y = y; a.wfrag = wstream; a.scale = scale; a.shift = shift; a.N = N; a.y_tiled = y_tiled != 0;
+    a.range_flag = ops_range_word(precision);
     HIP_TRY(zero_line(&a.zero));
     HIP_TRY(H16(precision, ap_launch_conv_s2p)(a, (hipStream_t)stream));
     return AP_OK;
@@ -169,6 +175,7 @@ int ap_conv_img3_nhwc(int precision, const void* x, const void* wstream, const f
         return fail(AP_EINVAL, "ap_conv_img3_nhwc: bad argument");
     ConvImg3Args a{};
     a.x = x; a.y = y; a.wfrag = wstream; a.scale = scale; a.shift = shift; a.N = N; a.y_tiled = y_tiled != 0;
+    a.range_flag = ops_range_word(precision);
     HIP_TRY(zero_line(&a.zero));
     HIP_TRY(H16(precision, ap_launch_conv_img3)(a, (hipStream_t)stream));
     return AP_OK;
@@ -214,7 +221,7 @@ int ap_stem_nhwc(int precision, int form, const float* x0, const float* x1, int 
     const int n1 = N - n_split;
     if (half) {
         if (form == 0) HIP_TRY(H16(precision, ap_launch_stem_conv_mfma)(x0, x1, n_split, wpacked, scale, shift, y, N, st));
-        else HIP_TRY(H16(precision, ap_launch_stem_pool)(x0, x1, n_split, wpacked, scale, shift, y, N, nullptr, form, st, nullptr));
+        else HIP_TRY(H16(precision, ap_launch_stem_pool)(x0, x1, n_split, wpacked, scale, shift, y, N, ops_range_word(precision), form, st, nullptr));
     } else if (precision == AP_PREC_BF16X2) {
         const void* wlo = (const char*)wpacked + (size_t)64 * AP_STEM_WLD * 2;
         if (form == 0) HIP_TRY(k_bf16::ap_launch_stem_conv_mfma_split(x0, x1, n_split, wpacked, wlo, scale, shift, y, N, st));
@@ -230,14 +237,14 @@ int ap_stem_nhwc(int precision, int form, const float* x0, const float* x1, int 
 
 int ap_maxpool_nhwc(int precision, const void* x, void* y, int N, void* stream) {
     if (!prec_valid(precision) || !x || !y || N <= 0) return fail(AP_EINVAL, "ap_maxpool_nhwc: bad argument");
-    HIP_TRY(H16(precision, ap_launch_maxpool)(x, y, N, prec_kind(precision), nullptr, (hipStream_t)stream));
+    HIP_TRY(H16(precision, ap_launch_maxpool)(x, y, N, prec_kind(precision), ops_range_word(precision), (hipStream_t)stream));
     return AP_OK;
 }
 
 int ap_avgpool_nhwc(int precision, const void* x, float* y, int N, int C, void* stream) {
     if (!prec_valid(precision) || !x || !y || N <= 0) return fail(AP_EINVAL, "ap_avgpool_nhwc: bad argument");
     if (C <= 0 || C % (precision == AP_PREC_FP32 ? 128 : 256)) return fail(AP_ESHAPE, "ap_avgpool_nhwc: C a multiple of 256 (fp32: 128)");
-    HIP_TRY(H16(precision, ap_launch_avgpool)(x, y, N, C, prec_kind(precision), nullptr, (hipStream_t)stream));
+    HIP_TRY(H16(precision, ap_launch_avgpool)(x, y, N, C, prec_kind(precision), ops_range_word(precision), (hipStream_t)stream));
     return AP_OK;
 }
 
@@ -265,7 +272,7 @@ int ap_conv_pair_nhwc(int precision, const void* t2, const void* wstream, const 
     if (!k_bf16::ap_conv_pair_supported(P, 0, 4 * P, N1)) return fail(AP_ESHAPE, "ap_conv_pair_nhwc: (P, N1) must be (128,128), (128,256) or (256,256)");
     PairArgs a{};
     a.t2 = t2; a.res = res; a.wstream = wstream; a.s3 = s3; a.h3 = h3; a.s1 = s1; a.h1 = h1; a.out = out; a.t1n = t1n; a.M = M;
-    a.dbg = g_conv_dbg;
+    a.dbg = g_conv_dbg; a.range_flag = ops_range_word(precision);
     HIP_TRY(H16(precision, ap_launch_conv_pair)(a, P, 0, 4 * P, N1, (hipStream_t)stream));
     return AP_OK;
 }
@@ -281,7 +288,7 @@ int ap_conv_pair_ds_nhwc(int precision, const void* t2, const void* x, const voi
     PairArgs a{};
     a.t2 = t2; a.x2 = x; a.wstream = wstream; a.s3 = s3; a.h3 = h3; a.s1 = s1; a.h1 = h1; a.out = out; a.t1n = t1n;
     a.M = N * Ho * Ho; a.Ho = a.Wo = Ho; a.H2 = a.W2 = Ho * stride; a.stride2 = stride;
-    a.dbg = g_conv_dbg;
+    a.dbg = g_conv_dbg; a.range_flag = ops_range_word(precision);
     HIP_TRY(H16(precision, ap_launch_conv_pair)(a, P, P2, C3, N1, (hipStream_t)stream));
     return AP_OK;
 }

@@ -11,7 +11,15 @@ namespace {
 // torn setting.
 std::atomic<int> g_conv_mode{-1};
 void* g_zero[16] = {nullptr};   // per-device 256-byte zero line
+// ap_debug_set_range_hook: one host-mapped word for the process, allocated on first use and kept; g_ops_range is that word while
+// the hook is on and NULL while it is off (one atomic pointer: a launch sees the old or the new value)
+int* g_ops_word = nullptr;
+std::atomic<int*> g_ops_range{nullptr};
 }  // namespace
+
+int* ap_internal::ops_range_word(int prec) {
+    return prec == AP_PREC_F16 ? g_ops_range.load(std::memory_order_relaxed) : nullptr;
+}
 
 hipError_t ap_internal::zero_line(const void** out) {
     int dev = 0;
@@ -586,6 +594,29 @@ int ap_trunk_fwd_twoview_async(ap_net* h, const float* x0, const float* x1, int 
 int ap_debug_set_trace(void* device_buf_160_u64) {
     g_conv_dbg = (unsigned long long*)device_buf_160_u64;
     return AP_OK;
+}
+
+int ap_debug_set_range_hook(int on) {
+    if (!on) {
+        g_ops_range.store(nullptr, std::memory_order_relaxed);
+        return AP_OK;
+    }
+    if (!g_ops_word) {
+        HIP_TRY(hipHostMalloc((void**)&g_ops_word, sizeof(int), hipHostMallocMapped | hipHostMallocPortable));
+    }
+    __atomic_store_n(g_ops_word, 0, __ATOMIC_RELAXED);
+    g_ops_range.store(g_ops_word, std::memory_order_relaxed);
+    return AP_OK;
+}
+
+int ap_debug_range_status(int precision, void* stream, int reset) {
+    if (!prec_valid(precision)) return fail(AP_EINVAL, "ap_debug_range_status: bad precision");
+    int* word = ops_range_word(precision);
+    if (!word) return AP_OK;                                 // hook off, or a precision without a range to leave
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    const int v = __atomic_load_n(word, __ATOMIC_RELAXED);
+    if (reset) __atomic_store_n(word, 0, __ATOMIC_RELAXED);
+    return v ? AP_ERANGE : AP_OK;
 }
 
 int ap_set_conv_config(int cfg) {

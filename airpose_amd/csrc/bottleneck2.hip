@@ -172,7 +172,10 @@ bneck2_kernel(const BneckArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 15, g4 = lane >> 4;
     const uint32_t lds0 = (uint32_t)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
-    uint32_t rng = 0u;                                       // fp16 range sentinel (ap_common.h); nothing in the bf16 set
+    // fp16 range sentinel (ap_common.h); nothing in the bf16 set.  rng: t1 as written to the LDS; rngq[g]: t2, y and t1n of the wave's
+    // halo row 2 wave + g -- row 0 / 15 and column 0 / 15 of the halo are computed from partial sums and never stored, in any tile, so
+    // they are left out when the rows are folded in at the end of the kernel
+    uint32_t rng = 0u, rngq[2] = {0u, 0u};
 
     // ---------------------------------------------------------------- once per workgroup: W1, W2, BatchNorm tables -> LDS
     // tile = 64 rows x 128 B, row rho = channel b2_row_channel(rho), 16-byte chunk c at position c ^ (rho & 7)
@@ -384,8 +387,10 @@ bneck2_kernel(const BneckArgs a) {
             wait_lgkmcnt<0>();
             sfor<0, 2>([&](auto GG) {
                 constexpr int g = GG;
-                u32x4 o = bn8(acc[g * 4 + 2 * q], acc[g * 4 + 2 * q + 1], tq[0], tq[1], tq[2], tq[3], nullptr, rng);
+                uint32_t unused = 0u;
+                u32x4 o = bn8(acc[g * 4 + 2 * q], acc[g * 4 + 2 * q + 1], tq[0], tq[1], tq[2], tq[3], nullptr, unused);
                 if (!inimg[g]) o = u32x4{0u, 0u, 0u, 0u};    // conv2 pads t1 with zeros, not with conv1 of zeros
+                ap_rng_note2(rng, o.x, o.y); ap_rng_note2(rng, o.z, o.w);   // (the value conv2 reads: not relu(shift) of a pixel outside the image)
                 lds_write_b128<g * 2048>(q ? tw ^ 64u : tw, o);
             });
         });
@@ -425,8 +430,8 @@ bneck2_kernel(const BneckArgs a) {
             constexpr int q = Q;
             rdT(tq, tab, std::integral_constant<int, T_S2 + q * 128>{}, std::integral_constant<int, T_H2 + q * 128>{});
             wait_lgkmcnt<0>();
-            y[q] = bn8(acc[2 * q], acc[2 * q + 1], tq[0], tq[1], tq[2], tq[3], nullptr, rng);
-            y[2 + q] = bn8(acc[4 + 2 * q], acc[4 + 2 * q + 1], tq[0], tq[1], tq[2], tq[3], nullptr, rng);
+            y[q] = bn8(acc[2 * q], acc[2 * q + 1], tq[0], tq[1], tq[2], tq[3], nullptr, rngq[0]);
+            y[2 + q] = bn8(acc[4 + 2 * q], acc[4 + 2 * q + 1], tq[0], tq[1], tq[2], tq[3], nullptr, rngq[1]);
         });
 
         // ------------------------------------------------------------ conv3 in four chunks of 64 channels
@@ -480,7 +485,7 @@ bneck2_kernel(const BneckArgs a) {
                 sfor<0, 2>([&](auto GG) {
                     constexpr int g = GG;
                     const u32x4 o = bn8(acc[g * 4 + 2 * q], acc[g * 4 + 2 * q + 1], tq[0], tq[1], tq[2], tq[3],
-                                        DS ? nullptr : &xc[DS ? 0 : g * 8 + cc * 2 + q], rng);
+                                        DS ? nullptr : &xc[DS ? 0 : g * 8 + cc * 2 + q], rngq[g]);
                     if constexpr (TAIL) xc[g * 8 + cc * 2 + q] = o;      // the block output replaces x: conv1' operand (same fragment)
                     if (B2_ABLATE & 2) asm volatile("" ::"v"(o), "v"(opp.off[g]));
                     else if (B2_ABLATE & 64) {               // shape experiment (data of the wrong pixels): 8 CONSECUTIVE lanes = one 128-byte line
@@ -520,7 +525,7 @@ bneck2_kernel(const BneckArgs a) {
                     wait_lgkmcnt<0>();
                     sfor<0, 2>([&](auto GG) {
                         constexpr int g = GG;
-                        const u32x4 o = bn8(acc[g * 4 + 2 * q], acc[g * 4 + 2 * q + 1], tq[0], tq[1], tq[2], tq[3], nullptr, rng);
+                        const u32x4 o = bn8(acc[g * 4 + 2 * q], acc[g * 4 + 2 * q + 1], tq[0], tq[1], tq[2], tq[3], nullptr, rngq[g]);
                         if (B2_ABLATE & 2) asm volatile("" ::"v"(o), "v"(opp.off1[g]));
                         else __builtin_amdgcn_raw_buffer_store_b128(o, t1rsrc, opp.off1[g] + cb * 128 + q * 64, 0, 0);
                     });
@@ -587,6 +592,10 @@ bneck2_kernel(const BneckArgs a) {
         T = Tn;
     }
     wait_vmcnt<0>();                                         // no LDS-DMA may be in flight when the LDS is released
+    if (lr >= 1 && lr <= 14) {
+        if (wave != 0) ap_rng_note2(rng, rngq[0], rngq[0]);
+        if (wave != 7) ap_rng_note2(rng, rngq[1], rngq[1]);
+    }
     ap_rng_flush(a.range_flag, rng);
 }
 

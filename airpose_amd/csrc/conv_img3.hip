@@ -202,18 +202,20 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         // ================================================================ bn2 + ReLU + 16-bit, 28 stores of 16 bytes per lane
         const bool live = img < a.N && li < CI_HALF;
         const uint32_t col = (uint32_t)(half * CI_HALF + li);
+        uint32_t rngu = 0u;                                  // this half image's share of the sentinel: counted only if it is stored
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int ch = cw * 64 + q * 32 + kq * 8;
 #pragma unroll
             for (int g = 0; g < 14; ++g) {
-                const u32x4 o = bi_bn8(acc[2 * q][g], acc[2 * q + 1][g], bs[q][0], bs[q][1], bh[q][0], bh[q][1], nullptr, rng);
+                const u32x4 o = bi_bn8(acc[2 * q][g], acc[2 * q + 1][g], bs[q][0], bs[q][1], bh[q][0], bh[q][1], nullptr, rngu);
                 const uint32_t m = ((uint32_t)img * CI_H + (uint32_t)(rh * CI_HALF + g)) * CI_H + col;     // linear pixel index
                 const uint32_t off = a.y_tiled ? (uint32_t)(((m >> 4) * (CI_P >> 3) + (uint32_t)(ch >> 3)) * 256u + (m & 15u) * 16u)
                                                : (uint32_t)(m * (CI_P * 2u) + (uint32_t)ch * 2u);
                 __builtin_amdgcn_raw_buffer_store_b128(o, yrsrc, (live && !(CI_ABLATE & 2)) ? off : 0xffffff00u, 0, 0);
             }
         }
+        if (img < a.N) ap_rng_note2(rng, rngu, rngu);        // (a padding half image of the last group computes relu(shift) and stores nothing)
         // the next half image has landed: vector-memory operations retire in order and only this wave's 28 stores are younger than its DMA
         bi_wait_vm<28>();
         __syncthreads();
@@ -221,7 +223,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     bi_wait_vm<0>();                                         // (the ring ran ahead: nothing may land after the exit)
 #pragma unroll
     for (int j = 0; j < CI_RING; ++j) asm volatile("" : "+v"(ar[j][0]), "+v"(ar[j][1]), "+v"(ar[j][2]), "+v"(ar[j][3]));
-    ap_rng_flush(a.range_flag, rng);
+    ap_rng_flush(a.range_flag, li < CI_HALF ? rng : 0u);    // (slots 14, 15 of a row are the halo / padding columns: computed, never stored)
 }
 
 }  // namespace

@@ -446,6 +446,7 @@ __global__ void __launch_bounds__(64 * WAVES_M * WAVES_N) conv_pipe_kernel(const
                 }
             }
         }
+        if constexpr (Elem2<T>::KIND == K_BF16) ap_rng_flush(p.range_flag, rng);
         return;
     }
     AP_BSTAMP(4);
@@ -478,7 +479,6 @@ __global__ void __launch_bounds__(64 * WAVES_M * WAVES_N) conv_pipe_kernel(const
                     o.y = pack_bf16x2(acc[fm][fn][2] * sc.z + sh.z, acc[fm][fn][3] * sc.w + sh.w);
                     asm("v_pk_max_i16 %0, %0, 0" : "+v"(o.x));
                     asm("v_pk_max_i16 %0, %0, 0" : "+v"(o.y));
-                    ap_rng_note2(rng, o.x, o.y);
                     *(uint2*)(c16 + px * CLD16 + chl) = o;
                 }
             }
@@ -491,6 +491,7 @@ __global__ void __launch_bounds__(64 * WAVES_M * WAVES_N) conv_pipe_kernel(const
                 const int m = bm * BM + px, ch = bn * BN + cc * EPC;
                 if (m >= p.M || ch >= p.Cout) continue;
                 const u32x4 o = *(const u32x4*)(c16 + px * CLD16 + cc * EPC);
+                ap_rng_note2(rng, o[0], o[1]); ap_rng_note2(rng, o[2], o[3]);   // (what is STORED: the stage also holds the tile's masked rows / channels)
                 *(u32x4*)(yq + (p.y_tiled ? ap_tiled_off((size_t)m, ch, p.Cout) : (size_t)m * p.ldy + ch)) = o;
             }
             ap_rng_flush(p.range_flag, rng);

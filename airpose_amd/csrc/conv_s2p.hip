@@ -213,6 +213,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
         // ================================================================ bn2 + ReLU + 16-bit, 14 stores of 16 bytes per lane
         const bool live = img < a.N && li < SP_Q;
         const uint32_t col = (uint32_t)(qx * SP_Q + li);
+        uint32_t rngu = 0u;                                  // this quarter's share of the sentinel: counted only if it is stored
         const float* const bn = (const float*)(smem + SP_BN);
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -221,13 +222,14 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
             const f32x4 h0v = *(const f32x4*)(bn + SP_P + ch), h1v = *(const f32x4*)(bn + SP_P + ch + 4);
 #pragma unroll
             for (int g = 0; g < 7; ++g) {
-                const u32x4 o = bi_bn8(acc[2 * q][g], acc[2 * q + 1][g], s0v, s1v, h0v, h1v, nullptr, rng);
+                const u32x4 o = bi_bn8(acc[2 * q][g], acc[2 * q + 1][g], s0v, s1v, h0v, h1v, nullptr, rngu);
                 const uint32_t m = ((uint32_t)img * SP_HO + (uint32_t)(qy * SP_Q + rh * 7 + g)) * SP_HO + col;     // linear pixel index
                 const uint32_t off = a.y_tiled ? (uint32_t)(((m >> 4) * (SP_P >> 3) + (uint32_t)(ch >> 3)) * 256u + (m & 15u) * 16u)
                                                : (uint32_t)(m * (SP_P * 2u) + (uint32_t)ch * 2u);
                 __builtin_amdgcn_raw_buffer_store_b128(o, yrsrc, (live && !(SP_ABLATE & 2)) ? off : 0xffffff00u, 0, 0);
             }
         }
+        if (img < a.N) ap_rng_note2(rng, rngu, rngu);        // (a padding quarter of the last group computes relu(shift) and stores nothing)
         // everything older than this wave's 14 stores has landed (the first ring pieces of the next quarter among it)
         bi_wait_vm<14>();
         __syncthreads();                                     // the fourth barrier of the quarter (the next one's first phase has landed)
@@ -235,7 +237,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
     bi_wait_vm<0>();                                         // (the ring ran ahead: nothing may land after the exit)
 #pragma unroll
     for (int j = 0; j < SP_RING; ++j) asm volatile("" : "+v"(ar[j][0]), "+v"(ar[j][1]), "+v"(ar[j][2]), "+v"(ar[j][3]));
-    ap_rng_flush(a.range_flag, rng);
+    ap_rng_flush(a.range_flag, li < SP_Q ? rng : 0u);       // (slots 14, 15 of a row are junk lanes: computed, never stored)
 }
 
 }  // namespace

@@ -366,8 +366,10 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4)))
                 o.y = pack_bf16x2(acc[fm][fn][2] * sc.z + sh.z, acc[fm][fn][3] * sc.w + sh.w);
                 asm("v_pk_max_i16 %0, %0, 0" : "+v"(o.x));
                 asm("v_pk_max_i16 %0, %0, 0" : "+v"(o.y));
-                ap_rng_note2(rng, o.x, o.y);
-                if (m < p.M && ch < p.Cout) *(uint2*)(yt + ap_tiled_off((size_t)m, ch, p.Cout) + (ch & 7)) = o;
+                if (m < p.M && ch < p.Cout) {                 // (the sentinel sees what is STORED, not the tile's masked rows / channels)
+                    ap_rng_note2(rng, o.x, o.y);
+                    *(uint2*)(yt + ap_tiled_off((size_t)m, ch, p.Cout) + (ch & 7)) = o;
+                }
             }
         }
         ap_rng_flush(p.range_flag, rng);
@@ -396,7 +398,6 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4)))
                 o.y = pack_bf16x2(acc[fm][fn][2] * sc.z + sh.z, acc[fm][fn][3] * sc.w + sh.w);
                 asm("v_pk_max_i16 %0, %0, 0" : "+v"(o.x));
                 asm("v_pk_max_i16 %0, %0, 0" : "+v"(o.y));
-                ap_rng_note2(rng, o.x, o.y);
                 *(uint2*)(c16 + px * CLD16 + chl) = o;
             }
         }
@@ -412,6 +413,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4)))
             const int m = bm * BM + px, ch = bn * BN + cc * 8;
             if (m >= p.M || ch >= p.Cout) continue;
             const u32x4 o = *(const u32x4*)(c16 + px * CLD16 + cc * 8);
+            ap_rng_note2(rng, o[0], o[1]); ap_rng_note2(rng, o[2], o[3]);   // (what is STORED: the stage also holds the tile's masked rows / channels)
             *(u32x4*)(yg + (p.y_tiled ? ap_tiled_off((size_t)m, ch, p.Cout) : (size_t)m * p.ldy + ch)) = o;
         }
         ap_rng_flush(p.range_flag, rng);

@@ -50,12 +50,13 @@ typedef struct ap_net ap_net;     /* ResNet-50 trunk + IEF regressor */
 typedef struct ap_smplx ap_smplx; /* SMPL-X body model */
 
 /* ABI number of this header: bumped whenever an exported signature changes or an entry point is added or removed
- * (11: ap_stem_pack_bytes / ap_stem_pack / ap_stem_nhwc, ap_maxpool_nhwc, ap_avgpool_nhwc -- operator forms of the stem and pooling kernels;
+ * (12: ap_debug_set_range_hook / ap_debug_range_status -- the fp16 range sentinel of the stand-alone operator entries;
+ *  11: ap_stem_pack_bytes / ap_stem_pack / ap_stem_nhwc, ap_maxpool_nhwc, ap_avgpool_nhwc -- operator forms of the stem and pooling kernels;
  *  10: ap_smplx_bwd, ap_batch_rodrigues_bwd -- the adjoints of ap_smplx_fwd and of lbs.batch_rodrigues;
  *  8: round 6 -- ap_net_parity_probe, ap_net_range_peek / _mark_next / _slot, ap_regressor_feat_part / _step_local / _step_finish;
  *  7: ap_conv_pw_*, ap_block_img_*; 6: ap_set_pair_groups removed).  A binding built against another number must refuse to load
  * the library (airpose_amd/_native.py does). */
-#define AP_ABI_VERSION 11
+#define AP_ABI_VERSION 12
 const char* ap_version(void);
 int ap_abi_version(void);
 const char* ap_last_error(void);
@@ -288,7 +289,9 @@ int ap_conv_img3_nhwc(int precision, const void* x, const void* wstream, const f
  *                    1  fused with the max-pool, one workgroup per strip of two pooled rows, y [N][56][56][64]: stem_pool_kernel
  *                       (16-bit), stem_pool_split_kernel (AP_PREC_BF16X2)
  *                    2  fused with the max-pool, persistent workgroups, y [N][56][56][64]: stem_pool2_kernel (16-bit; the trunk's default)
- *                  The fp16 range sentinel is not connected (a handle's business: ap_net_set_range_check).
+ *                  The fp16 range sentinel of forms 1 / 2 (the converted crop values and the pooled maxima) reports through
+ *                  ap_debug_set_range_hook; the un-pooled kernel of form 0 carries none: an inf it stores is the maximum of its
+ *                  window and is reported by the max-pool that follows it (ap_maxpool_nhwc; in a trunk pass, the same two launches).
  * ap_maxpool_nhwc: MaxPool2d(3, stride 2, pad 1), x [N][112][112][64] -> y [N][56][56][64] in the storage type of `precision`.  Domain:
  *                  x >= 0 (post-ReLU values, as in the trunk); the result is one of the inputs, bit for bit.
  * ap_avgpool_nhwc: AvgPool2d(7) + view(B, -1) (model_copenet.py:66, 173-174): x [N][49][C] in the storage type of `precision` -> y [N][C]
@@ -372,6 +375,18 @@ int ap_set_conv_config(int cfg);
 /* Profiling aid: device buffer of 160 uint64 receiving per-phase cycle stamps of workgroup 0 of the pipelined
  * convolution kernel (2 waves x 8 K steps x 10 stamps); NULL (default) disables it. */
 int ap_debug_set_trace(void* device_buf_160_u64);
+/* Test aid: the fp16 range sentinel (see ap_net_set_range_check) of the stand-alone operator entries.  The library owns ONE
+ * host-mapped word for the process.  on != 0 clears it and connects it: from then on every operator entry that launches a kernel
+ * with a sentinel -- ap_conv2d_nhwc, ap_bottleneck64_nhwc / _tail_nhwc, ap_conv_pw_nhwc / _ds_nhwc / _k3s2_nhwc, ap_block_img_nhwc,
+ * ap_conv_img3_nhwc, ap_conv_s2p_nhwc, ap_conv_pair_nhwc / _ds_nhwc, ap_stem_nhwc (forms 1 and 2), ap_maxpool_nhwc, ap_avgpool_nhwc --
+ * hands that word to its kernel when called with AP_PREC_F16, exactly as a trunk pass hands over its handle's; the kernel sets it
+ * when a value it STORES is +-inf or NaN (ap_avgpool_nhwc: when a pooled feature is not finite).  on = 0 (the default) disconnects
+ * it: the entries pass no word, as they always did.  Process-wide (one atomic pointer: a launch sees the old or the new value);
+ * handles are not affected.
+ * ap_debug_range_status synchronises `stream` and returns AP_ERANGE when the word is set, AP_OK otherwise; reset != 0 clears it.
+ * For AP_PREC_FP32 / _BF16 / _BF16X2 (no range to leave), and while the hook is off, it returns AP_OK without synchronising. */
+int ap_debug_set_range_hook(int on);
+int ap_debug_range_status(int precision, void* stream, int reset);
 
 /* Stage timing for bench.py: when enabled, HIP events bracket the stem, the implicit-GEMM conv stack,
  * the pooling tail and the regressor on the caller's stream.  ap_net_timing synchronises on the last

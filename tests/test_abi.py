@@ -127,6 +127,26 @@ def test_conv_config_knob_validates_on_the_host():
         assert L.ap_set_conv_config(-1) == 0
 
 
+def test_range_hook_entries_validate_on_the_host():
+    """ap_debug_set_range_hook / ap_debug_range_status (ABI 12): declared, bound and exported; off is the default and needs no GPU;
+    with the hook off the status is AP_OK for every precision without touching a stream, and a bad precision is AP_EINVAL."""
+    from airpose_amd import _native as Nn
+    L = Nn.lib()
+    assert Nn.ABI_VERSION >= 12 and L.ap_abi_version() >= 12
+    for name in ("ap_debug_set_range_hook", "ap_debug_range_status"):
+        assert name in _declared() and name in Nn.SIGNATURES and hasattr(L, name)
+    assert Nn.SIGNATURES["ap_debug_set_range_hook"][1] == [ctypes.c_int]
+    assert Nn.SIGNATURES["ap_debug_range_status"][1] == [ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+    assert L.ap_debug_set_range_hook(0) == 0
+    for prec in sorted(Nn.PRECISIONS.values()):
+        for reset in (0, 1):
+            assert L.ap_debug_range_status(prec, None, reset) == 0, prec
+    for prec in (-1, 4, 7):
+        assert L.ap_debug_range_status(prec, None, 0) == -1, prec
+    hdr = open(os.path.join(REPO, "include", "airpose_hip.h")).read()
+    assert "sentinel is not connected" not in hdr
+
+
 def test_one_library_carries_both_16bit_storage_types():
     """AP_PREC_F16 is a precision of the ONE library (no second .so, no flavour switch): the enum values are distinct, the
     f16 kernel set (namespace k_f16) is linked in, and the host-only entry points validate the precision argument."""
