@@ -1,5 +1,5 @@
 // What the host translation units of libairpose_hip.so (api_*.hip) share: error reporting, device buffers, the three handle
-// structs and the few functions that cross files.  No kernel and no exported symbol: everything that crosses a file is in
+// structs, the launch functions of the trunk kernels (launch_*: api_ops.hip) and the few other functions that cross files.  No kernel and no exported symbol: everything that crosses a file is in
 // namespace ap_internal with hidden visibility; whatever one file alone uses stays in that file's anonymous namespace.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -67,12 +67,24 @@ struct HostTensor {
     size_t numel() const { return data.size(); }
 };
 
+// one convolution + folded BatchNorm as the launch functions take it: plain pointers and shapes -- a Layer of the trunk, or the
+// arguments of a stand-alone operator entry (w: packed rows, or the fragment stream of the kernel that is launched)
+struct ConvDesc {
+    const void* w;
+    const float *scale, *shift;
+    int cin, cout, k, stride, pad, wld;
+    int cin2, stride2;              // second K segment (downsample folded into conv3)
+};
+
 struct Layer {                  // a conv or linear layer in packed device form
     int cin = 0, cout = 0, k = 1, stride = 1, pad = 0;
     int wld = 0, cout_pad = 0;
     int cin2 = 0, stride2 = 1;      // second K segment (downsample folded into conv3)
     DevBuf w, scale, shift;
     DevBuf pw;                      // pointwise layers of layer3 / layer4: the weights as conv_pw.hip's fragment streams
+    ConvDesc desc(bool pw_stream = false) const {
+        return ConvDesc{pw_stream ? pw.p : w.p, scale.as<float>(), shift.as<float>(), cin, cout, k, stride, pad, wld, cin2, stride2};
+    }
 };
 
 struct Timing {
@@ -173,10 +185,48 @@ extern unsigned long long* g_conv_dbg;   // phase-stamp buffer (ap_debug_set_tra
 int* ops_range_word(int prec);
 hipError_t zero_line(const void** out);
 hipError_t device_cus(int* n);
-hipError_t dispatch_conv(ConvArgs& a, int prec /* AP_PREC_* */, hipStream_t st);
+int conv_mode();                         // the raw value of ap_set_conv_config, read once: a caller decodes ONE value per launch / per pass
+hipError_t dispatch_conv(ConvArgs& a, int prec /* AP_PREC_* */, hipStream_t st, int mode);
+inline hipError_t dispatch_conv(ConvArgs& a, int prec, hipStream_t st) { return dispatch_conv(a, prec, st, conv_mode()); }
 int trunk_fwd(ap_net* h, const float* x0, int n0, const float* x1, int n1, float* feat, hipStream_t st, hipStream_t st_out = nullptr);
 // api_net.hip
 int finalize_trunk(ap_net* h);
+
+// api_ops.hip -- ONE launch function per kernel a trunk pass can run: it fills the kernel's argument struct from plain shapes and
+// pointers, takes the zero line, sets the phase-stamp buffer and calls the launcher.  The pass (api_trunk.hip) calls it with its
+// Layer fields and workspace, the stand-alone operator entry with its validated arguments: a test of the operator is a test of
+// the launch path the trunk runs on.  rflag: the range word of the caller (NULL: none)
+// generic kernels via dispatch_conv.  x2: the block input of a folded downsample (second K segment of c.cin2 channels, H2 x H2,
+// sampled with c.stride2), or NULL.  pool_out: AvgPool2d(7) into [N][cout] fp32 inside the lean kernel where it takes the shape
+// (*pooled = true, y not written); otherwise the plain convolution into y
+hipError_t launch_conv(const ConvDesc& c, const void* x, int N, int H, int W, const void* res, void* y, int relu, int y_tiled,
+                       const void* x2, int H2, float* pool_out, bool* pooled, int prec, int mode, int* rflag, hipStream_t st);
+// conv_pw.hip (c.w: its fragment stream): pointwise (+ identity), pointwise + folded downsample, 3 x 3 / stride 2; *_fits: the
+// kernel's own predicate on the arguments that launch would build
+hipError_t launch_conv_pw(const ConvDesc& c, const void* x, const void* res, void* y, int M, int prec, int* rflag, hipStream_t st);
+bool conv_pw_ds_fits(const ConvDesc& c, int N, int Ho, int H2);
+hipError_t launch_conv_pw_ds(const ConvDesc& c, const void* t, const void* x2, void* y, int N, int Ho, int H2, int prec, int* rflag, hipStream_t st);
+bool conv_pw_k3_fits(const ConvDesc& c, int N, int H);
+hipError_t launch_conv_pw_k3(const ConvDesc& c, const void* x, void* y, int N, int H, int prec, int* rflag, hipStream_t st);
+// bottleneck2.hip (c1 / c2 / c3, and c1n of the tail variant: w, scale, shift only)
+hipError_t launch_bneck2(const ConvDesc& c1, const ConvDesc& c2, const ConvDesc& c3, int ds, const void* x, void* y, int N, int H, int W,
+                         const ConvDesc* c1n, void* t1n, int y_even, int prec, int* rflag, hipStream_t st);
+hipError_t launch_block_img(const void* x, const void* wfrag, const float* s1, const float* h1, const float* s2, const float* h2,
+                            const float* s3, const float* h3, void* y, int N, int prec, int* rflag, hipStream_t st);
+hipError_t launch_conv_img3(const void* x, const void* wfrag, const float* scale, const float* shift, void* y, int N, int y_tiled,
+                            int prec, int* rflag, hipStream_t st);
+hipError_t launch_conv_s2p(const void* x, const void* wfrag, const float* scale, const float* shift, void* y, int N, int y_tiled,
+                           int prec, int* rflag, hipStream_t st);
+// conv_pair.hip: identity block (in = the residual; H2 = 0) or stage-first block (in = the block input [N][H2][H2][P2], sampled with stride2)
+struct PairLayout { int t2_tiled, res_tiled, out_tiled, out_even; };
+hipError_t launch_conv_pair(const void* t2, const void* wstream, const float* s3, const float* h3, const float* s1, const float* h1,
+                            const void* in, void* out, void* t1n, int M, int Ho, int H2, int stride2, int P, int P2, int N1,
+                            PairLayout lay, int prec, int* rflag, hipStream_t st);
+// stem.hip: form 0 un-pooled, 1 a workgroup per strip + max-pool, 2 persistent + max-pool (ap_stem_nhwc); x0: the first n0 of n images
+hipError_t launch_stem(int prec, int form, const float* x0, const float* x1, int n0, int n, const void* w, const void* w_lo,
+                       const float* scale, const float* shift, void* y, int* rflag, hipStream_t st);
+hipError_t launch_maxpool(const void* x, void* y, int n, int prec, int* rflag, hipStream_t st);
+hipError_t launch_avgpool(const void* x, float* y, int n, int C, int prec, int* rflag, hipStream_t st);
 
 }  // namespace ap_internal
 using namespace ap_internal;

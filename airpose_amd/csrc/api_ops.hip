@@ -1,19 +1,142 @@
-// Stand-alone operator entry points of libairpose_hip.so: every kernel a trunk pass can launch on caller-owned tensors (the
-// element-wise tests go through these), and the geometry operators.
+// The launch functions of the trunk kernels (ap_internal::launch_*, declared in api_internal.h): each fills ONE kernel's argument
+// struct and calls its launcher, for the trunk pass (api_trunk.hip) and for the stand-alone operator entry alike.  Below them
+// the operator entry points: every kernel a trunk pass can launch on caller-owned tensors -- validate the arguments, then the
+// shared launch (the element-wise tests go through these) -- and the geometry operators.
 #include "api_internal.h"
 
-namespace {
-// what the two bottleneck64 entry points fill alike (the zero line is the caller's: its failure is the caller's error)
-BneckArgs bneck_args(const void* x, const void* w1, const float* s1, const float* h1, const void* w2, const float* s2, const float* h2,
-                     const void* w3, const float* s3, const float* h3, void* y, int N, int H, int W, int precision) {
-    BneckArgs a{};
-    a.range_flag = ops_range_word(precision);
-    a.x = x; a.y = y; a.w1 = w1; a.w2 = w2; a.w3 = w3;
-    a.s1 = s1; a.h1 = h1; a.s2 = s2; a.h2 = h2; a.s3 = s3; a.h3 = h3;
-    a.N = N; a.H = H; a.W = W; a.dbg = g_conv_dbg;
-    return a;
+hipError_t ap_internal::launch_conv(const ConvDesc& c, const void* x, int N, int H, int W, const void* res, void* y, int relu, int y_tiled,
+                                    const void* x2, int H2, float* pool_out, bool* pooled, int prec, int mode, int* rflag, hipStream_t st) {
+    ConvArgs a{};
+    a.x = x; a.w = c.w; a.scale = c.scale; a.shift = c.shift; a.res = res; a.y = y;
+    a.N = N; a.H = H; a.W = W; a.Cin = c.cin; a.Cout = c.cout;
+    a.Ho = (H + 2 * c.pad - c.k) / c.stride + 1;
+    a.Wo = (W + 2 * c.pad - c.k) / c.stride + 1;
+    a.KH = a.KW = c.k; a.stride = c.stride; a.pad = c.pad;
+    a.M = N * a.Ho * a.Wo;
+    a.ldx = c.cin; a.ldy = c.cout; a.ldr = c.cout; a.wld = c.wld;
+    a.relu = relu; a.y_tiled = y_tiled; a.range_flag = rflag;
+    if (x2) { a.x2 = x2; a.H2 = a.W2 = H2; a.Cin2 = a.ldx2 = c.cin2; a.stride2 = c.stride2; }
+    if (pool_out && k_bf16::ap_conv_lean_supported(a, prec_kind(prec))) {
+        a.y = nullptr; a.pool_out = pool_out; a.dbg = g_conv_dbg;
+        hipError_t e = zero_line(&a.zero);
+        if (e != hipSuccess) return e;
+        *pooled = true;
+        return H16(prec, ap_launch_conv_lean)(a, st);
+    }
+    return dispatch_conv(a, prec, st, mode);
 }
+
+namespace {
+// conv_pw.hip's three forms
+PwArgs pw_args(const ConvDesc& c, const void* x, const void* res, void* y, int M, int* rflag) {
+    PwArgs p{};
+    p.x = x; p.y = y; p.res = res; p.wfrag = c.w; p.scale = c.scale; p.shift = c.shift;
+    p.M = M; p.Cin = c.cin; p.Cout = c.cout; p.relu = 1; p.range_flag = rflag;
+    return p;
+}
+PwArgs pw_ds_args(const ConvDesc& c, const void* t, const void* x2, void* y, int N, int Ho, int H2, int* rflag) {
+    PwArgs p = pw_args(c, t, nullptr, y, N * Ho * Ho, rflag);
+    p.x2 = x2; p.Cin2 = c.cin2; p.Ho = p.Wo = Ho; p.H2 = p.W2 = H2; p.stride2 = c.stride2;
+    return p;
+}
+PwArgs pw_k3_args(const ConvDesc& c, const void* x, void* y, int N, int H, int* rflag) {
+    PwArgs p = pw_args(c, x, nullptr, y, N * (H / 2) * (H / 2), rflag);
+    p.k3 = 1; p.Ho = p.Wo = H / 2; p.H2 = p.W2 = H; p.stride2 = 2;
+    return p;
+}
+const char g_any = 0;   // the shape predicates only ask that an operand exists
 }  // namespace
+
+hipError_t ap_internal::launch_conv_pw(const ConvDesc& c, const void* x, const void* res, void* y, int M, int prec, int* rflag, hipStream_t st) {
+    return H16(prec, ap_launch_conv_pw)(pw_args(c, x, res, y, M, rflag), st);
+}
+bool ap_internal::conv_pw_ds_fits(const ConvDesc& c, int N, int Ho, int H2) {
+    return k_bf16::ap_conv_pw_ds_supported(pw_ds_args(c, &g_any, &g_any, nullptr, N, Ho, H2, nullptr));
+}
+hipError_t ap_internal::launch_conv_pw_ds(const ConvDesc& c, const void* t, const void* x2, void* y, int N, int Ho, int H2, int prec,
+                                          int* rflag, hipStream_t st) {
+    return H16(prec, ap_launch_conv_pw)(pw_ds_args(c, t, x2, y, N, Ho, H2, rflag), st);
+}
+bool ap_internal::conv_pw_k3_fits(const ConvDesc& c, int N, int H) {
+    return !(H & 1) && k_bf16::ap_conv_pw_k3_supported(pw_k3_args(c, &g_any, nullptr, N, H, nullptr));
+}
+hipError_t ap_internal::launch_conv_pw_k3(const ConvDesc& c, const void* x, void* y, int N, int H, int prec, int* rflag, hipStream_t st) {
+    return H16(prec, ap_launch_conv_pw)(pw_k3_args(c, x, y, N, H, rflag), st);
+}
+
+hipError_t ap_internal::launch_bneck2(const ConvDesc& c1, const ConvDesc& c2, const ConvDesc& c3, int ds, const void* x, void* y, int N,
+                                      int H, int W, const ConvDesc* c1n, void* t1n, int y_even, int prec, int* rflag, hipStream_t st) {
+    BneckArgs a{};
+    a.x = x; a.y = y; a.w1 = c1.w; a.w2 = c2.w; a.w3 = c3.w;
+    a.s1 = c1.scale; a.h1 = c1.shift; a.s2 = c2.scale; a.h2 = c2.shift; a.s3 = c3.scale; a.h3 = c3.shift;
+    a.N = N; a.H = H; a.W = W; a.range_flag = rflag; a.dbg = g_conv_dbg;
+    if (c1n) { a.w1n = c1n->w; a.s1n = c1n->scale; a.h1n = c1n->shift; a.t1n = t1n; a.y_even = y_even; }
+    hipError_t e = zero_line(&a.zero);
+    if (e != hipSuccess) return e;
+    return H16(prec, ap_launch_bneck2)(a, ds, st);
+}
+
+hipError_t ap_internal::launch_block_img(const void* x, const void* wfrag, const float* s1, const float* h1, const float* s2, const float* h2,
+                                         const float* s3, const float* h3, void* y, int N, int prec, int* rflag, hipStream_t st) {
+    BlkImgArgs a{};
+    a.x = x; a.y = y; a.wfrag = wfrag; a.s1 = s1; a.h1 = h1; a.s2 = s2; a.h2 = h2; a.s3 = s3; a.h3 = h3; a.N = N;
+    a.range_flag = rflag; a.dbg = g_conv_dbg;
+    return H16(prec, ap_launch_block_img)(a, st);
+}
+
+hipError_t ap_internal::launch_conv_img3(const void* x, const void* wfrag, const float* scale, const float* shift, void* y, int N, int y_tiled,
+                                         int prec, int* rflag, hipStream_t st) {
+    ConvImg3Args a{};
+    a.x = x; a.y = y; a.wfrag = wfrag; a.scale = scale; a.shift = shift; a.N = N; a.y_tiled = y_tiled; a.range_flag = rflag;
+    hipError_t e = zero_line(&a.zero);
+    if (e != hipSuccess) return e;
+    return H16(prec, ap_launch_conv_img3)(a, st);
+}
+
+hipError_t ap_internal::launch_conv_s2p(const void* x, const void* wfrag, const float* scale, const float* shift, void* y, int N, int y_tiled,
+                                        int prec, int* rflag, hipStream_t st) {
+    ConvS2pArgs a{};
+    a.x = x; a.y = y; a.wfrag = wfrag; a.scale = scale; a.shift = shift; a.N = N; a.y_tiled = y_tiled; a.range_flag = rflag;
+    hipError_t e = zero_line(&a.zero);
+    if (e != hipSuccess) return e;
+    return H16(prec, ap_launch_conv_s2p)(a, st);
+}
+
+hipError_t ap_internal::launch_conv_pair(const void* t2, const void* wstream, const float* s3, const float* h3, const float* s1, const float* h1,
+                                         const void* in, void* out, void* t1n, int M, int Ho, int H2, int stride2, int P, int P2, int N1,
+                                         PairLayout lay, int prec, int* rflag, hipStream_t st) {
+    PairArgs a{};
+    a.t2 = t2; a.wstream = wstream; a.s3 = s3; a.h3 = h3; a.s1 = s1; a.h1 = h1; a.out = out; a.t1n = t1n; a.M = M;
+    a.Ho = a.Wo = Ho;
+    if (H2) { a.x2 = in; a.H2 = a.W2 = H2; a.stride2 = stride2; }
+    else a.res = in;
+    a.t2_tiled = lay.t2_tiled; a.res_tiled = lay.res_tiled; a.out_tiled = lay.out_tiled; a.out_even = lay.out_even;
+    a.dbg = g_conv_dbg; a.range_flag = rflag;
+    return H16(prec, ap_launch_conv_pair)(a, P, P2, 4 * P, N1, st);
+}
+
+hipError_t ap_internal::launch_stem(int prec, int form, const float* x0, const float* x1, int n0, int n, const void* w, const void* w_lo,
+                                    const float* scale, const float* shift, void* y, int* rflag, hipStream_t st) {
+    if (prec_half(prec)) {
+        if (form == 0) return H16(prec, ap_launch_stem_conv_mfma)(x0, x1, n0, w, scale, shift, y, n, st);
+        return H16(prec, ap_launch_stem_pool)(x0, x1, n0, w, scale, shift, y, n, rflag, form, st, g_conv_dbg);
+    }
+    if (prec == AP_PREC_BF16X2) {
+        if (form == 0) return k_bf16::ap_launch_stem_conv_mfma_split(x0, x1, n0, w, w_lo, scale, shift, y, n, st);
+        return k_bf16::ap_launch_stem_pool_split(x0, x1, n0, w, w_lo, scale, shift, y, n, st);
+    }
+    hipError_t e = n0 ? k_bf16::ap_launch_stem_conv(x0, (const float*)w, scale, shift, y, n0, K_F32, st) : hipSuccess;
+    if (e == hipSuccess && n > n0)
+        e = k_bf16::ap_launch_stem_conv(x1, (const float*)w, scale, shift, (char*)y + (size_t)n0 * 112 * 112 * 64 * 4, n - n0, K_F32, st);
+    return e;
+}
+
+hipError_t ap_internal::launch_maxpool(const void* x, void* y, int n, int prec, int* rflag, hipStream_t st) {
+    return H16(prec, ap_launch_maxpool)(x, y, n, prec_kind(prec), rflag, st);
+}
+hipError_t ap_internal::launch_avgpool(const void* x, float* y, int n, int C, int prec, int* rflag, hipStream_t st) {
+    return H16(prec, ap_launch_avgpool)(x, y, n, C, prec_kind(prec), rflag, st);
+}
 
 extern "C" {
 
@@ -27,17 +150,10 @@ int ap_conv2d_nhwc(int precision, const void* x, const void* w, const float* sca
         return fail(AP_EINVAL, "ap_conv2d_nhwc: bad argument");
     if (Cin % (bf ? 64 : 32) || Cout % (precision == AP_PREC_FP32 ? 4 : 8) || Cin <= 0 || Cout <= 0)
         return fail(AP_ESHAPE, "ap_conv2d_nhwc: Cin must be a multiple of 64 (bf16) / 32 (fp32), Cout of 8 / 4");
-    ConvArgs a{};
-    a.x = x; a.w = w; a.scale = scale; a.shift = shift; a.res = res; a.y = y;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin;
-    a.Ho = (H + 2 * pad - ksize) / stride + 1;
-    a.Wo = (W + 2 * pad - ksize) / stride + 1;
-    if (a.Ho <= 0 || a.Wo <= 0) return fail(AP_ESHAPE, "ap_conv2d_nhwc: empty output");
-    a.Cout = Cout; a.KH = a.KW = ksize; a.stride = stride; a.pad = pad;
-    a.M = N * a.Ho * a.Wo;
-    a.ldx = Cin; a.ldy = Cout; a.ldr = Cout; a.wld = ksize * ksize * Cin; a.relu = relu;
-    a.range_flag = ops_range_word(precision);
-    HIP_TRY(dispatch_conv(a, precision, (hipStream_t)stream));
+    if ((H + 2 * pad - ksize) / stride + 1 <= 0 || (W + 2 * pad - ksize) / stride + 1 <= 0) return fail(AP_ESHAPE, "ap_conv2d_nhwc: empty output");
+    const ConvDesc c{w, scale, shift, Cin, Cout, ksize, stride, pad, ksize * ksize * Cin, 0, 1};
+    HIP_TRY(launch_conv(c, x, N, H, W, res, y, relu, 0, nullptr, 0, nullptr, nullptr, precision, conv_mode(), ops_range_word(precision),
+                        (hipStream_t)stream));
     return AP_OK;
 }
 
@@ -48,9 +164,8 @@ int ap_bottleneck64_nhwc(int precision, const void* x, const void* w1, const flo
         return fail(AP_EINVAL, "ap_bottleneck64_nhwc: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16)");
     if (H <= 0 || W <= 0 || H % 14 || W % 14 || !((Cin == 256 && !downsample) || (Cin == 64 && downsample)))
         return fail(AP_ESHAPE, "ap_bottleneck64_nhwc: H, W multiples of 14; Cin 256 (identity) or 64 (downsample)");
-    BneckArgs a = bneck_args(x, w1, s1, h1, w2, s2, h2, w3, s3, h3, y, N, H, W, precision);
-    HIP_TRY(zero_line(&a.zero));
-    HIP_TRY(H16(precision, ap_launch_bneck2)(a, downsample ? 1 : 0, (hipStream_t)stream));
+    HIP_TRY(launch_bneck2(ConvDesc{w1, s1, h1}, ConvDesc{w2, s2, h2}, ConvDesc{w3, s3, h3}, downsample ? 1 : 0, x, y, N, H, W, nullptr, nullptr, 0,
+                          precision, ops_range_word(precision), (hipStream_t)stream));
     return AP_OK;
 }
 
@@ -62,10 +177,9 @@ int ap_bottleneck64_tail_nhwc(int precision, const void* x, const void* w1, cons
         !t1n || N <= 0)
         return fail(AP_EINVAL, "ap_bottleneck64_tail_nhwc: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16)");
     if (H <= 0 || W <= 0 || H % 14 || W % 14) return fail(AP_ESHAPE, "ap_bottleneck64_tail_nhwc: H, W multiples of 14");
-    BneckArgs a = bneck_args(x, w1, s1, h1, w2, s2, h2, w3, s3, h3, y, N, H, W, precision);
-    a.w1n = w1n; a.s1n = s1n; a.h1n = h1n; a.t1n = t1n; a.y_even = y_even != 0;
-    HIP_TRY(zero_line(&a.zero));
-    HIP_TRY(H16(precision, ap_launch_bneck2)(a, 0, (hipStream_t)stream));
+    const ConvDesc c1n{w1n, s1n, h1n};
+    HIP_TRY(launch_bneck2(ConvDesc{w1, s1, h1}, ConvDesc{w2, s2, h2}, ConvDesc{w3, s3, h3}, 0, x, y, N, H, W, &c1n, t1n, y_even != 0, precision,
+                          ops_range_word(precision), (hipStream_t)stream));
     return AP_OK;
 }
 
@@ -86,10 +200,7 @@ int ap_conv_pw_nhwc(int precision, const void* x, const void* wstream, const flo
         return fail(AP_EINVAL, "ap_conv_pw_nhwc: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16)");
     if (!k_bf16::ap_conv_pw_supported(M, Cin, Cout))
         return fail(AP_ESHAPE, "ap_conv_pw_nhwc: M must be a multiple of 196, Cin of 128 (>= 256), Cout of 256");
-    PwArgs p{};
-    p.x = x; p.y = y; p.res = res; p.wfrag = wstream; p.scale = scale; p.shift = shift; p.M = M; p.Cin = Cin; p.Cout = Cout; p.relu = 1;
-    p.range_flag = ops_range_word(precision);
-    HIP_TRY(H16(precision, ap_launch_conv_pw)(p, (hipStream_t)stream));
+    HIP_TRY(launch_conv_pw(ConvDesc{wstream, scale, shift, Cin, Cout}, x, res, y, M, precision, ops_range_word(precision), (hipStream_t)stream));
     return AP_OK;
 }
 
@@ -97,13 +208,10 @@ int ap_conv_pw_ds_nhwc(int precision, const void* t2, const void* x, const void*
                        void* y, int N, int Ho, int Cin, int Cin2, int Cout, int stride, void* stream) {
     if (!prec_half(precision) || !t2 || !x || !wstream || !scale || !shift || !y || N <= 0 || Ho <= 0 || stride < 1 || stride > 2)
         return fail(AP_EINVAL, "ap_conv_pw_ds_nhwc: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16; stride 1 or 2)");
-    PwArgs p{};
-    p.x = t2; p.y = y; p.wfrag = wstream; p.scale = scale; p.shift = shift; p.M = N * Ho * Ho; p.Cin = Cin; p.Cout = Cout; p.relu = 1;
-    p.x2 = x; p.Cin2 = Cin2; p.Ho = p.Wo = Ho; p.H2 = p.W2 = Ho * stride; p.stride2 = stride;
-    p.range_flag = ops_range_word(precision);
-    if (!k_bf16::ap_conv_pw_ds_supported(p))
+    const ConvDesc c{wstream, scale, shift, Cin, Cout, 1, 1, 0, Cin + Cin2, Cin2, stride};
+    if (!conv_pw_ds_fits(c, N, Ho, Ho * stride))
         return fail(AP_ESHAPE, "ap_conv_pw_ds_nhwc: N Ho Ho a multiple of 196 with Ho Ho | 196, Cin and Cin2 multiples of 64 (sum: of 128), Cout of 256");
-    HIP_TRY(H16(precision, ap_launch_conv_pw)(p, (hipStream_t)stream));
+    HIP_TRY(launch_conv_pw_ds(c, t2, x, y, N, Ho, Ho * stride, precision, ops_range_word(precision), (hipStream_t)stream));
     return AP_OK;
 }
 
@@ -111,13 +219,10 @@ int ap_conv_pw_k3s2_nhwc(int precision, const void* x, const void* wstream, cons
                          int H, int Cin, int Cout, void* stream) {
     if (!prec_half(precision) || !x || !wstream || !scale || !shift || !y || N <= 0 || H <= 0)
         return fail(AP_EINVAL, "ap_conv_pw_k3s2_nhwc: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16)");
-    PwArgs p{};
-    p.k3 = 1; p.Ho = p.Wo = H / 2; p.H2 = p.W2 = H; p.stride2 = 2; p.M = N * p.Ho * p.Wo; p.Cin = Cin; p.Cout = Cout; p.relu = 1;
-    p.x = x; p.y = y; p.wfrag = wstream; p.scale = scale; p.shift = shift;
-    p.range_flag = ops_range_word(precision);
-    if ((H & 1) || !k_bf16::ap_conv_pw_k3_supported(p))
+    const ConvDesc c{wstream, scale, shift, Cin, Cout, 3, 2, 1};
+    if (!conv_pw_k3_fits(c, N, H))
         return fail(AP_ESHAPE, "ap_conv_pw_k3s2_nhwc: H even with (H / 2)^2 | 196 (14 or 28), N (H / 2)^2 a multiple of 196, Cin / 64 a power of two >= 2, Cout a multiple of 256");
-    HIP_TRY(H16(precision, ap_launch_conv_pw)(p, (hipStream_t)stream));
+    HIP_TRY(launch_conv_pw_k3(c, x, y, N, H, precision, ops_range_word(precision), (hipStream_t)stream));
     return AP_OK;
 }
 
@@ -134,10 +239,7 @@ int ap_block_img_nhwc(int precision, const void* x, const void* wstream, const f
                       const float* h2, const float* s3, const float* h3, void* y, int N, void* stream) {
     if (!prec_half(precision) || !x || !wstream || !s1 || !h1 || !s2 || !h2 || !s3 || !h3 || !y || N <= 0)
         return fail(AP_EINVAL, "ap_block_img_nhwc: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16)");
-    BlkImgArgs a{};
-    a.x = x; a.y = y; a.wfrag = wstream; a.s1 = s1; a.h1 = h1; a.s2 = s2; a.h2 = h2; a.s3 = s3; a.h3 = h3; a.N = N;
-    a.dbg = g_conv_dbg; a.range_flag = ops_range_word(precision);
-    HIP_TRY(H16(precision, ap_launch_block_img)(a, (hipStream_t)stream));
+    HIP_TRY(launch_block_img(x, wstream, s1, h1, s2, h2, s3, h3, y, N, precision, ops_range_word(precision), (hipStream_t)stream));
     return AP_OK;
 }
 
@@ -155,11 +257,7 @@ int ap_conv_s2p_nhwc(int precision, const void* x, const void* wstream, const fl
                      int y_tiled, void* stream) {
     if (!prec_half(precision) || !x || !wstream || !scale || !shift || !y || N <= 0)
         return fail(AP_EINVAL, "ap_conv_s2p_nhwc: bad argument");
-    ConvS2pArgs a{};
-    a.x = x; a.y = y; a.wfrag = wstream; a.scale = scale; a.shift = shift; a.N = N; a.y_tiled = y_tiled != 0;
-    a.range_flag = ops_range_word(precision);
-    HIP_TRY(zero_line(&a.zero));
-    HIP_TRY(H16(precision, ap_launch_conv_s2p)(a, (hipStream_t)stream));
+    HIP_TRY(launch_conv_s2p(x, wstream, scale, shift, y, N, y_tiled != 0, precision, ops_range_word(precision), (hipStream_t)stream));
     return AP_OK;
 }
 
@@ -173,11 +271,7 @@ int ap_conv_img3_nhwc(int precision, const void* x, const void* wstream, const f
                       int y_tiled, void* stream) {
     if (!prec_half(precision) || !x || !wstream || !scale || !shift || !y || N <= 0)
         return fail(AP_EINVAL, "ap_conv_img3_nhwc: bad argument");
-    ConvImg3Args a{};
-    a.x = x; a.y = y; a.wfrag = wstream; a.scale = scale; a.shift = shift; a.N = N; a.y_tiled = y_tiled != 0;
-    a.range_flag = ops_range_word(precision);
-    HIP_TRY(zero_line(&a.zero));
-    HIP_TRY(H16(precision, ap_launch_conv_img3)(a, (hipStream_t)stream));
+    HIP_TRY(launch_conv_img3(x, wstream, scale, shift, y, N, y_tiled != 0, precision, ops_range_word(precision), (hipStream_t)stream));
     return AP_OK;
 }
 
@@ -217,34 +311,21 @@ int ap_stem_nhwc(int precision, int form, const float* x0, const float* x1, int 
     const bool half = prec_half(precision);
     if (form < 0 || form > (half ? 2 : precision == AP_PREC_BF16X2 ? 1 : 0))
         return fail(AP_EINVAL, "ap_stem_nhwc: form 0 (un-pooled; every precision), 1 (strip kernel; 16-bit, bf16x2), 2 (persistent kernel; 16-bit)");
-    hipStream_t st = (hipStream_t)stream;
-    const int n1 = N - n_split;
-    if (half) {
-        if (form == 0) HIP_TRY(H16(precision, ap_launch_stem_conv_mfma)(x0, x1, n_split, wpacked, scale, shift, y, N, st));
-        else HIP_TRY(H16(precision, ap_launch_stem_pool)(x0, x1, n_split, wpacked, scale, shift, y, N, ops_range_word(precision), form, st, nullptr));
-    } else if (precision == AP_PREC_BF16X2) {
-        const void* wlo = (const char*)wpacked + (size_t)64 * AP_STEM_WLD * 2;
-        if (form == 0) HIP_TRY(k_bf16::ap_launch_stem_conv_mfma_split(x0, x1, n_split, wpacked, wlo, scale, shift, y, N, st));
-        else HIP_TRY(k_bf16::ap_launch_stem_pool_split(x0, x1, n_split, wpacked, wlo, scale, shift, y, N, st));
-    } else {
-        if (n_split) HIP_TRY(k_bf16::ap_launch_stem_conv(x0, (const float*)wpacked, scale, shift, y, n_split, K_F32, st));
-        if (n1)
-            HIP_TRY(k_bf16::ap_launch_stem_conv(x1, (const float*)wpacked, scale, shift, (char*)y + (size_t)n_split * 112 * 112 * 64 * 4, n1,
-                                                K_F32, st));
-    }
+    const void* wlo = (const char*)wpacked + (size_t)64 * AP_STEM_WLD * 2;   // (AP_PREC_BF16X2: the low plane follows the high one)
+    HIP_TRY(launch_stem(precision, form, x0, x1, n_split, N, wpacked, wlo, scale, shift, y, ops_range_word(precision), (hipStream_t)stream));
     return AP_OK;
 }
 
 int ap_maxpool_nhwc(int precision, const void* x, void* y, int N, void* stream) {
     if (!prec_valid(precision) || !x || !y || N <= 0) return fail(AP_EINVAL, "ap_maxpool_nhwc: bad argument");
-    HIP_TRY(H16(precision, ap_launch_maxpool)(x, y, N, prec_kind(precision), ops_range_word(precision), (hipStream_t)stream));
+    HIP_TRY(launch_maxpool(x, y, N, precision, ops_range_word(precision), (hipStream_t)stream));
     return AP_OK;
 }
 
 int ap_avgpool_nhwc(int precision, const void* x, float* y, int N, int C, void* stream) {
     if (!prec_valid(precision) || !x || !y || N <= 0) return fail(AP_EINVAL, "ap_avgpool_nhwc: bad argument");
     if (C <= 0 || C % (precision == AP_PREC_FP32 ? 128 : 256)) return fail(AP_ESHAPE, "ap_avgpool_nhwc: C a multiple of 256 (fp32: 128)");
-    HIP_TRY(H16(precision, ap_launch_avgpool)(x, y, N, C, prec_kind(precision), ops_range_word(precision), (hipStream_t)stream));
+    HIP_TRY(launch_avgpool(x, y, N, C, precision, ops_range_word(precision), (hipStream_t)stream));
     return AP_OK;
 }
 
@@ -270,10 +351,8 @@ int ap_conv_pair_nhwc(int precision, const void* t2, const void* wstream, const 
     if (!prec_half(precision) || !t2 || !wstream || !s3 || !h3 || !res || !s1 || !h1 || !out || !t1n || M <= 0)
         return fail(AP_EINVAL, "ap_conv_pair_nhwc: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16)");
     if (!k_bf16::ap_conv_pair_supported(P, 0, 4 * P, N1)) return fail(AP_ESHAPE, "ap_conv_pair_nhwc: (P, N1) must be (128,128), (128,256) or (256,256)");
-    PairArgs a{};
-    a.t2 = t2; a.res = res; a.wstream = wstream; a.s3 = s3; a.h3 = h3; a.s1 = s1; a.h1 = h1; a.out = out; a.t1n = t1n; a.M = M;
-    a.dbg = g_conv_dbg; a.range_flag = ops_range_word(precision);
-    HIP_TRY(H16(precision, ap_launch_conv_pair)(a, P, 0, 4 * P, N1, (hipStream_t)stream));
+    HIP_TRY(launch_conv_pair(t2, wstream, s3, h3, s1, h1, res, out, t1n, M, 0, 0, 0, P, 0, N1, PairLayout{}, precision, ops_range_word(precision),
+                             (hipStream_t)stream));
     return AP_OK;
 }
 
@@ -282,14 +361,10 @@ int ap_conv_pair_ds_nhwc(int precision, const void* t2, const void* x, const voi
                          void* stream) {
     if (!prec_half(precision) || !t2 || !x || !wstream || !s3 || !h3 || !out || N <= 0 || Ho <= 0 || (N1 > 0 && (!s1 || !h1 || !t1n)))
         return fail(AP_EINVAL, "ap_conv_pair_ds_nhwc: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16)");
-    const int C3 = 4 * P;
-    if (!k_bf16::ap_conv_pair_supported(P, P2, C3, N1) || stride < 1 || stride > 2)
+    if (!k_bf16::ap_conv_pair_supported(P, P2, 4 * P, N1) || stride < 1 || stride > 2)
         return fail(AP_ESHAPE, "ap_conv_pair_ds_nhwc: (P, P2, N1) must be (128,256,128) or (256,512,0); stride 1 or 2");
-    PairArgs a{};
-    a.t2 = t2; a.x2 = x; a.wstream = wstream; a.s3 = s3; a.h3 = h3; a.s1 = s1; a.h1 = h1; a.out = out; a.t1n = t1n;
-    a.M = N * Ho * Ho; a.Ho = a.Wo = Ho; a.H2 = a.W2 = Ho * stride; a.stride2 = stride;
-    a.dbg = g_conv_dbg; a.range_flag = ops_range_word(precision);
-    HIP_TRY(H16(precision, ap_launch_conv_pair)(a, P, P2, C3, N1, (hipStream_t)stream));
+    HIP_TRY(launch_conv_pair(t2, wstream, s3, h3, s1, h1, x, out, t1n, N * Ho * Ho, Ho, Ho * stride, stride, P, P2, N1, PairLayout{}, precision,
+                             ops_range_word(precision), (hipStream_t)stream));
     return AP_OK;
 }
 

@@ -1,5 +1,7 @@
-// The trunk schedule of libairpose_hip.so: which kernel runs each convolution (dispatch_conv, run_*), one depth-first pass
-// (trunk_chunk), the concurrent passes of a call (trunk_passes, trunk_fwd) and the process-wide tuning knobs.
+// The trunk schedule of libairpose_hip.so: the tile configuration of the generic kernels (dispatch_conv), the chip-fill rule
+// (fills_chip), what runs each block of one depth-first pass (plan_pass: decisions only) and the loop that launches it through the
+// launch functions of api_ops.hip (trunk_chunk), the concurrent passes of a call (trunk_passes, trunk_fwd) and the process-wide
+// tuning knobs.
 #include "api_internal.h"
 
 unsigned long long* ap_internal::g_conv_dbg = nullptr;
@@ -7,10 +9,10 @@ unsigned long long* ap_internal::g_conv_dbg = nullptr;
 namespace {
 // Tuning knob of ap_set_conv_config, process-wide: ONE atomic word holding the raw value (-1 automatic, -4 automatic
 // without the slab / lean kernels, -5 automatic without the lean kernel, 0..14 / 17 / 100 one explicit configuration);
-// dispatch_conv reads it once per launch and decodes it (trunk_chunk: once per pass), so handles on different threads never see a
-// torn setting.
+// conv_mode() reads it, once per launch (dispatch_conv's three-argument form) or once per pass (trunk_chunk, which hands the value
+// down), so handles on different threads never see a torn setting.
 std::atomic<int> g_conv_mode{-1};
-void* g_zero[16] = {nullptr};   // per-device 256-byte zero line
+void* g_zero[AP_MAX_DEVICES] = {nullptr};   // per-device 256-byte zero line
 // ap_debug_set_range_hook: one host-mapped word for the process, allocated on first use and kept; g_ops_range is that word while
 // the hook is on and NULL while it is off (one atomic pointer: a launch sees the old or the new value)
 int* g_ops_word = nullptr;
@@ -21,11 +23,12 @@ int* ap_internal::ops_range_word(int prec) {
     return prec == AP_PREC_F16 ? g_ops_range.load(std::memory_order_relaxed) : nullptr;
 }
 
+int ap_internal::conv_mode() { return g_conv_mode.load(std::memory_order_relaxed); }
+
 hipError_t ap_internal::zero_line(const void** out) {
     int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    hipError_t e = ap_current_device(&dev);
     if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 16) return hipErrorInvalidDevice;
     if (!g_zero[dev]) {
         e = hipMalloc(&g_zero[dev], 256);
         if (e != hipSuccess) return e;
@@ -50,9 +53,8 @@ hipError_t ap_internal::device_cus(int* n) {
 }
 
 // choose the tile configuration: large tiles need enough tiles to fill 256 CUs (1 workgroup per CU)
-hipError_t ap_internal::dispatch_conv(ConvArgs& a, int prec /* AP_PREC_* */, hipStream_t st) {
+hipError_t ap_internal::dispatch_conv(ConvArgs& a, int prec /* AP_PREC_* */, hipStream_t st, int mode /* conv_mode() */) {
     const int is_bf16 = prec_kind(prec);                     // storage kind inside the kernel set: K_F32 / K_BF16 (16-bit) / K_SPLIT
-    const int mode = g_conv_mode.load(std::memory_order_relaxed);
     const bool use_slab = mode == -1 || mode == -5, use_lean = mode == -1;
     int cfg = mode < 0 ? -1 : mode;
     if (cfg < 0) {
@@ -99,125 +101,119 @@ hipError_t ap_internal::dispatch_conv(ConvArgs& a, int prec /* AP_PREC_* */, hip
 
 namespace {
 
-// pw: 0 = the generic kernels; 1 / 2 / 3 = conv_pw.hip where the layer has a stream and the shape fits (1: only when its tiles fill
-// half the chip, or whole rounds of it to 80 %) -- same bits either way, so the choice may depend on the problem size
-// the size rule of conv_pw.hip's automatic choice: its 196-pixel x 256-channel tiles fill half a round of the chip at least, or whole rounds to 80 %
-bool pw_fills(long M, int cout, int pw, int* err) {
-    int cus = 0;
-    if ((*err = device_cus(&cus)) != hipSuccess) return false;
-    const int NN = cout >> 8, gmax = k_bf16::ap_conv_pw_grid(1L << 40, cout, cus);
-    const long T = ((M / 196 + 7) & ~7L) * NN, rounds = (T + gmax - 1) / gmax;
-    return pw == 2 || pw == 3 || (T <= gmax ? T * 2 >= gmax : T * 5 >= rounds * gmax * 4);
-}
-// the 3 x 3 / stride-2 convolution of a stage's first block (model_copenet.py:32-34, :18) as nine pointwise taps of conv_pw.hip?
-bool pw_k3_args(const Layer& L, int N, int H, int W, int prec, PwArgs* p) {
-    if (!L.pw.p || !prec_half(prec) || L.k != 3 || L.stride != 2 || L.pad != 1 || (H & 1) || (W & 1)) return false;
-    *p = PwArgs{};
-    p->k3 = 1; p->Ho = H / 2; p->Wo = W / 2; p->H2 = H; p->W2 = W; p->stride2 = 2;
-    p->M = N * p->Ho * p->Wo; p->Cin = L.cin; p->Cout = L.cout; p->relu = 1;
-    p->wfrag = L.pw.p; p->scale = L.scale.as<float>(); p->shift = L.shift.as<float>();
-    return k_bf16::ap_conv_pw_k3_supported(*p);
+// T units of work on a grid of at most G per round: does the launch fill the chip?  Whole rounds (the last one counted as whole)
+// to num / den; a launch of less than one round to part_num / part_den of it (part_den 0: never)
+bool fills_chip(long T, long G, int num, int den, int part_num, int part_den) {
+    if (T < G) return part_den && T * part_den >= G * part_num;
+    return T * den >= (T + G - 1) / G * G * num;
 }
 
-int run_conv(const Layer& L, const void* x, int N, int H, int W, void* y, const void* res, int relu, int prec,
-             hipStream_t st, int* rflag = nullptr, int y_tiled = 0, int pw = 0) {
-    if (pw && L.pw.p && prec_half(prec) && relu && !y_tiled && L.k == 1 && L.stride == 1 &&
-        g_conv_mode.load(std::memory_order_relaxed) == -1 && k_bf16::ap_conv_pw_supported((long)N * H * W, L.cin, L.cout)) {
-        const long M = (long)N * H * W;
-        int err = 0;
-        const bool fills = pw_fills(M, L.cout, pw, &err);
-        HIP_TRY((hipError_t)err);
-        if (fills) {
-            PwArgs p{};
-            p.x = x; p.y = y; p.res = res; p.wfrag = L.pw.p; p.scale = L.scale.as<float>(); p.shift = L.shift.as<float>();
-            p.M = (int)M; p.Cin = L.cin; p.Cout = L.cout; p.relu = 1; p.range_flag = rflag;
-            HIP_TRY(H16(prec, ap_launch_conv_pw)(p, st));
-            return AP_OK;
-        }
-    }
-    PwArgs p3;
-    if (pw && relu && !res && !y_tiled && g_conv_mode.load(std::memory_order_relaxed) == -1 && pw_k3_args(L, N, H, W, prec, &p3)) {
-        int err = 0;
-        const bool fills = pw_fills(p3.M, L.cout, pw, &err);
-        HIP_TRY((hipError_t)err);
-        if (fills) {
-            p3.x = x; p3.y = y; p3.range_flag = rflag;
-            HIP_TRY(H16(prec, ap_launch_conv_pw)(p3, st));
-            return AP_OK;
-        }
-    }
-    ConvArgs a{};
-    a.range_flag = rflag;
-    a.y_tiled = y_tiled;
-    a.x = x; a.w = L.w.p; a.scale = L.scale.as<float>(); a.shift = L.shift.as<float>(); a.res = res; a.y = y;
-    a.N = N; a.H = H; a.W = W; a.Cin = L.cin;
-    a.Ho = (H + 2 * L.pad - L.k) / L.stride + 1;
-    a.Wo = (W + 2 * L.pad - L.k) / L.stride + 1;
-    a.Cout = L.cout;
-    a.KH = a.KW = L.k; a.stride = L.stride; a.pad = L.pad;
-    a.M = N * a.Ho * a.Wo;
-    a.ldx = L.cin; a.ldy = L.cout; a.ldr = L.cout; a.wld = L.wld;
-    a.relu = relu;
-    HIP_TRY(dispatch_conv(a, prec, st));
-    return AP_OK;
-}
+// What runs one block of a pass
+enum : uint8_t { B_BNECK, B_IMG, B_CONVS };                  // form: fused layer1 bottleneck / image-resident layer3 block / separate convolutions
+enum : uint8_t { C1_READY, C1_CONV, C1_PW };                 // conv1: the previous kernel produced it / generic kernels / conv_pw.hip
+enum : uint8_t { C2_CONV, C2_PW, C2_IMG3, C2_S2P };          // conv2: generic / conv_pw.hip 3 x 3 / conv_img3.hip / conv_s2p.hip
+// how the block ends: pair kernel / folded downsample on the generic kernels or conv_pw.hip / conv3 + average pool / conv3 +
+// identity on the generic kernels or conv_pw.hip / downsample, then conv3
+enum : uint8_t { E_PAIR, E_FOLD, E_FOLD_PW, E_POOL, E_C3, E_C3_PW, E_DS_C3 };
+struct BlockPlan {
+    uint8_t form, c1, c2, end;
+    bool tail, y_even;                                       // B_BNECK: conv1 of the next block in the kernel; output at the even pixels only
+    bool t2_tiled, res_tiled, out_tiled, out_even;           // layouts: t2 of the block; E_PAIR: the block input and output
+};
+constexpr size_t MAX_BLOCKS = 16;
 
-// fused conv3 + downsample of a stage's first block: t [N][Ho][Ho][cin] (pointwise) and x [N][Hin][Hin][cin2]
-// sampled with stride2, concatenated along K
-int run_c3_ds(const Layer& L, const void* t, const void* x, int N, int Ho, int Hin, void* y, int prec,
-              hipStream_t st, int* rflag = nullptr, int pw = 0) {
-    if (pw && L.pw.p && prec_half(prec) && g_conv_mode.load(std::memory_order_relaxed) == -1) {       // conv_pw.hip, as in run_conv
-        PwArgs p{};
-        p.x = t; p.y = y; p.wfrag = L.pw.p; p.scale = L.scale.as<float>(); p.shift = L.shift.as<float>();
-        p.M = N * Ho * Ho; p.Cin = L.cin; p.Cout = L.cout; p.relu = 1; p.range_flag = rflag;
-        p.x2 = x; p.Cin2 = L.cin2; p.Ho = p.Wo = Ho; p.H2 = p.W2 = Hin; p.stride2 = L.stride2;
-        if (k_bf16::ap_conv_pw_ds_supported(p)) {
-            int cus = 0;
-            HIP_TRY(device_cus(&cus));
-            const int NN = L.cout >> 8, gmax = k_bf16::ap_conv_pw_grid(1L << 40, L.cout, cus);
-            const long T = (((long)p.M / 196 + 7) & ~7L) * NN, rounds = (T + gmax - 1) / gmax;
-            // (whole rounds only: at half a round -- 64 pairs -- the generic kernel beside the other pass is faster: -0.8 % of that bench)
-            if (pw == 2 || pw == 3 || (T >= gmax && T * 5 >= rounds * gmax * 4)) {
-                HIP_TRY(H16(prec, ap_launch_conv_pw)(p, st));
-                return AP_OK;
-            }
+// The schedule of one pass over n images, decisions only (no HIP call, no launch): knobs and packed streams of h, the CU count, the
+// conv mode as read once for the pass, and whether a sibling pass shares the chip.
+// Fragment-tiled intermediates (ap_common.h: ap_tiled_off): a tensor whose ONLY reader is the fused pair kernel is stored
+// as [M/16][C/8][16 pixels][8 channels], the order the pair kernel's lanes fetch it in -- t2 of every pair block, and a
+// pair block's output when the next block is an identity pair block that also got its conv1 from this kernel.  Same
+// values, same arithmetic: the features are bit-identical with the layout off (ap_net_set_tiled).
+void plan_pass(const ap_net* h, int n, int cus, int mode, bool shared, BlockPlan* plan) {
+    const bool bf = h->half(), automatic = mode == -1;       // bf gates the fused kernels of the 16-bit throughput modes
+    const bool tiling = bf && h->tiled && mode < 0;
+    // conv_pw.hip: automatic rule = conv1 only (layer4 at 512 images: 156 / 70 / 71 -> 136 / 60 / 61 us; whole bench +1.0 % single
+    // pass, +0.6 % with two concurrent passes).  conv3 + identity (2: forced) is 3-9 us slower than the lean kernel and, beside a
+    // concurrent pass, turns the gain into -0.5 %: a one-wave-per-SIMD kernel keeps the other pass's workgroups off its CUs.
+    // Same bits as the generic kernels, so the choice may depend on the problem size: its 196-pixel x 256-channel tiles fill whole
+    // rounds of the chip to 80 % or (part) half a round at least; 2 / 3 force it
+    const int pw = h->pw_conv;
+    auto pw_fills = [&](long M, int cout, bool part) {
+        const int NN = cout >> 8, gmax = k_bf16::ap_conv_pw_grid(1L << 40, cout, cus);
+        return pw == 2 || pw == 3 || fills_chip(((M / 196 + 7) & ~7L) * NN, gmax, 4, 5, 1, part ? 2 : 0);
+    };
+    auto pw_1x1 = [&](const Layer& L, long M) {
+        return pw && L.pw.p && bf && L.k == 1 && L.stride == 1 && automatic && k_bf16::ap_conv_pw_supported(M, L.cin, L.cout) &&
+               pw_fills(M, L.cout, true);
+    };
+    // an image (half an image) per CU: 256 (512) images = one (two) full rounds; 300 = two rounds 59 % full
+    const bool img_fit = h->img_block == 2 || (h->img_block == 1 && fills_chip(n, cus, 7, 8, 7, 8));
+    const bool img3_fit = h->img3 == 2 || (h->img3 == 1 && fills_chip(2L * n, cus, 7, 8, 7, 8));
+    auto is_pair = [&](const ap_net::Block& X) {
+        return bf && h->fuse_pair && X.pair_p && &X != &h->blocks.back() && (!X.has_down || h->fuse_ds);
+    };
+    bool t1_ready = false, cur_tiled = false;                // ws_t1 already holds this block's conv1 output; layout of the block input
+    int H = 56;
+    for (size_t i = 0; i < h->blocks.size(); ++i) {
+        const ap_net::Block& B = h->blocks[i];
+        const ap_net::Block* Nx = i + 1 < h->blocks.size() ? &B + 1 : nullptr;
+        BlockPlan& p = plan[i] = BlockPlan{};
+        const int Ho = (H + 2 - 3) / B.c2.stride + 1;
+        if (bf && h->fuse_block && B.c2.cout == 64 && B.c2.stride == 1 && H % 14 == 0 && (!B.has_down || B.c1.cin == 64)) {
+            // layer1: conv1 -> conv2 -> conv3 (+identity | folded downsample) in one kernel, intermediates in LDS.
+            // last block of layer1: conv1 of layer2.0 (model_copenet.py:29-31) on the block output while it is in registers; what
+            // is left to read of that output is layer2.0's stride-2 downsample branch (:41-42, :97-102) -> even pixels only
+            p.form = B_BNECK;
+            p.tail = h->fuse_tail && !B.has_down && Nx && Nx->has_down && Nx->c1.cin == 256 && Nx->c1.cout == 128 &&
+                     Nx->c2.stride == 2 && Nx->down.stride == 2 && mode < 0;
+            p.y_even = p.tail && h->even_out;
+            t1_ready = p.tail;
+            continue;
         }
+        if (bf && img_fit && B.imgw.p && H == 14 && !t1_ready && !cur_tiled && automatic) {
+            p.form = B_IMG;                                  // layer3 identity block: one kernel, an image per workgroup, t1 / t2 in LDS
+            continue;
+        }
+        p.form = B_CONVS;
+        p.c1 = t1_ready ? C1_READY : pw_1x1(B.c1, (long)n * H * H) ? C1_PW : C1_CONV;
+        const bool pair = is_pair(B);
+        // conv2 of layer2.0 on the polyphase kernel (conv_s2p.hip; ap_net_set_s2p, off by default): its K order is its own, so when on it
+        // takes the layer at EVERY batch size.
+        // conv2 of a stage's first block (model_copenet.py:32-34, :18) on conv_pw.hip (nine taps): it writes NHWC rows, so t2 stays
+        // untiled for that block's pair kernel.  Automatic rule: only for a pass that has the chip to itself (l4.0.c2 164 -> 149 us,
+        // l3.0.c2 168 -> 157: +0.55 % of the whole bench there, -0.45 % beside a concurrent pass, whose workgroups a one-wave-per-SIMD
+        // kernel keeps off its CUs)
+        const Layer& L2 = B.c2;
+        if (bf && h->s2p && B.c2s2.p && H == 56 && L2.stride == 2 && automatic) p.c2 = C2_S2P;
+        else if (pw && pw != 4 && !(pw == 1 && shared) && automatic && bf && L2.pw.p && L2.k == 3 && L2.stride == 2 && L2.pad == 1 &&
+                 conv_pw_k3_fits(L2.desc(true), n, H) && pw_fills((long)n * (H / 2) * (H / 2), L2.cout, true))
+            p.c2 = C2_PW;
+        else if (bf && img3_fit && B.c2img.p && H == 28 && L2.stride == 1 && automatic) p.c2 = C2_IMG3;
+        p.t2_tiled = pair && tiling && p.c2 != C2_PW;
+        t1_ready = false;
+        if (pair) {
+            // conv3 (+ identity | + folded downsample, ReLU) AND -- where the pair carries it -- the next block's conv1 in one
+            // kernel: the block output is written once and not read back for conv1 (model_copenet.py:38-45 of this block,
+            // :29-31 of the next)
+            p.end = E_PAIR;
+            p.res_tiled = cur_tiled;
+            cur_tiled = p.out_tiled = p.t2_tiled && B.pair_n1 > 0 && is_pair(*Nx) && !Nx->has_down;
+            // the next block is a stage's first one and got its conv1 from this kernel: all that is read of `out` is that block's
+            // stride-2 downsample branch (model_copenet.py:41-42, :97-102) -- the even pixels
+            p.out_even = h->even_out && !p.out_tiled && B.pair_n1 > 0 && Nx->has_down && Nx->down.stride == 2 && Nx->c2.stride == 2;
+            t1_ready = B.pair_n1 > 0;
+        } else if (B.has_down && h->fuse_ds) {
+            // (conv_pw.hip, whole rounds only: at half a round -- 64 pairs -- the generic kernel beside the other pass is faster: -0.8 % of that bench)
+            const Layer& L = B.c3ds;
+            p.end = pw && L.pw.p && bf && automatic && conv_pw_ds_fits(L.desc(true), n, Ho, H) && pw_fills((long)n * Ho * Ho, L.cout, false)
+                        ? E_FOLD_PW : E_FOLD;
+        } else if (bf && h->fuse_pool && !Nx && !B.has_down && Ho == 7 && automatic) {
+            p.end = E_POOL;                                  // last convolution of the trunk, with AvgPool2d(7) + view in its epilogue
+        } else {
+            // (conv3 + identity on conv_pw.hip: 89-95 us against the lean kernel's 86: only when forced)
+            p.end = B.has_down ? E_DS_C3 : pw == 2 && pw_1x1(B.c3, (long)n * Ho * Ho) ? E_C3_PW : E_C3;
+        }
+        H = Ho;
     }
-    ConvArgs a{};
-    a.range_flag = rflag;
-    a.x = t; a.w = L.w.p; a.scale = L.scale.as<float>(); a.shift = L.shift.as<float>(); a.res = nullptr; a.y = y;
-    a.N = N; a.H = Ho; a.W = Ho; a.Cin = L.cin; a.Ho = Ho; a.Wo = Ho; a.Cout = L.cout;
-    a.KH = a.KW = 1; a.stride = 1; a.pad = 0;
-    a.M = N * Ho * Ho;
-    a.ldx = L.cin; a.ldy = L.cout; a.ldr = L.cout; a.wld = L.wld; a.relu = 1;
-    a.x2 = x; a.H2 = Hin; a.W2 = Hin; a.Cin2 = L.cin2; a.stride2 = L.stride2; a.ldx2 = L.cin2;
-    HIP_TRY(dispatch_conv(a, prec, st));
-    return AP_OK;
-}
-
-// fused layer1 bottleneck (bf16): x [N][H][H][c1.cin] -> y [N][H][H][256]
-// c1n (or NULL): conv1 of the NEXT block computed on the block output in the same kernel -> t1n [N][H][H][128]; y_even: the block
-// output is stored at the even pixels only (its one remaining reader is a stride-2 downsample branch)
-int run_bneck64(const Layer& c1, const Layer& c2, const Layer& c3, bool ds, const void* x, int N, int H, void* y,
-                int prec, hipStream_t st, int* rflag = nullptr, const Layer* c1n = nullptr, void* t1n = nullptr, int y_even = 0) {
-    BneckArgs a{};
-    a.range_flag = rflag;
-    if (c1n) {
-        if (ds || c1n->cin != 256 || c1n->cout != 128 || c1n->k != 1 || c1n->stride != 1 || !t1n)
-            return fail(AP_ESHAPE, "fused layer1 bottleneck + next conv1: identity block, 1x1, 256 -> 128");
-        a.w1n = c1n->w.p; a.s1n = c1n->scale.as<float>(); a.h1n = c1n->shift.as<float>(); a.t1n = t1n; a.y_even = y_even;
-    }
-    a.x = x; a.y = y;
-    a.w1 = c1.w.p; a.w2 = c2.w.p; a.w3 = c3.w.p;
-    a.s1 = c1.scale.as<float>(); a.h1 = c1.shift.as<float>();
-    a.s2 = c2.scale.as<float>(); a.h2 = c2.shift.as<float>();
-    a.s3 = c3.scale.as<float>(); a.h3 = c3.shift.as<float>();
-    a.N = N; a.H = H; a.W = H;
-    HIP_TRY(zero_line(&a.zero));
-    a.dbg = g_conv_dbg;
-    if (!((!ds && c1.cin == 256) || (ds && c1.cin == 64))) return fail(AP_ESHAPE, "fused layer1 bottleneck: C_in 256 (identity) or 64 (first block)");
-    HIP_TRY(H16(prec, ap_launch_bneck2)(a, ds ? 1 : 0, st));
-    return AP_OK;
 }
 
 // workspace of one pass over n images (a grow may synchronise the device and free: never while a sibling pass is in flight)
@@ -233,193 +229,94 @@ int reserve_trunk_ws(ap_net* h, ap_net::TrunkWs& w, int n) {
     return AP_OK;
 }
 
-// one depth-first pass over n = n0 + n1 images: the first n0 from x0, the rest from x1 (two views, one pass)
+// one depth-first pass over n = n0 + n1 images: the first n0 from x0, the rest from x1 (two views, one pass).  shared: a sibling
+// pass runs beside this one.  The loop walks the plan: it owns the buffers and their swaps, the timing marks and ev_skew
 int trunk_chunk(ap_net* h, ap_net::TrunkWs& w, const float* x0, int n0, const float* x1, int n1, float* feat, hipStream_t st,
-                size_t* ev_out = nullptr, int signal_at = 0) {
-    const int bf = h->half();                                // gates the fused kernels of the 16-bit throughput modes
+                bool shared, size_t* ev_out = nullptr, int signal_at = 0) {
+    const int bf = h->half();
     const int prec = h->prec;                                // selects the kernel set (H16) and, as prec_kind, the storage kind
-    const int kind = h->kind();
-    const size_t es = h->esize();
     const int n = n0 + n1;
-    const int conv_mode = g_conv_mode.load(std::memory_order_relaxed);   // ONE schedule for the whole pass, whatever a setter does meanwhile
+    const int mode = conv_mode();                            // ONE schedule for the whole pass, whatever a setter does meanwhile
+    int cus = 0;
+    HIP_TRY(device_cus(&cus));
+    if (h->blocks.size() > MAX_BLOCKS) return fail(AP_ESTATE, "trunk: more bottleneck blocks than a pass plans");
+    BlockPlan plan[MAX_BLOCKS];
+    plan_pass(h, n, cus, mode, shared, plan);
     { int rc0 = reserve_trunk_ws(h, w, n); if (rc0) return rc0; }
     size_t e0 = 0, e1 = 0, e2 = 0, e3 = 0;
     if (h->tm.on == 1) HIP_TRY(h->tm.rec(st, &e0));
-    if (bf && h->fuse_stem) {
-        HIP_TRY(H16(prec, ap_launch_stem_pool)(x0, x1, n0, h->stem_wpk.p, h->stem_scale.as<float>(), h->stem_shift.as<float>(),
-                                               w.ws_a.p, n, w.rflag, h->fuse_stem == 2 ? 1 : 2, st, g_conv_dbg));
-    } else if (bf) {
-        HIP_TRY(H16(prec, ap_launch_stem_conv_mfma)(x0, x1, n0, h->stem_wpk.p, h->stem_scale.as<float>(),
-                                                    h->stem_shift.as<float>(), w.ws_stem.p, n, st));
-    } else if (kind == AP_PREC_BF16X2 && h->fuse_stem) {
-        HIP_TRY(k_bf16::ap_launch_stem_pool_split(x0, x1, n0, h->stem_wpk.p, h->stem_wpk_lo.p, h->stem_scale.as<float>(),
-                                          h->stem_shift.as<float>(), w.ws_a.p, n, st));
-    } else if (kind == AP_PREC_BF16X2) {
-        HIP_TRY(k_bf16::ap_launch_stem_conv_mfma_split(x0, x1, n0, h->stem_wpk.p, h->stem_wpk_lo.p, h->stem_scale.as<float>(),
-                                               h->stem_shift.as<float>(), w.ws_stem.p, n, st));
-    } else {
-        if (n0)
-            HIP_TRY(k_bf16::ap_launch_stem_conv(x0, h->stem_w.as<float>(), h->stem_scale.as<float>(), h->stem_shift.as<float>(),
-                                        w.ws_stem.p, n0, kind, st));
-        if (n1)
-            HIP_TRY(k_bf16::ap_launch_stem_conv(x1, h->stem_w.as<float>(), h->stem_scale.as<float>(), h->stem_shift.as<float>(),
-                                        (char*)w.ws_stem.p + (size_t)n0 * 112 * 112 * 64 * es, n1, kind, st));
-    }
-    if (!(h->fuse_stem && (bf || kind == AP_PREC_BF16X2))) HIP_TRY(H16(prec, ap_launch_maxpool)(w.ws_stem.p, w.ws_a.p, n, kind, w.rflag, st));
+    const bool stem_pools = h->fuse_stem && (bf || prec == AP_PREC_BF16X2);
+    HIP_TRY(launch_stem(prec, !stem_pools ? 0 : !bf || h->fuse_stem == 2 ? 1 : 2, x0, x1, n0, n, prec == AP_PREC_FP32 ? h->stem_w.p : h->stem_wpk.p,
+                        h->stem_wpk_lo.p, h->stem_scale.as<float>(), h->stem_shift.as<float>(), stem_pools ? w.ws_a.p : w.ws_stem.p, w.rflag, st));
+    if (!stem_pools) HIP_TRY(launch_maxpool(w.ws_stem.p, w.ws_a.p, n, prec, w.rflag, st));
     if (h->tm.on) HIP_TRY(h->tm.rec(st, &e1));
     if (signal_at == 1) HIP_TRY(hipEventRecord(h->ev_skew, st));
-    void *cur = w.ws_a.p, *nxt = w.ws_b.p;
+    void *cur = w.ws_a.p, *nxt = w.ws_b.p, *t1 = w.ws_t1.p, *t2 = w.ws_t2.p;
     int H = 56;
-    int rc;
-    int blk = 0;
-    bool t1_ready = false;                                   // ws_t1 already holds this block's conv1 output (fused pair)
-    bool pooled = false;                                     // the last convolution wrote the pooled features itself
-    // Fragment-tiled intermediates (ap_common.h: ap_tiled_off): a tensor whose ONLY reader is the fused pair kernel is stored
-    // as [M/16][C/8][16 pixels][8 channels], the order the pair kernel's lanes fetch it in -- t2 of every pair block, and a
-    // pair block's output when the next block is an identity pair block that also got its conv1 from this kernel.  Same
-    // values, same arithmetic: the features are bit-identical with the layout off (ap_net_set_tiled).
-    const bool tiling = bf && h->tiled && conv_mode < 0;
-    auto is_pair = [&](const ap_net::Block& X) {
-        return bf && h->fuse_pair && X.pair_p && &X != &h->blocks.back() && (!X.has_down || h->fuse_ds);
-    };
     bool cur_tiled = false;                                  // layout of `cur`
-    // conv_pw.hip: automatic rule = conv1 only (layer4 at 512 images: 156 / 70 / 71 -> 136 / 60 / 61 us; whole bench +1.0 % single
-    // pass, +0.6 % with two concurrent passes).  conv3 + identity (2: forced) is 3-9 us slower than the lean kernel and, beside a
-    // concurrent pass, turns the gain into -0.5 %: a one-wave-per-SIMD kernel keeps the other pass's workgroups off its CUs
-    const int pw_conv = h->pw_conv;
-    for (auto& B : h->blocks) {
-        if (signal_at >= 2 && blk++ == signal_at - 2) HIP_TRY(hipEventRecord(h->ev_skew, st));
+    bool pooled = false;                                     // the last convolution wrote the pooled features itself
+#define LAUNCH(expr) do { HIP_TRY(expr); ++h->conv_launches; } while (0)   /* a launch of the conv stack: counted where it is issued */
+    // a convolution + BN (+ residual) (+ ReLU) on the generic kernels
+    auto conv = [&](const Layer& L, const void* x, int Hin, const void* res, void* y, int relu, int y_tiled) {
+        return launch_conv(L.desc(), x, n, Hin, Hin, res, y, relu, y_tiled, nullptr, 0, nullptr, nullptr, prec, mode, w.rflag, st);
+    };
+    for (size_t i = 0; i < h->blocks.size(); ++i) {
+        const ap_net::Block& B = h->blocks[i];
+        const BlockPlan& p = plan[i];
+        if (signal_at >= 2 && (int)i == signal_at - 2) HIP_TRY(hipEventRecord(h->ev_skew, st));
         const int Ho = (H + 2 - 3) / B.c2.stride + 1;
-        if (bf && h->fuse_block && B.c2.cout == 64 && B.c2.stride == 1 && H % 14 == 0 && (!B.has_down || B.c1.cin == 64)) {
-            // layer1: conv1 -> conv2 -> conv3 (+identity | folded downsample) in one kernel, intermediates in LDS
-            const Layer& L3 = B.has_down ? B.c3ds : B.c3;
-            // last block of layer1: conv1 of layer2.0 (model_copenet.py:29-31) on the block output while it is in registers; what
-            // is left to read of that output is layer2.0's stride-2 downsample branch (:41-42, :97-102) -> even pixels only
-            const ap_net::Block* Nx = &B != &h->blocks.back() ? &B + 1 : nullptr;
-            const bool tail = h->fuse_tail && !B.has_down && Nx && Nx->has_down && Nx->c1.cin == 256 && Nx->c1.cout == 128 &&
-                              Nx->c2.stride == 2 && Nx->down.stride == 2 && conv_mode < 0;
-            if ((rc = run_bneck64(B.c1, B.c2, L3, B.has_down, cur, n, H, nxt, prec, st, w.rflag, tail ? &Nx->c1 : nullptr,
-                                  w.ws_t1.p, tail && h->even_out)))
-                return rc;
-            ++h->conv_launches;
-            t1_ready = tail;
+        const Layer& L3 = B.has_down ? B.c3ds : B.c3;
+        if (p.form == B_BNECK) {
+            const Layer* c1n = p.tail ? &h->blocks[i + 1].c1 : nullptr;
+            if (B.c1.cin != (B.has_down ? 64 : 256) || (c1n && (c1n->k != 1 || c1n->stride != 1)))
+                return fail(AP_ESHAPE, "fused layer1 bottleneck: C_in 256 (identity) or 64 (first block); next conv1: 1x1, 256 -> 128");
+            const ConvDesc d1n = c1n ? c1n->desc() : ConvDesc{};
+            LAUNCH(launch_bneck2(B.c1.desc(), B.c2.desc(), L3.desc(), B.has_down, cur, nxt, n, H, H, c1n ? &d1n : nullptr, t1, p.y_even, prec, w.rflag, st));
             std::swap(cur, nxt);
             continue;
         }
-        bool img_fit = h->img_block == 2;
-        if (h->img_block == 1) {                             // an image per CU: 256 (512) images = one (two) full rounds; 300 = two rounds 59 % full
-            int cus = 0;
-            HIP_TRY(device_cus(&cus));
-            const long rounds = (n + cus - 1) / cus;
-            img_fit = (long)n * 8 >= rounds * cus * 7;
-        }
-        if (bf && img_fit && B.imgw.p && H == 14 && !t1_ready && !cur_tiled && conv_mode == -1) {
-            // layer3 identity block: conv1 -> conv2 -> conv3 + identity in one kernel, an image per workgroup, t1 / t2 in LDS
-            BlkImgArgs a{};
-            a.x = cur; a.y = nxt; a.wfrag = B.imgw.p; a.N = n; a.range_flag = w.rflag; a.dbg = g_conv_dbg;
-            a.s1 = B.c1.scale.as<float>(); a.h1 = B.c1.shift.as<float>();
-            a.s2 = B.c2.scale.as<float>(); a.h2 = B.c2.shift.as<float>();
-            a.s3 = B.c3.scale.as<float>(); a.h3 = B.c3.shift.as<float>();
-            HIP_TRY(H16(prec, ap_launch_block_img)(a, st));
-            ++h->conv_launches;
+        if (p.form == B_IMG) {
+            LAUNCH(launch_block_img(cur, B.imgw.p, B.c1.scale.as<float>(), B.c1.shift.as<float>(), B.c2.scale.as<float>(), B.c2.shift.as<float>(),
+                                    B.c3.scale.as<float>(), B.c3.shift.as<float>(), nxt, n, prec, w.rflag, st));
             std::swap(cur, nxt);
             continue;
         }
-        if (!t1_ready && cur_tiled) return fail(AP_ESTATE, "trunk: conv1 of a block would read a tiled block output");
-        if (!t1_ready && (rc = run_conv(B.c1, cur, n, H, H, w.ws_t1.p, nullptr, 1, prec, st, w.rflag, 0, pw_conv))) return rc;
-        h->conv_launches += (t1_ready ? 0 : 1) + 2 + ((!is_pair(B) && B.has_down && !h->fuse_ds) ? 1 : 0);   // conv1, conv2, conv3 (+ an unfused downsample)
-        t1_ready = false;
-        const bool pair = is_pair(B);
-        // conv2 of a stage's first block on conv_pw.hip (nine taps): it writes NHWC rows, so t2 stays untiled for that block's pair kernel.
-        // Automatic rule: only for a pass that has the chip to itself (l4.0.c2 164 -> 149 us, l3.0.c2 168 -> 157: +0.55 % of the whole
-        // bench there, -0.45 % beside a concurrent pass, whose workgroups a one-wave-per-SIMD kernel keeps off its CUs; ev_out marks it)
-        // conv2 of layer2.0 on the polyphase kernel (conv_s2p.hip; ap_net_set_s2p, off by default): its K order is its own, so when on it
-        // takes the layer at EVERY batch size
-        const bool c2_s2p = bf && h->s2p && B.c2s2.p && H == 56 && B.c2.stride == 2 && conv_mode == -1;
-        bool c2_pw = false;
-        if (!c2_s2p && pw_conv && pw_conv != 4 && !(pw_conv == 1 && ev_out) && B.c2.stride == 2 && conv_mode == -1) {
-            PwArgs p3;
-            int err = 0;
-            c2_pw = pw_k3_args(B.c2, n, H, H, prec, &p3) && pw_fills(p3.M, B.c2.cout, pw_conv, &err);
-            HIP_TRY((hipError_t)err);
-        }
-        const int t2_tiled = pair && tiling && !c2_pw;
-        bool c2_img = false;
-        if (bf && h->img3 && B.c2img.p && H == 28 && B.c2.stride == 1 && conv_mode == -1) {
-            c2_img = h->img3 == 2;
-            if (h->img3 == 1) {                              // half an image per CU: whole rounds of the chip
-                int cus = 0;
-                HIP_TRY(device_cus(&cus));
-                const long units = 2L * n, rounds = (units + cus - 1) / cus;
-                c2_img = units * 8 >= rounds * cus * 7;
-            }
-        }
-        if (c2_s2p) {
-            ConvS2pArgs ca{};
-            ca.x = w.ws_t1.p; ca.y = w.ws_t2.p; ca.wfrag = B.c2s2.p; ca.scale = B.c2.scale.as<float>(); ca.shift = B.c2.shift.as<float>();
-            ca.N = n; ca.y_tiled = t2_tiled; ca.range_flag = w.rflag;
-            HIP_TRY(zero_line(&ca.zero));
-            HIP_TRY(H16(prec, ap_launch_conv_s2p)(ca, st));
-        } else if (c2_img) {
-            ConvImg3Args ca{};
-            ca.x = w.ws_t1.p; ca.y = w.ws_t2.p; ca.wfrag = B.c2img.p; ca.scale = B.c2.scale.as<float>(); ca.shift = B.c2.shift.as<float>();
-            ca.N = n; ca.y_tiled = t2_tiled; ca.range_flag = w.rflag;
-            HIP_TRY(zero_line(&ca.zero));
-            HIP_TRY(H16(prec, ap_launch_conv_img3)(ca, st));
-        } else if ((rc = run_conv(B.c2, w.ws_t1.p, n, H, H, w.ws_t2.p, nullptr, 1, prec, st, w.rflag, t2_tiled, c2_pw ? pw_conv : 0))) return rc;
-        if (pair) {
-            // conv3 (+ identity | + folded downsample, ReLU) AND -- where the pair carries it -- the next block's conv1 in one
-            // kernel: the block output is written once and not read back for conv1 (model_copenet.py:38-45 of this block,
-            // :29-31 of the next)
-            const ap_net::Block& Nx = *(&B + 1);
-            const Layer& L3 = B.has_down ? B.c3ds : B.c3;
-            PairArgs a{};
-            a.t2 = w.ws_t2.p; a.wstream = B.pair.p;
-            a.s3 = L3.scale.as<float>(); a.h3 = L3.shift.as<float>();
-            a.s1 = Nx.c1.scale.as<float>(); a.h1 = Nx.c1.shift.as<float>();
-            a.out = nxt; a.t1n = w.ws_t1.p; a.M = n * Ho * Ho; a.dbg = g_conv_dbg; a.range_flag = w.rflag;
-            a.t2_tiled = t2_tiled; a.res_tiled = cur_tiled;
-            a.out_tiled = t2_tiled && B.pair_n1 > 0 && is_pair(Nx) && !Nx.has_down;
-            cur_tiled = a.out_tiled != 0;
-            a.Ho = a.Wo = Ho;
-            if (B.has_down) { a.x2 = cur; a.H2 = a.W2 = H; a.stride2 = L3.stride2; }
-            else a.res = cur;
-            // the next block is a stage's first one and got its conv1 from this kernel: all that is read of `out` is that block's
-            // stride-2 downsample branch (model_copenet.py:41-42, :97-102) -- the even pixels
-            a.out_even = h->even_out && !a.out_tiled && B.pair_n1 > 0 && Nx.has_down && Nx.down.stride == 2 && Nx.c2.stride == 2;
-            HIP_TRY(H16(prec, ap_launch_conv_pair)(a, B.pair_p, B.pair_p2, B.pair_c3, B.pair_n1, st));
-            t1_ready = B.pair_n1 > 0;
+        if (p.c1 != C1_READY && cur_tiled) return fail(AP_ESTATE, "trunk: conv1 of a block would read a tiled block output");
+        if (p.c1 == C1_PW) LAUNCH(launch_conv_pw(B.c1.desc(true), cur, nullptr, t1, n * H * H, prec, w.rflag, st));
+        else if (p.c1 == C1_CONV) LAUNCH(conv(B.c1, cur, H, nullptr, t1, 1, 0));
+        const float *s2 = B.c2.scale.as<float>(), *h2 = B.c2.shift.as<float>();
+        if (p.c2 == C2_S2P) LAUNCH(launch_conv_s2p(t1, B.c2s2.p, s2, h2, t2, n, p.t2_tiled, prec, w.rflag, st));
+        else if (p.c2 == C2_IMG3) LAUNCH(launch_conv_img3(t1, B.c2img.p, s2, h2, t2, n, p.t2_tiled, prec, w.rflag, st));
+        else if (p.c2 == C2_PW) LAUNCH(launch_conv_pw_k3(B.c2.desc(true), t1, t2, n, H, prec, w.rflag, st));
+        else LAUNCH(conv(B.c2, t1, H, nullptr, t2, 1, p.t2_tiled));
+        if (p.end == E_PAIR) {
+            const ap_net::Block& Nx = h->blocks[i + 1];
+            LAUNCH(launch_conv_pair(t2, B.pair.p, L3.scale.as<float>(), L3.shift.as<float>(), Nx.c1.scale.as<float>(), Nx.c1.shift.as<float>(), cur,
+                                    nxt, t1, n * Ho * Ho, Ho, B.has_down ? H : 0, L3.stride2, B.pair_p, B.pair_p2, B.pair_n1,
+                                    PairLayout{p.t2_tiled, p.res_tiled, p.out_tiled, p.out_even}, prec, w.rflag, st));
+            cur_tiled = p.out_tiled;
         } else if (cur_tiled) {                               // (cannot happen: out_tiled is only set when the next block is a pair block)
             return fail(AP_ESTATE, "trunk: a tiled block output reached a kernel that reads NHWC");
-        } else if (B.has_down && h->fuse_ds) {
-            if ((rc = run_c3_ds(B.c3ds, w.ws_t2.p, cur, n, Ho, H, nxt, prec, st, w.rflag, pw_conv))) return rc;
-        } else if (bf && h->fuse_pool && &B == &h->blocks.back() && !B.has_down && Ho == 7 && conv_mode == -1) {
-            // last convolution of the trunk: conv3 + bn3 + identity + ReLU AND AvgPool2d(7) + view in one kernel
-            // (model_copenet.py:38-47 of layer4.2, then :173-175); the block output is never written
-            ConvArgs a{};
-            a.x = w.ws_t2.p; a.w = B.c3.w.p; a.scale = B.c3.scale.as<float>(); a.shift = B.c3.shift.as<float>(); a.res = cur; a.y = nullptr;
-            a.N = n; a.H = a.W = a.Ho = a.Wo = Ho; a.Cin = B.c3.cin; a.Cout = B.c3.cout;
-            a.KH = a.KW = 1; a.stride = 1; a.pad = 0; a.M = n * Ho * Ho;
-            a.ldx = B.c3.cin; a.ldy = B.c3.cout; a.ldr = B.c3.cout; a.wld = B.c3.wld; a.relu = 1;
-            a.pool_out = feat; a.range_flag = w.rflag;
-            HIP_TRY(zero_line(&a.zero));
-            if (k_bf16::ap_conv_lean_supported(a, kind)) {
-                HIP_TRY(H16(prec, ap_launch_conv_lean)(a, st));
-                pooled = true;
-            } else if ((rc = run_conv(B.c3, w.ws_t2.p, n, Ho, Ho, nxt, cur, 1, prec, st, w.rflag))) return rc;
+        } else if (p.end == E_FOLD_PW) {
+            LAUNCH(launch_conv_pw_ds(L3.desc(true), t2, cur, nxt, n, Ho, H, prec, w.rflag, st));
+        } else if (p.end == E_FOLD) {
+            LAUNCH(launch_conv(L3.desc(), t2, n, Ho, Ho, nullptr, nxt, 1, 0, cur, H, nullptr, nullptr, prec, mode, w.rflag, st));
+        } else if (p.end == E_POOL) {
+            // conv3 + bn3 + identity + ReLU AND AvgPool2d(7) + view in one kernel (model_copenet.py:38-47 of layer4.2, then :173-175);
+            // the block output is never written
+            LAUNCH(launch_conv(B.c3.desc(), t2, n, Ho, Ho, cur, nxt, 1, 0, nullptr, 0, feat, &pooled, prec, mode, w.rflag, st));
+        } else if (p.end == E_C3_PW) {
+            LAUNCH(launch_conv_pw(B.c3.desc(true), t2, cur, nxt, n * Ho * Ho, prec, w.rflag, st));
         } else {
-            const void* res = cur;
-            if (B.has_down) {
-                if ((rc = run_conv(B.down, cur, n, H, H, w.ws_ds.p, nullptr, 0, prec, st, w.rflag))) return rc;
-                res = w.ws_ds.p;
-            }
-            if ((rc = run_conv(B.c3, w.ws_t2.p, n, Ho, Ho, nxt, res, 1, prec, st, w.rflag, 0, (B.has_down || pw_conv != 2) ? 0 : pw_conv))) return rc;   // (conv3 + identity: 89-95 us against the lean kernel's 86: only when forced)
+            if (p.end == E_DS_C3) LAUNCH(conv(B.down, cur, H, nullptr, w.ws_ds.p, 0, 0));
+            LAUNCH(conv(B.c3, t2, Ho, p.end == E_DS_C3 ? w.ws_ds.p : cur, nxt, 1, 0));
         }
         std::swap(cur, nxt);
         H = Ho;
     }
+#undef LAUNCH
     if (h->tm.on) HIP_TRY(h->tm.rec(st, &e2));
-    if (!pooled) HIP_TRY(H16(prec, ap_launch_avgpool)(cur, feat, n, 2048, kind, w.rflag, st));
+    if (!pooled) HIP_TRY(launch_avgpool(cur, feat, n, 2048, prec, w.rflag, st));
     if (h->tm.on == 1) HIP_TRY(h->tm.rec(st, &e3));
     if (ev_out) {                                            // the caller combines the events of two concurrent passes
         ev_out[0] = e0; ev_out[1] = e1; ev_out[2] = e2; ev_out[3] = e3;
@@ -489,7 +386,7 @@ int trunk_passes(ap_net* h, const float* x0, int n0, const float* x1, int n1, fl
                 c = cnt / nr + (r < cnt % nr ? 1 : 0);
                 const float* xv = (v ? x1 : x0) + (size_t)(lo + s0) * IMG_ELEMS;
                 rc = trunk_chunk(h, h->tw[q], xv, c, nullptr, 0, feat + ((v ? (size_t)n0 : 0) + lo + s0) * 2048, h->aux[q],
-                                 &ev[((size_t)q * rounds + r) * 4], (q == 0 && np == 2 && r == 0) ? h->dual_skew : 0);
+                                 true, &ev[((size_t)q * rounds + r) * 4], (q == 0 && np == 2 && r == 0) ? h->dual_skew : 0);
             }
         }
         // ap_net_range_mark_next: each pass stream snapshots ITS range word behind its last kernel of this call
@@ -538,7 +435,7 @@ int trunk_passes(ap_net* h, const float* x0, int n0, const float* x1, int n1, fl
         const int a0 = std::min(i0, n0), a1 = std::min(i1, n0);          // part taken from x0
         const int b0 = std::max(i0, n0) - n0, b1 = std::max(i1, n0) - n0; // part taken from x1
         int rc = trunk_chunk(h, h->tw[0], x0 + a0 * IMG_ELEMS, a1 - a0, x1 ? x1 + b0 * IMG_ELEMS : nullptr, b1 - b0,
-                             feat + (size_t)i0 * 2048, st);
+                             feat + (size_t)i0 * 2048, st, false);
         if (rc) return rc;
     }
     if (h->mark_slot >= 0 && h->range_flag) HIP_TRY(ap_launch_word_copy(h->range_flag, h->range_slots + 4 * h->mark_slot, st));

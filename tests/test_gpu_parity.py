@@ -2760,3 +2760,66 @@ def test_trunk_with_polyphase_conv2_is_close_to_the_generic_path(netf16, dev):
     print("trunk, polyphase conv2 vs generic: %.3e" % e)
     assert 0.0 < e < 2e-3                                     # (0: the knob did nothing)
     assert torch.equal(again, got)                            # and reproducible
+
+
+# (knob, value, images) -> conv-stack launches of one 16-bit pass with every other knob at its default
+LAUNCHES_16BIT = [
+    (None, None, 2, 33),                  # 3 layer1 kernels + 4 x 2 (layer2) + 2 + 3 + 4 x 2 (layer3) + 3 x 3 (layer4)
+    ("set_img_block", 2, 2, 27),          # layer3.1 .. 3.5 as one kernel each
+    ("set_img_block", 0, 2, 33),
+    ("set_fuse_pair", 0, 2, 41),
+    ("set_fuse_block", 0, 2, 40),
+    ("set_fuse_tail", 0, 2, 34),
+    ("set_pw_conv", 0, 4, 33),            # 4 images: one 196-pixel tile at 7 x 7
+    ("set_pw_conv", 2, 4, 33),
+    ("set_img3", 0, 2, 33),
+    ("set_img3", 2, 2, 33),
+    ("set_s2p", 1, 2, 33),
+    ("set_fuse_pool", 1, 2, 33),
+]
+KNOB_DEFAULTS = {"set_img_block": 1, "set_fuse_pair": 1, "set_fuse_block": 1, "set_fuse_tail": 1, "set_pw_conv": 1, "set_img3": 1,
+                 "set_s2p": 0, "set_fuse_pool": 0}
+
+
+def test_conv_launch_counts_of_one_pass(net32, netbf, netf16, dev):
+    """What ap_net_last_conv_launches reports after ONE trunk pass (set_dual_stream(0)) is pinned: it is the number bench.py prints
+    and the only outside view of which kernels the schedule chose.  fp32: every block as three convolutions, 48, and 52 with the
+    four downsample convolutions unfused.  16-bit: 27 when the pass fills whole rounds of the chip with the image-resident layer3
+    blocks (n * 8 >= ceil(n / CUs) * CUs * 7: the two batch sizes on either side of the first threshold), 33 when it does not
+    (54 / 66 for two passes).  The rows of LAUNCHES_16BIT that neither follows from are what the library returned through
+    this call before the schedule was split into a plan and a launching loop -- equalities, no margin."""
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    n_fill = (cus * 7 + 7) // 8                               # smallest n with n * 8 >= cus * 7 (224 on 256 CUs)
+    x = torch.randn(n_fill, 3, 224, 224, generator=torch.Generator(device="cpu").manual_seed(2700)).to(dev)
+
+    def count(net, n):
+        net.forward_feat_ext(x[:n])
+        return net.last_conv_launches()
+
+    got, want = {}, {}
+    try:
+        for net in (net32, netbf, netf16):
+            net.set_dual_stream(0)
+        got["fp32"], want["fp32"] = count(net32, 2), 48
+        net32.set_fuse_ds(0)
+        got["fp32 fuse_ds 0"], want["fp32 fuse_ds 0"] = count(net32, 2), 52
+        for name, net in (("bf16", netbf), ("f16", netf16)):
+            got[name, "fills", n_fill], want[name, "fills", n_fill] = count(net, n_fill), 27
+            got[name, "fills", n_fill - 1], want[name, "fills", n_fill - 1] = count(net, n_fill - 1), 33
+            for knob, value, n, launches in LAUNCHES_16BIT:
+                if knob:
+                    getattr(net, knob)(value)
+                got[name, knob, value, n], want[name, knob, value, n] = count(net, n), launches
+                if knob:
+                    getattr(net, knob)(KNOB_DEFAULTS[knob])
+    finally:
+        net32.set_fuse_ds(1)
+        for net in (net32, netbf, netf16):
+            net.set_dual_stream(1)
+        for net in (netbf, netf16):
+            for knob, value in KNOB_DEFAULTS.items():
+                getattr(net, knob)(value)
+    torch.cuda.synchronize()
+    for k in got:
+        print("conv launches", k, got[k], "want", want[k])
+    assert got == want
