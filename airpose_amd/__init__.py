@@ -14,6 +14,8 @@ Public mirrors of the reference interfaces:
   AirPosePlusSequence (sequence.py)    <- copenet_real_data/scripts/bundle_adj.py around its loop: network outputs in, fitted bodies out
   RealSequenceBatches (real_batches.py) <- copenet_real/dsets/copenet_real.py __getitem__ and its agreement filter: frames and raw
                                           detections in, the batch dict of TwoViewInference / RealDataLoss out, boxes kept on the device
+  SyntheticBatches (synth_batches.py)  <- copenet/src/copenet/dsets/aerialpeople.py __getitem__: AerialPeople records and images in,
+                                          the batch dict of the trainers, TrainingLoss, EvalMetrics and MeshMetrics out
 The compute lives in libairpose_hip.so (include/airpose_hip.h); nothing here falls back to CPU.
 """
 __version__ = "0.1.0"
@@ -45,4 +47,7 @@ def __getattr__(name):
     if name == "RealSequenceBatches":                                     # likewise (real_batches.py)
         from .real_batches import RealSequenceBatches
         return RealSequenceBatches
+    if name == "SyntheticBatches":                                        # likewise (synth_batches.py)
+        from .synth_batches import SyntheticBatches
+        return SyntheticBatches
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -88,7 +88,13 @@ SIGNATURES = {
     "apg_seq_export": (_i, [_i] + [_vp] * 13 + [_vp]),
     # real-data batches (seq_batch.hip); principal and size are HOST arrays
     "apg_real_batch": (_i, [_i, _i, _i, _vp, _c.POINTER(_f), _ip, _f, _i] + [_vp] * 6 + [_vp]),
+    # synthetic-data batches (synth_batch.hip): 9 inputs and 14 outputs, all device pointers
+    "apg_synth_batch": (_i, [_i] * 11 + [_f, _f, _u64, _i] + [_vp] * 9 + [_vp] * 14 + [_vp]),
+    "apg_synth_crops": (_i, [_i] * 4 + [_vp] * 6 + [_vp]),
 }
+SYNTH_ORIGINS = {"region": 0, "frame": 1}                    # include/airpose_grad.h: APG_SYNTH_ORIGIN_*
+SYNTH_CLAMPED, SYNTH_WIDENED, SYNTH_OUTSIDE = 1, 2, 4        # include/airpose_grad.h: APG_SYNTH_*, the bits of status
+SYNTH_THREADS = 128      # include/airpose_grad.h: APG_SYNTH_THREADS
 SEQ_ROWS = 4             # include/airpose_grad.h: APG_SEQ_ROWS
 BATCH_WAVES = 4          # include/airpose_grad.h: APG_BATCH_WAVES
 BATCH_FALLBACK, BATCH_CLAMPED, BATCH_WIDENED = 1, 2, 4       # include/airpose_grad.h: APG_BATCH_*, the bits of status

@@ -662,6 +662,79 @@ int apg_seq_export(int L, const float* z, const float* phi, const float* tau, co
 int apg_real_batch(int L, int a, int n, const float* det, const float* principal, const int* size, float agreement_px, int border,
                   float* j2d, int* crops, int* crop_info, float* bb, float* j2d_crop, int* status, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Synthetic-data batches (synth_batch.hip): what aerialpeople_crop.__getitem__ (copenet/src/copenet/dsets/aerialpeople.py:81-226)
+ * computes between a sample's pickled record and the batch dict, for n samples and both cameras, apart from the file reading and the
+ * SMPL-X forward of the canonical body (:179-197, which airpose_amd.SyntheticBatches runs on the existing ap_smplx_fwd).
+ * apg_synth_batch: the jittered crop box of each camera (:98-135), bb, the ground truth in each camera's frame (:148-177 with
+ * transform_smpl, utils.py:237-256, and perspective_projection with R = I, t = 0), smplpose_rotmat (lbs.batch_rodrigues, epsilon
+ * 1e-8) and the per-sample camera shuffle (:208-211).  It reads no image.  apg_synth_crops: the images, from the boxes and the flips
+ * that apg_synth_batch left on the device.  Nobody validates a box on the host, so THE KERNEL guarantees the box invariant below for
+ * any bit pattern in bb_in.  Additive under ABI 2: a binding tells a library that has them by looking up apg_synth_batch.
+ * Stateless, no workspace; all pointers are device pointers to contiguous arrays, 4-byte aligned (frames: any alignment).
+ *
+ * apg_synth_batch, inputs (c = camera 0 / 1, i < n):
+ *   n in 1 .. 65535; V in 1 .. 2^24 vertices; J in 1 .. 2^16 joints; H, W: the frame's size, 1 .. 2^20; Hc, Wc: the canvas's size
+ *   (the images apg_synth_crops will read), 1 .. 2^20; margin: whole pixels, 0 .. 2^20 (the reference: 200).
+ *   origin: APG_SYNTH_ORIGIN_REGION (0) the canvas holds the region [ymin:ymax, xmin:xmax] of the frame at its top-left (the
+ *     reference's pre-cropped dataset), APG_SYNTH_ORIGIN_FRAME (1) the canvas is the whole frame.
+ *   jitter, shuffle: 0 or 1; 0 sets the four offsets / the flip to 0.  fx, fy: the focal length (the reference: 1475), finite.
+ *   seed, epoch: see the draws.  index (n) int32: the samples' dataset indices.
+ *   bb_in (n, 2, 2, 2) int32 = [[x0, y0], [x1, y1]] per camera; intr (n, 2, 3, 3); extr (n, 2, 4, 4) (rows 0 .. 2 are [R | t]);
+ *   pose (n, 63) axis-angle; verts (n, V, 3), joints (n, J, 3), orient (n, 3, 3), trans (n, 3): the *_wrt_origin fields; all fp32.
+ * The box, per (i, c) and per axis (y with H and Hc, x with W and Wc), in 32-bit integers that cannot overflow:
+ *   y0, y1 are clamped to [0, H] (rule 1).
+ *   ymin = y0 - margin if y0 - margin > 0 else 0;  ymax = y1 + margin if y1 + margin < H else H  (both comparisons strict).
+ *   The draws: Philox4x32-10 (Random123's constants), key = (seed's low word, seed's high word), counter = (index[i], epoch, c, 0).
+ *     Its words 0 .. 3 give the offsets in the reference's draw order -- ymin side, ymax side, xmin side, xmax side -- over the
+ *     ranges r = y0 - ymin, ymax - y1, x0 - xmin, xmax - x1: offset = 0 if r == 0 else mulhi32(word, r), which is in [0, r).
+ *     flip[i] = bit 31 of word 0 of the counter (index[i], epoch, 2, 0).  A draw depends on (seed, epoch, index, camera) alone.
+ *   The crop is [ymin + o0, ymax - o1); if that is empty it becomes the one pixel [min(ymin + o0, H - 1), + 1) (rule 2).
+ *   crop_info = [[ymin, xmin], [ymax, xmax]]: the region, as in the reference, NOT the crop.
+ *   Canvas coordinates are the crop minus ymin (origin region) or minus 0 (origin frame); if they leave [0, Hc] they are clamped
+ *     to 0 <= y0' <= Hc - 1, y0' + 1 <= y1' <= Hc (rule 3).  `crops` holds them; bb and scale are taken from the same box, moved back.
+ * The box invariant, for ANY bb_in: 0 <= y0' < y1' <= Hc and 0 <= x0' < x1' <= Wc.  Each rule is the identity wherever the
+ * reference itself works (a box inside the frame, a crop that is not empty, a canvas that holds the region or the frame).
+ * Outputs, every element written, indexed by SUFFIX s: suffix s of sample i is camera flip[i] ^ s.
+ *   crops (2, n, 4) int32 = y0', y1', x0', x1' (canvas, the layout ap_preprocess_crops reads); crop_info (2, n, 2, 2) int32;
+ *   status (2, n) int32: bit 0 (APG_SYNTH_CLAMPED) rule 1 moved a corner, bit 1 (APG_SYNTH_WIDENED) rule 2, bit 2
+ *     (APG_SYNTH_OUTSIDE) rule 3;  flip (n) int32 = 0 or 1.
+ *   bb (2, n, 3) = ((xa + xb) / 2 / cx - 1, (ya + yb) / 2 / cy - 1, scale): xa, xb, ya, yb the box in FRAME coordinates, cx =
+ *     intr[i, c, 0, 2], cy = intr[i, c, 1, 2], each operation rounded to fp32 in that order; scale = (float)(224.0 / (double)max(h, w)),
+ *     the expression of ap_preprocess_crops and apg_synth_crops: the scales are bit-equal.
+ *   intr_out (2, n, 3, 3), extr_out (2, n, 4, 4): copies.
+ *   verts_rel (2, n, V, 3), joints_rel (2, n, J, 3) = R p + t evaluated as ((R0 x + R1 y) + R2 z) + t, every product and sum
+ *     rounded to fp32 once (no fused multiply-add); each vertex is read once and written for both cameras.
+ *   orient_rel (2, n, 3, 3) = R orient and trans_rel (2, n, 3) = R trans + t, sums in the same order.
+ *   j2d (2, n, J, 2) = (fx (x / z) + cx, fy (y / z) + cy) of joints_rel; j2d_crop (2, n, J, 2) = scale * (j2d - (bb_xy + 1) * c),
+ *     no pad offset (the reference applies none); each operation rounded to fp32.
+ *   pose_rotmat (n, 21, 3, 3) = I + sin(a) K + (1 - cos(a)) K K, a = |r + 1e-8|, K the cross-product matrix of r / a, K K summed
+ *     in bmm's order.
+ * Two launches on `stream` (the per-sample records and joints; the vertices), no LDS traffic between samples, no atomic, every sum
+ * in a fixed order: bit-identical from run to run.  No host synchronisation.
+ *
+ * apg_synth_crops: one launch over (pixel, sample, suffix).  frames (2 cameras, n, Hc, Wc, 3) uint8; bgr as ap_preprocess_crops;
+ *   crops (2, n, 4) and flip (n) as apg_synth_batch wrote them.  For suffix s of sample i it reads the canvas of camera
+ *   (flip[i] & 1) ^ s through crops[s, i] and writes im (2, n, 3, 224, 224), scale (2, n), pad (2, n, 2) int32 = left, top.  The
+ *   per-pixel arithmetic is ONE source with ap_preprocess_crops (csrc/preprocess_px.inc): the same bits for the same box.  A row
+ *   whose box breaks the invariant is neither read through nor written (apg_synth_batch writes no such box).
+ * APG_EINVAL before any GPU call, the message naming the argument: a NULL or misaligned pointer, a size outside its limits, origin,
+ * jitter, shuffle or bgr outside their values, fx or fy not finite, an output that is its own input. */
+#define APG_SYNTH_ORIGIN_REGION 0
+#define APG_SYNTH_ORIGIN_FRAME 1
+#define APG_SYNTH_CLAMPED 1
+#define APG_SYNTH_WIDENED 2
+#define APG_SYNTH_OUTSIDE 4
+#define APG_SYNTH_THREADS 128
+int apg_synth_batch(int n, int V, int J, int H, int W, int Hc, int Wc, int margin, int origin, int jitter, int shuffle, float fx,
+                    float fy, uint64_t seed, int epoch, const int* index, const int* bb_in, const float* intr, const float* extr,
+                    const float* pose, const float* verts, const float* joints, const float* orient, const float* trans, int* crops,
+                    int* crop_info, int* status, int* flip, float* bb, float* intr_out, float* extr_out, float* verts_rel,
+                    float* joints_rel, float* orient_rel, float* trans_rel, float* j2d, float* j2d_crop, float* pose_rotmat,
+                    void* stream);
+int apg_synth_crops(int n, int Hc, int Wc, int bgr, const unsigned char* frames, const int* crops, const int* flip, float* im,
+                    float* scale, int* pad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
