@@ -11,6 +11,8 @@ Public mirrors of the reference interfaces:
   EvalMetrics (eval_metrics.py)        <- test_epoch_end of the four trainers: MPJPE, MPE, angle error
   Renderer (renderer.py)               <- utils/renderer.py Renderer: visualize_tb of the trainers' summaries(), without pyrender
   MeshMetrics (mesh_metrics.py)        <- no counterpart in the reference: MPJPE / PVE, absolute, root- and Procrustes-aligned
+  CrossViewMetrics (cross_view_metrics.py) <- copenet_real/scripts/*_res_compile.py and utils/geometry.py lstsq_triangulation: real
+                                          two-view data scored without ground truth (cross-view gaps, reprojection, triangulation)
   AirPosePlusSequence (sequence.py)    <- copenet_real_data/scripts/bundle_adj.py around its loop: network outputs in, fitted bodies out
   RealSequenceBatches (real_batches.py) <- copenet_real/dsets/copenet_real.py __getitem__ and its agreement filter: frames and raw
                                           detections in, the batch dict of TwoViewInference / RealDataLoss out, boxes kept on the device
@@ -41,6 +43,9 @@ def __getattr__(name):
     if name == "MeshMetrics":                                             # likewise (mesh_metrics.py)
         from .mesh_metrics import MeshMetrics
         return MeshMetrics
+    if name == "CrossViewMetrics":                                        # likewise (cross_view_metrics.py)
+        from .cross_view_metrics import CrossViewMetrics
+        return CrossViewMetrics
     if name == "AirPosePlusSequence":                                     # likewise (sequence.py)
         from .sequence import AirPosePlusSequence
         return AirPosePlusSequence

@@ -83,6 +83,11 @@ SIGNATURES = {
     "apg_align_workspace_bytes": (_i64, [_i, _i, _i]),
     "apg_align_acc_doubles": (_i64, []),
     "apg_align_update": (_i, [_i, _i, _i] + [_i64] * 4 + [_vpp] + [_vp] * 4 + [_i64, _vp]),
+    # the cross-view metrics (xview_metrics.hip); strides is a HOST array
+    "apg_xview_workspace_bytes": (_i64, [_i, _i, _i]),
+    "apg_xview_acc_doubles": (_i64, []),
+    "apg_xview_update": (_i, [_i] * 5 + [_c.POINTER(_i64), _vpp, _c.c_double] + [_vp] * 4 + [_i64, _vp]),
+    "apg_xview_triangulate": (_i, [_i, _i] + [_vp] * 6 + [_c.c_double, _vp, _vp]),
     # AirPose+ on a whole sequence (seq_fit.hip)
     "apg_seq_init": (_i, [_i] + [_vp] * 9 + [_f, _f] + [_vp] * 5 + [_vp]),
     "apg_seq_export": (_i, [_i] + [_vp] * 13 + [_vp]),

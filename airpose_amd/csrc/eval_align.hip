@@ -62,29 +62,6 @@ struct AlignArgs {
 
 static_assert(2 * (3 + 1) <= COMBINE_NT && 3 + 1 <= ACC, "metric_combine_kernel: a thread per (view, sum) and one per view");
 
-// v[k] summed over the workgroup in a fixed order; every thread returns with the totals in tot[0 .. NV)
-template <int NT, int NV>
-__device__ __forceinline__ void wg_sum(double (&v)[NV], double* red, double* tot) {
-    constexpr int NW = NT / 64;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v[k] += __shfl_down(v[k], d);
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) red[wave * NV + k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < NV) {
-        double s = red[threadIdx.x];
-        for (int w = 1; w < NW; ++w) s += red[w * NV + threadIdx.x];      // waves in index order
-        tot[threadIdx.x] = s;
-    }
-    __syncthreads();
-}
-
 // entry (i, j) of a symmetric 4 x 4 matrix kept as its upper triangle, row by row
 __host__ __device__ constexpr int tri(int i, int j) { return i <= j ? 4 * i - i * (i - 1) / 2 + (j - i) : 4 * j - j * (j - 1) / 2 + (i - j); }
 

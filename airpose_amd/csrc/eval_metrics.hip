@@ -46,7 +46,6 @@ constexpr int NJ = 22;                   // body joints
 constexpr int ITEMS = ET / 2;            // (sample, view) pairs per workgroup: two chains each
 constexpr int NSUM = 25;                 // sums per view and workgroup: all joints, each joint (22), translation, angle
 constexpr int ACC = APG_EVAL_ACC_PER_VIEW;
-constexpr float EPS = 1e-6f;
 
 struct EvalArgs {
     int B, views, matrix;
@@ -63,25 +62,7 @@ struct EvalArgs {
 
 static_assert(2 * (NSUM + 1) <= COMBINE_NT && NSUM + 1 <= ACC, "metric_combine_kernel: a thread per (view, sum) and one per view");
 
-__device__ __forceinline__ void aa_to_rotmat(float x, float y, float z, float* R) {
-    const float t2 = fmaf(z, z, fmaf(y, y, x * x));
-    if (t2 > EPS) {
-        const float th = sqrtf(t2);
-        const float d = th + EPS;
-        const float wx = x / d, wy = y / d, wz = z / d;
-        const float c = cosf(th), s = sinf(th);
-        const float omc = 1.f - c;
-        const float ax = wx * omc, ay = wy * omc, az = wz * omc;
-        const float sx = wx * s, sy = wy * s, sz = wz * s;
-        R[0] = fmaf(wx, ax, c), R[1] = fmaf(wx, ay, -sz), R[2] = fmaf(wx, az, sy);
-        R[3] = fmaf(wx, ay, sz), R[4] = fmaf(wy, ay, c), R[5] = fmaf(wy, az, -sx);
-        R[6] = fmaf(wx, az, -sy), R[7] = fmaf(wy, az, sx), R[8] = fmaf(wz, az, c);
-    } else {
-        R[0] = 1.f, R[1] = -z, R[2] = y;
-        R[3] = z, R[4] = 1.f, R[5] = -x;
-        R[6] = -y, R[7] = x, R[8] = 1.f;
-    }
-}
+#include "rot_aa.inc"                    // aa_to_rotmat
 
 __global__ void __launch_bounds__(ET) eval_main_kernel(const EvalArgs a) {
     __shared__ float sm[(NJ - 1) * 12 * ET];             // the walk: sm[(j * 12 + c) * ET + lane]; afterwards the per-sample errors

@@ -1,8 +1,31 @@
-// What the two metric sources of libairpose_grad.so share, once, for eval_metrics.hip and eval_align.hip: the fp32 norm every error
-// is, the combine kernel that makes both metrics bit-reproducible, and the host checks of the arguments the two entry points have in
-// common.  Included inside each file's unnamed namespace, after its `#pragma clang fp contract(off)`.
+// What the metric sources of libairpose_grad.so share, once, for eval_metrics.hip, eval_align.hip and xview_metrics.hip: the fp32 norm
+// every error is, the workgroup's fixed-order fp64 sum, the combine kernel that makes the metrics bit-reproducible, and the host checks
+// of the arguments the entry points have in common.  Included inside each file's unnamed namespace, after its `#pragma clang fp contract(off)`.
 
 __device__ __forceinline__ float norm3(float d0, float d1, float d2) { return sqrtf(fmaf(d2, d2, fmaf(d1, d1, d0 * d0))); }
+
+// v[k] summed over the workgroup in a fixed order; every thread returns with the totals in tot[0 .. NV)
+template <int NT, int NV>
+__device__ __forceinline__ void wg_sum(double (&v)[NV], double* red, double* tot) {
+    constexpr int NW = NT / 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) v[k] += __shfl_down(v[k], d);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) red[wave * NV + k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < NV) {
+        double s = red[threadIdx.x];
+        for (int w = 1; w < NW; ++w) s += red[w * NV + threadIdx.x];      // waves in index order
+        tot[threadIdx.x] = s;
+    }
+    __syncthreads();
+}
 
 constexpr int COMBINE_NT = 64;           // one workgroup of one wave: a thread per (view, sum), then one per view for the counts
 constexpr int COMBINE_COUNTS = 3;

@@ -1,6 +1,6 @@
 // The 3-vector and the rotation matrix -> axis-angle map with its adjoint, once, for fitting.hip (libairpose_hip.so: the fitter's
-// decoder output) and loss_real_grad.hip (libairpose_grad.so: the VPoser prior's way in and back).  Included inside each file's
-// unnamed namespace.
+// decoder output) and loss_real_grad.hip (libairpose_grad.so: the VPoser prior's way in and back), and the axis-angle -> rotation
+// matrix map of eval_metrics.hip and xview_metrics.hip.  Included inside each file's unnamed namespace.
 
 struct V3 { float x, y, z; };
 __device__ __forceinline__ V3 v3(float x, float y, float z) { return V3{x, y, z}; }
@@ -66,4 +66,26 @@ __device__ __forceinline__ void aa_bwd(const AA& a, V3 daa, float* dr) {
     }
     // t00 = r[0], t10 = r[1], t20 = r[2], t01 = r[3], t11 = r[4], t21 = r[5], t02 = r[6], t12 = r[7], t22 = r[8]
     dr[0] = d00; dr[1] = d10; dr[2] = d20; dr[3] = d01; dr[4] = d11; dr[5] = d21; dr[6] = d02; dr[7] = d12; dr[8] = d22;
+}
+
+// axis-angle -> rotation matrix (row-major R[9]), tgm 0.1.2's angle_axis_to_rotation_matrix: the formula is in eval_metrics.hip's
+// head and in include/airpose_grad.h; every fused product is an explicit fmaf (the including files turn contraction off)
+__device__ __forceinline__ void aa_to_rotmat(float x, float y, float z, float* R) {
+    const float t2 = fmaf(z, z, fmaf(y, y, x * x));
+    if (t2 > 1e-6f) {
+        const float th = sqrtf(t2);
+        const float d = th + 1e-6f;
+        const float wx = x / d, wy = y / d, wz = z / d;
+        const float c = cosf(th), s = sinf(th);
+        const float omc = 1.f - c;
+        const float ax = wx * omc, ay = wy * omc, az = wz * omc;
+        const float sx = wx * s, sy = wy * s, sz = wz * s;
+        R[0] = fmaf(wx, ax, c), R[1] = fmaf(wx, ay, -sz), R[2] = fmaf(wx, az, sy);
+        R[3] = fmaf(wx, ay, sz), R[4] = fmaf(wy, ay, c), R[5] = fmaf(wy, az, -sx);
+        R[6] = fmaf(wx, az, -sy), R[7] = fmaf(wy, az, sx), R[8] = fmaf(wz, az, c);
+    } else {
+        R[0] = 1.f, R[1] = -z, R[2] = y;
+        R[3] = z, R[4] = 1.f, R[5] = -x;
+        R[6] = -y, R[7] = x, R[8] = 1.f;
+    }
 }

@@ -2,6 +2,8 @@
 (copenet/src/copenet/utils/geometry.py:47-61 rot6d_to_rotmat, :63-91 perspective_projection).
 Each is one launch of a hand-written HIP kernel through the C ABI; no CPU path.  rot6d_to_rotmat and perspective_projection are
 differentiable when an input requires grad: the forward is the same kernel, the backward a kernel of libairpose_grad.so."""
+import math
+
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -141,3 +143,38 @@ def perspective_projection(points, rotation, translation, focal_length, camera_c
     if _grad_wanted(points, rotation, translation, cc):
         return _Projection.apply(points, rotation, translation, cc, fx, fy)
     return _projection_fwd(points, rotation, translation, fx, fy, cc)
+
+
+def lstsq_triangulation(intrinsic, extrinsic, points_2d, min_ray_angle_deg=0.0):
+    """The batched two-camera mirror of the reference's lstsq_triangulation (copenet_real utils/geometry.py:160-192), one launch of
+    apg_xview_triangulate (libairpose_grad.so), solved per joint in fp64 on the device.
+    intrinsic (B, 2, 3, 3) (fx, fy, cx, cy are read: the reference's K^-1 agrees where the skew is 0); extrinsic (B, 2, 4, 4) or
+    (B, 2, 3, 4), world -> camera; points_2d (B, 2, J, 2) or (B, 2, J, 3) with a confidence (absent: 1).
+    -> (points (B, J, 3) in the world frame, valid (B, J) bool).  A joint is valid where both confidences are > 0, both points are
+    finite, the extrinsics are finite and orthonormal to 1e-3 and the two rays meet at min_ray_angle_deg or more; points is 0
+    elsewhere."""
+    dev = _cuda(points_2d, "lstsq_triangulation")
+    if points_2d.dim() != 4 or points_2d.shape[1] != 2 or points_2d.shape[3] not in (2, 3) or points_2d.shape[2] < 1:
+        raise RuntimeError("lstsq_triangulation: points_2d must be (B, 2, J, 2 or 3), got %s" % (tuple(points_2d.shape),))
+    B, J = points_2d.shape[0], points_2d.shape[2]
+    if tuple(intrinsic.shape) != (B, 2, 3, 3):
+        raise RuntimeError("lstsq_triangulation: intrinsic must be (%d, 2, 3, 3), got %s" % (B, tuple(intrinsic.shape)))
+    if tuple(extrinsic.shape) not in ((B, 2, 4, 4), (B, 2, 3, 4)):
+        raise RuntimeError("lstsq_triangulation: extrinsic must be (%d, 2, 4, 4) or (%d, 2, 3, 4), got %s" % (B, B, tuple(extrinsic.shape)))
+    if not 0.0 <= float(min_ray_angle_deg) <= 90.0:
+        raise RuntimeError("lstsq_triangulation: min_ray_angle_deg must be in 0 .. 90, got %r" % (min_ray_angle_deg,))
+    if B < 1:
+        raise RuntimeError("lstsq_triangulation: points_2d holds no sample")
+    pts = N.f32c(points_2d.detach(), dev)
+    if pts.shape[3] == 2:
+        pts = torch.cat([pts, torch.ones(B, 2, J, 1, device=dev, dtype=torch.float32)], 3)
+    K, E = N.f32c(intrinsic.detach(), dev), N.f32c(extrinsic.detach(), dev)
+    if E.shape[2] == 3:                                      # the entry point strides over 4 x 4 matrices; row 3 is never read
+        E = torch.cat([E, torch.zeros(B, 2, 1, 4, device=dev, dtype=torch.float32)], 2)
+    kp, Kv, Ev = [pts[:, v].contiguous() for v in range(2)], [K[:, v].contiguous() for v in range(2)], [E[:, v].contiguous() for v in range(2)]
+    out = torch.empty(B, J, 4, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        G.check(G.lib().apg_xview_triangulate(B, J, G.vp(kp[0]), G.vp(kp[1]), G.vp(Kv[0]), G.vp(Kv[1]), G.vp(Ev[0]), G.vp(Ev[1]),
+                                              math.sin(math.radians(float(min_ray_angle_deg))) ** 2, G.vp(out), G.stream(dev)),
+                "apg_xview_triangulate")
+    return out[..., :3], out[..., 3] > 0

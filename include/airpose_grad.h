@@ -579,6 +579,95 @@ int apg_align_update(int B, int views, int N, int64_t pred_stride, int64_t gt_st
                      int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Cross-view metrics (xview_metrics.hip): how well the two views of a calibrated camera pair agree on one body -- what the
+ * reference's result scripts print for real footage, which has no 3-D ground truth (copenet_real_res_compile.py:132-143,
+ * final_res_compile.py:149-152: each view's prediction carried into the world frame by the inverse extrinsics, the distance between
+ * the two; utils/geometry.py:160-192 lstsq_triangulation; the confidence-weighted reprojection term of copenet_twoview.py:112-123).
+ * Additive under ABI 2: a binding tells a library that has it by looking up apg_xview_update.
+ *
+ * Per sample b, with E_v = extr_v[b] = [R_v | t_v] (world -> camera; rows 0 .. 2 of a row-major 3 x 4 or 4 x 4 matrix, row 3 is never
+ * read) and W_v(p) = R_v^T (p - t_v), the transpose taken as the inverse:
+ *   skip rule: the sample is skipped and counted under `skipped` if an entry of rows 0 .. 2 of either extr is not finite, or if
+ *     max |R_v^T R_v - I| > 1e-3 for either view.  The gate is a design constant, not a measurement: an fp32 rotation out of
+ *     angle_axis_to_rotation_matrix is orthonormal to about 1e-6, a matrix that misses by 1e-3 is not a rotation and its transpose is
+ *     not its inverse.  A skipped sample adds to no other slot, its per-sample row is 1 followed by zeros, its tri rows are zeros.
+ *   joint_gap_world  = mean over the first n_joints joints of |W_0(p0_i) - W_1(p1_i)|;  vertex_gap_world the same over the N vertices
+ *   joint_gap_root   = the same after subtracting each view's root: |R_0^T (p0_i - r0) - R_1^T (p1_i - r1)|; vertex_gap_root likewise
+ *     with the same roots.  The root is a pointer and a stride: the predicted translation, joint 0, or anything else.
+ *   trans_gap        = |W_0(s0) - W_1(s1)| of the two translations
+ *   orient_gap_deg   = the angle between R_0^T Q0_0 and R_1^T Q1_0 (the root's rotation carried into the world)
+ *   pose_gap_deg     = the mean over the body joints j = 1 .. 21 of the angle between Q0_j and Q1_j
+ *     angle formula: the angle of A and B is that of D = A^T B, atan2(|(D21 - D12, D02 - D20, D10 - D01)|, tr D - 1), in degrees,
+ *     in fp64 -- not acos of the trace, which loses half the digits near 0 and near 180 degrees.  The rotations are (22, 3, 3)
+ *     matrices (APG_XVIEW_ROTMAT) or (22, 3) angle-axis vectors (APG_XVIEW_ANGLE_AXIS) taken through tgm 0.1.2's
+ *     angle_axis_to_rotation_matrix in fp32, the formula given under the evaluation metrics above.
+ *   reproj_px_v      = sum_i c_i |j2d_v,i - k_v,i| / sum_i c_i over the first 22 joints, k = (x, y) and c the confidence of keypoint
+ *     row i = (x, y, c); a keypoint counts where x, y, c are finite and c > 0; reproj_n_v is their number.  A sample whose
+ *     sum of c is 0 adds to neither the sum nor its count.
+ *   triangulation (lstsq_triangulation for two cameras, unweighted, per joint i < 22, in fp64):
+ *     n_v = ((x - cx_v) / fx_v, (y - cy_v) / fy_v) with fx = K[0][0], cx = K[0][2], fy = K[1][1], cy = K[1][2] of intr_v[b]; no
+ *     other entry is read (the reference's K^-1 agrees where the skew is 0).  Rows n_v[r] E_v[2, :3] - E_v[r, :3], right side
+ *     E_v[r, 3] - E_v[2, 3] n_v[r], r = 0, 1: a 4 x 3 system A T = y solved through its normal equations (A^T A) T = A^T y by
+ *     cofactors.
+ *     validity rule: T_i is valid iff both confidences are > 0, x, y, c of both keypoints and both n_v are finite, the rays
+ *     d_v = R_v^T (n_v, 1) have |d_0 x d_1|^2 / (|d_0|^2 |d_1|^2) >= min_sin2, and T_i is finite.
+ *     tri_mpjpe_v = mean over the valid joints of |W_v(p_v,i) - T_i|; tri_n is their number.
+ * Every point is carried in fp64, a difference is rounded to float once per component and its norm taken in fp32
+ * (sqrtf(fmaf(d2, d2, fmaf(d1, d1, d0 * d0)))); sums are fp64.  Two views that hold the same bits under identity extrinsics give
+ * every gap exactly 0.
+ *
+ * apg_xview_update, one call per batch:
+ *   views: 2.  n_joints: the joints compared (at least 1).  N: the vertices per sample, 0 = none.
+ *   flags: APG_XVIEW_ANGLE_AXIS or APG_XVIEW_ROTMAT, what `rot` holds.
+ *   per_view: HOST array of 2 * APG_XVIEW_PER_VIEW device pointers; per view joints (n_joints x 3; 22 x 3 at least with intr), extr,
+ *     vertices (N x 3), root (3), trans (3), rot, j2d (22 x 2), keypoints (22 x 3), intr (3 x 3).  All but joints and extr may be
+ *     NULL, for both views or neither; vertices exactly when N > 0; j2d needs keypoints, intr needs keypoints, keypoints need one of
+ *     the two.  strides: HOST array of APG_XVIEW_PER_VIEW int64: floats from one sample to the next of each entry (the same in both
+ *     views), at least the entry's size (extr: 12); read only where the entry is given.
+ *   min_sin2: sin^2 of the smallest ray angle a triangulation is accepted at, in 0 .. 1.
+ *   per_sample (B, APG_XVIEW_PER_SAMPLE): optional, written in full: [0] skipped (1 / 0), [1] joint_gap_world, [2] joint_gap_root,
+ *     [3] vertex_gap_world, [4] vertex_gap_root, [5] trans_gap, [6] orient_gap_deg, [7] pose_gap_deg, [8] [9] reproj_px of view 0 / 1,
+ *     [10] [11] reproj_n, [12] [13] tri_mpjpe of view 0 / 1 over the sample's valid joints, [14] tri_n, [15] 0; 0 where not fed.
+ *   tri (B, 22, 4): optional (needs intr), written in full: x, y, z, valid (1 / 0) in the world frame; zeros where not valid.
+ *   acc: apg_xview_acc_doubles() = APG_XVIEW_ACC doubles (device, 8-byte aligned), ADDED to; the caller zeroes it to start or reset:
+ *     [0] samples seen (skipped ones included), [1] skipped, [2] sum of joint_gap_world, [3] sum of joint_gap_root, [4] samples that
+ *     had roots, [5] sum of vertex_gap_world, [6] sum of vertex_gap_root, [7] samples that had vertices, [8] samples that had
+ *     vertices and roots, [9] sum of trans_gap, [10] samples that had translations, [11] sum of orient_gap_deg, [12] sum of
+ *     pose_gap_deg, [13] samples that had rotations, [14] [15] sum of reproj_px of view 0 / 1, [16] [17] samples whose sum of c was
+ *     > 0 in view 0 / 1, [18] [19] sum of reproj_n, [20] samples that had j2d, [21] [22] sum over the valid joints of
+ *     |W_v(p_v,i) - T_i| of view 0 / 1, [23] tri_n, [24] samples that had intr, [25] reserved, untouched.  All counts but [0] and
+ *     [1] leave skipped samples out.  The means: [2] / ([0] - [1]), [3] / [4], [5] / [7], [6] / [8], [9] / [10], [11] / [13],
+ *     [12] / [13], [14] / [16], [15] / [17], [21] / [23], [22] / [23].
+ *   workspace: at least apg_xview_workspace_bytes(B, 2, N) bytes (negative outside the limits below), 8-byte aligned, else
+ *     APG_ENOMEM; the workgroups' partial sums.  It carries nothing from call to call and needs no initialisation.
+ * All other data is fp32, 4-byte aligned; every access is a 4-byte one, so alignment changes no bit.
+ * Limits: 1 <= B <= 2^22, 1 <= n_joints <= 2^16, 0 <= N <= 2^24, B * ceil(N / 1024) < 2^31.
+ * Determinism: no atomics and no arrival counter; a workgroup owns one (sample, chunk of 1024 vertices) and sums in a fixed order in
+ * fp64 (thread, wave, workgroup); a second launch adds a sample's chunks in chunk order and the samples in a fixed order in fp64 and
+ * adds each total to acc.  The partition depends on (B, N) alone, so every output is bit-identical from run to run.  Two launches,
+ * no host synchronisation.
+ * APG_EINVAL before any GPU call, the message naming the argument: B, n_joints or N outside the limits, views other than 2, flags
+ * neither of the two, min_sin2 outside 0 .. 1, a NULL strides, per_view, joints, extr, acc or workspace, an optional entry given for
+ * one view only, vertices without N or N without vertices, j2d or intr without keypoints, keypoints alone, tri without intr, a stride
+ * below its entry's size, a pointer that is not 4-byte (acc, workspace: 8-byte) aligned.
+ *
+ * apg_xview_triangulate: the solve alone, on the same device function.  kp0, kp1 (B, J, 3) = x, y, c; intr0, intr1 (B, 3, 3);
+ * extr0, extr1 (B, 4, 4) (rows 0 .. 2 are read); out (B, J, 4) = x, y, z, valid, zeros where not valid -- which includes every joint
+ * of a sample the skip rule rejects.  1 <= B <= 2^22, 1 <= J <= 2^16.  One launch. */
+#define APG_XVIEW_ANGLE_AXIS 0
+#define APG_XVIEW_ROTMAT 1
+#define APG_XVIEW_PER_VIEW 9
+#define APG_XVIEW_ACC 26
+#define APG_XVIEW_PER_SAMPLE 16
+int64_t apg_xview_workspace_bytes(int B, int views, int N);
+int64_t apg_xview_acc_doubles(void);
+int apg_xview_update(int B, int views, int n_joints, int N, int flags, const int64_t* strides, const void* const* per_view,
+                     double min_sin2, float* per_sample, float* tri, double* acc, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+int apg_xview_triangulate(int B, int J, const float* kp0, const float* kp1, const float* intr0, const float* intr1,
+                          const float* extr0, const float* extr1, double min_sin2, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * AirPose+ on a whole sequence (seq_fit.hip): the per-frame work on either side of the fitting loop (ap_fit_run of
  * libairpose_hip.so) -- the loop's initial state and filtered detections from the network's outputs (bundle_adj.py:176-200,
  * copenet_real.py:105-106) and the fitted bodies under the names the rest of the package reads (bundle_adj.py:404-412, 510-516).
