@@ -64,6 +64,9 @@ SIGNATURES = {
     "ap_muhmr_fwd": (_i, [_vp, _vp, _vp] + [_vp, _i] * 6 + [_i, _i] + [_vp] * 4 + [_vp]),
     "ap_hmr_fwd": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "ap_conv2d_nhwc": (_i, [_i] + [_vp] * 6 + [_i] * 9 + [_vp]),
+    "ap_conv2d_tiled_nhwc": (_i, [_i] + [_vp] * 6 + [_i] * 9 + [_vp]),
+    "ap_conv2d_fold_nhwc": (_i, [_i] + [_vp] * 7 + [_i] * 8 + [_vp]),
+    "ap_conv2d_pool_nhwc": (_i, [_i] + [_vp] * 6 + [_i] * 3 + [_vp]),
     "ap_set_conv_config": (_i, [_i]),
     "ap_abi_version": (_i, []),
     "ap_debug_set_trace": (_i, [_vp]),
@@ -87,6 +90,7 @@ SIGNATURES = {
     "ap_conv_pair_pack": (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "ap_conv_pair_nhwc": (_i, [_i] + [_vp] * 9 + [_i] * 3 + [_vp]),
     "ap_conv_pair_ds_nhwc": (_i, [_i] + [_vp] * 9 + [_i] * 6 + [_vp]),
+    "ap_conv_pair_layout_nhwc": (_i, [_i] + [_vp] * 9 + [_i] * 10 + [_vp]),
     "ap_bottleneck64_nhwc": (_i, [_i] + [_vp] * 11 + [_i] * 5 + [_vp]),
     "ap_bottleneck64_tail_nhwc": (_i, [_i] + [_vp] * 15 + [_i] * 4 + [_vp]),
     "ap_block_img_stream_bytes": (_c.c_int64, []),
@@ -138,7 +142,7 @@ SIGNATURES = {
     "ap_perspective_projection": (_i, [_vp, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp]),
 }
 
-ABI_VERSION = 12        # include/airpose_hip.h: AP_ABI_VERSION
+ABI_VERSION = 13        # include/airpose_hip.h: AP_ABI_VERSION
 _lib = None
 _lib_lock = threading.Lock()
 

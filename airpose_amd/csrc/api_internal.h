@@ -187,6 +187,7 @@ hipError_t zero_line(const void** out);
 hipError_t device_cus(int* n);
 int conv_mode();                         // the raw value of ap_set_conv_config, read once: a caller decodes ONE value per launch / per pass
 hipError_t dispatch_conv(ConvArgs& a, int prec /* AP_PREC_* */, hipStream_t st, int mode);
+const char* conv_refusal(const ConvArgs& a, int prec, int mode);   // why dispatch_conv would not run these arguments (NULL: it runs); no launch
 inline hipError_t dispatch_conv(ConvArgs& a, int prec, hipStream_t st) { return dispatch_conv(a, prec, st, conv_mode()); }
 int trunk_fwd(ap_net* h, const float* x0, int n0, const float* x1, int n1, float* feat, hipStream_t st, hipStream_t st_out = nullptr);
 // api_net.hip
@@ -201,6 +202,9 @@ int finalize_trunk(ap_net* h);
 // (*pooled = true, y not written); otherwise the plain convolution into y
 hipError_t launch_conv(const ConvDesc& c, const void* x, int N, int H, int W, const void* res, void* y, int relu, int y_tiled,
                        const void* x2, int H2, float* pool_out, bool* pooled, int prec, int mode, int* rflag, hipStream_t st);
+bool conv_pool_fits(const ConvDesc& c, int N, int prec);     // launch_conv would pool N 7 x 7 images (with an identity and ReLU)
+// conv_refusal on the arguments launch_conv would build for a plain / tiled / folded convolution
+const char* conv_form_refusal(const ConvDesc& c, int N, int H, int W, int y_tiled, bool fold, int H2, int prec, int mode);
 // conv_pw.hip (c.w: its fragment stream): pointwise (+ identity), pointwise + folded downsample, 3 x 3 / stride 2; *_fits: the
 // kernel's own predicate on the arguments that launch would build
 hipError_t launch_conv_pw(const ConvDesc& c, const void* x, const void* res, void* y, int M, int prec, int* rflag, hipStream_t st);

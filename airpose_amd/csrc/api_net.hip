@@ -493,7 +493,7 @@ int ap_internal::finalize_trunk(ap_net* h) {
 
 extern "C" {
 
-const char* ap_version(void) { return "airpose_hip 0.7 (gfx950; abi 12)"; }
+const char* ap_version(void) { return "airpose_hip 0.7 (gfx950; abi 13)"; }
 int ap_abi_version(void) { return AP_ABI_VERSION; }
 const char* ap_last_error(void) { return g_err.c_str(); }
 

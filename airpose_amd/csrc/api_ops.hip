@@ -1,11 +1,15 @@
 // The launch functions of the trunk kernels (ap_internal::launch_*, declared in api_internal.h): each fills ONE kernel's argument
 // struct and calls its launcher, for the trunk pass (api_trunk.hip) and for the stand-alone operator entry alike.  Below them
 // the operator entry points: every kernel a trunk pass can launch on caller-owned tensors -- validate the arguments, then the
-// shared launch (the element-wise tests go through these) -- and the geometry operators.
+// shared launch (the element-wise tests go through these; the forms a pass selects with y_tiled, x2, pool_out and PairLayout have
+// entries of their own: ap_conv2d_tiled_nhwc, _fold_nhwc, _pool_nhwc, ap_conv_pair_layout_nhwc) -- and the geometry operators.
 #include "api_internal.h"
 
-hipError_t ap_internal::launch_conv(const ConvDesc& c, const void* x, int N, int H, int W, const void* res, void* y, int relu, int y_tiled,
-                                    const void* x2, int H2, float* pool_out, bool* pooled, int prec, int mode, int* rflag, hipStream_t st) {
+namespace {
+const char g_any = 0;   // the shape predicates only ask that an operand exists
+// the generic kernels' argument struct from plain shapes and pointers (x2: second K segment of c.cin2 channels, or NULL)
+ConvArgs conv_args(const ConvDesc& c, const void* x, int N, int H, int W, const void* res, void* y, int relu, int y_tiled, const void* x2,
+                   int H2, int* rflag) {
     ConvArgs a{};
     a.x = x; a.w = c.w; a.scale = c.scale; a.shift = c.shift; a.res = res; a.y = y;
     a.N = N; a.H = H; a.W = W; a.Cin = c.cin; a.Cout = c.cout;
@@ -16,6 +20,13 @@ hipError_t ap_internal::launch_conv(const ConvDesc& c, const void* x, int N, int
     a.ldx = c.cin; a.ldy = c.cout; a.ldr = c.cout; a.wld = c.wld;
     a.relu = relu; a.y_tiled = y_tiled; a.range_flag = rflag;
     if (x2) { a.x2 = x2; a.H2 = a.W2 = H2; a.Cin2 = a.ldx2 = c.cin2; a.stride2 = c.stride2; }
+    return a;
+}
+}  // namespace
+
+hipError_t ap_internal::launch_conv(const ConvDesc& c, const void* x, int N, int H, int W, const void* res, void* y, int relu, int y_tiled,
+                                    const void* x2, int H2, float* pool_out, bool* pooled, int prec, int mode, int* rflag, hipStream_t st) {
+    ConvArgs a = conv_args(c, x, N, H, W, res, y, relu, y_tiled, x2, H2, rflag);
     if (pool_out && k_bf16::ap_conv_lean_supported(a, prec_kind(prec))) {
         a.y = nullptr; a.pool_out = pool_out; a.dbg = g_conv_dbg;
         hipError_t e = zero_line(&a.zero);
@@ -24,6 +35,13 @@ hipError_t ap_internal::launch_conv(const ConvDesc& c, const void* x, int N, int
         return H16(prec, ap_launch_conv_lean)(a, st);
     }
     return dispatch_conv(a, prec, st, mode);
+}
+// launch_conv's own condition for the pooling branch, on the arguments it would build (7 x 7 images, identity, ReLU)
+bool ap_internal::conv_pool_fits(const ConvDesc& c, int N, int prec) {
+    return k_bf16::ap_conv_lean_supported(conv_args(c, &g_any, N, 7, 7, &g_any, nullptr, 1, 0, nullptr, 0, nullptr), prec_kind(prec));
+}
+const char* ap_internal::conv_form_refusal(const ConvDesc& c, int N, int H, int W, int y_tiled, bool fold, int H2, int prec, int mode) {
+    return conv_refusal(conv_args(c, &g_any, N, H, W, nullptr, nullptr, 1, y_tiled, fold ? &g_any : nullptr, H2, nullptr), prec, mode);
 }
 
 namespace {
@@ -44,7 +62,6 @@ PwArgs pw_k3_args(const ConvDesc& c, const void* x, void* y, int N, int H, int* 
     p.k3 = 1; p.Ho = p.Wo = H / 2; p.H2 = p.W2 = H; p.stride2 = 2;
     return p;
 }
-const char g_any = 0;   // the shape predicates only ask that an operand exists
 }  // namespace
 
 hipError_t ap_internal::launch_conv_pw(const ConvDesc& c, const void* x, const void* res, void* y, int M, int prec, int* rflag, hipStream_t st) {
@@ -153,6 +170,54 @@ int ap_conv2d_nhwc(int precision, const void* x, const void* w, const float* sca
     if ((H + 2 * pad - ksize) / stride + 1 <= 0 || (W + 2 * pad - ksize) / stride + 1 <= 0) return fail(AP_ESHAPE, "ap_conv2d_nhwc: empty output");
     const ConvDesc c{w, scale, shift, Cin, Cout, ksize, stride, pad, ksize * ksize * Cin, 0, 1};
     HIP_TRY(launch_conv(c, x, N, H, W, res, y, relu, 0, nullptr, 0, nullptr, nullptr, precision, conv_mode(), ops_range_word(precision),
+                        (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_conv2d_tiled_nhwc(int precision, const void* x, const void* w, const float* scale, const float* shift,
+                         const void* res, void* y, int N, int H, int W, int Cin, int Cout, int ksize, int stride, int pad,
+                         int relu, void* stream) {
+    const int bf = prec_half(precision);
+    if (!prec_valid(precision) || !x || !w || !scale || !shift || !y || N <= 0 || H <= 0 || W <= 0 || ksize <= 0 || stride <= 0 || pad < 0)
+        return fail(AP_EINVAL, "ap_conv2d_tiled_nhwc: bad argument");
+    if (Cin % (bf ? 64 : 32) || Cout % (precision == AP_PREC_FP32 ? 4 : 8) || Cin <= 0 || Cout <= 0)
+        return fail(AP_ESHAPE, "ap_conv2d_tiled_nhwc: Cin must be a multiple of 64 (bf16) / 32 (fp32), Cout of 8 / 4");
+    if ((H + 2 * pad - ksize) / stride + 1 <= 0 || (W + 2 * pad - ksize) / stride + 1 <= 0)
+        return fail(AP_ESHAPE, "ap_conv2d_tiled_nhwc: empty output");
+    const ConvDesc c{w, scale, shift, Cin, Cout, ksize, stride, pad, ksize * ksize * Cin, 0, 1};
+    const int mode = conv_mode();                            // ONE value for the check and for the launch
+    if (const char* why = conv_form_refusal(c, N, H, W, 1, false, 0, precision, mode)) return fail(AP_ESHAPE, std::string("ap_conv2d_tiled_nhwc: ") + why);
+    HIP_TRY(launch_conv(c, x, N, H, W, res, y, relu, 1, nullptr, 0, nullptr, nullptr, precision, mode, ops_range_word(precision),
+                        (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_conv2d_fold_nhwc(int precision, const void* t, const void* x2, const void* w, const float* scale, const float* shift,
+                        const void* res, void* y, int N, int Ho, int H2, int Cin, int Cin2, int Cout, int stride2, int relu,
+                        void* stream) {
+    const int bf = prec_half(precision);
+    if (!prec_valid(precision) || !t || !x2 || !w || !scale || !shift || !y || N <= 0 || Ho <= 0 || H2 <= 0 || stride2 < 1 || stride2 > 2)
+        return fail(AP_EINVAL, "ap_conv2d_fold_nhwc: bad argument (stride2 1 or 2)");
+    if (Cin % (bf ? 64 : 32) || Cin2 % (bf ? 64 : 32) || Cout % (precision == AP_PREC_FP32 ? 4 : 8) || Cin <= 0 || Cin2 <= 0 || Cout <= 0)
+        return fail(AP_ESHAPE, "ap_conv2d_fold_nhwc: Cin and Cin2 must be multiples of 64 (bf16) / 32 (fp32), Cout of 8 / 4");
+    if (Ho != (H2 - 1) / stride2 + 1) return fail(AP_ESHAPE, "ap_conv2d_fold_nhwc: Ho must be (H2 - 1) / stride2 + 1");
+    const ConvDesc c{w, scale, shift, Cin, Cout, 1, 1, 0, Cin + Cin2, Cin2, stride2};
+    const int mode = conv_mode();                            // ONE value for the check and for the launch
+    if (const char* why = conv_form_refusal(c, N, Ho, Ho, 0, true, H2, precision, mode)) return fail(AP_ESHAPE, std::string("ap_conv2d_fold_nhwc: ") + why);
+    HIP_TRY(launch_conv(c, t, N, Ho, Ho, res, y, relu, 0, x2, H2, nullptr, nullptr, precision, mode, ops_range_word(precision),
+                        (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_conv2d_pool_nhwc(int precision, const void* x, const void* w, const float* scale, const float* shift, const void* res,
+                        float* pool_out, int N, int Cin, int Cout, void* stream) {
+    if (!prec_valid(precision) || !x || !w || !scale || !shift || !res || !pool_out || N <= 0)
+        return fail(AP_EINVAL, "ap_conv2d_pool_nhwc: bad argument (the identity is part of the operator)");
+    const ConvDesc c{w, scale, shift, Cin, Cout, 1, 1, 0, Cin, 0, 1};
+    if (Cin <= 0 || Cout <= 0 || Cin % 64 || Cout % 8 || !conv_pool_fits(c, N, precision))
+        return fail(AP_ESHAPE, "ap_conv2d_pool_nhwc: 16-bit precision, Cin a multiple of 64, Cout of 8, tensors below 4 GiB");
+    bool pooled = false;                                     // (true after the call: conv_pool_fits IS launch_conv's condition for the pooling branch)
+    HIP_TRY(launch_conv(c, x, N, 7, 7, res, nullptr, 1, 0, nullptr, 0, pool_out, &pooled, precision, conv_mode(), ops_range_word(precision),
                         (hipStream_t)stream));
     return AP_OK;
 }
@@ -365,6 +430,21 @@ int ap_conv_pair_ds_nhwc(int precision, const void* t2, const void* x, const voi
         return fail(AP_ESHAPE, "ap_conv_pair_ds_nhwc: (P, P2, N1) must be (128,256,128) or (256,512,0); stride 1 or 2");
     HIP_TRY(launch_conv_pair(t2, wstream, s3, h3, s1, h1, x, out, t1n, N * Ho * Ho, Ho, Ho * stride, stride, P, P2, N1, PairLayout{}, precision,
                              ops_range_word(precision), (hipStream_t)stream));
+    return AP_OK;
+}
+
+int ap_conv_pair_layout_nhwc(int precision, const void* t2, const void* in, const void* wstream, const float* s3, const float* h3,
+                             const float* s1, const float* h1, void* out, void* t1n, int N, int Ho, int P, int P2, int stride, int N1,
+                             int t2_tiled, int res_tiled, int out_tiled, int out_even, void* stream) {
+    if (!prec_half(precision) || !t2 || !in || !wstream || !s3 || !h3 || !out || N <= 0 || Ho <= 0 || (N1 > 0 && (!s1 || !h1 || !t1n)))
+        return fail(AP_EINVAL, "ap_conv_pair_layout_nhwc: bad argument (precision: AP_PREC_BF16 or AP_PREC_F16)");
+    if (!k_bf16::ap_conv_pair_supported(P, P2, 4 * P, N1) || (P2 > 0 && (stride < 1 || stride > 2)))
+        return fail(AP_ESHAPE, "ap_conv_pair_layout_nhwc: (P, P2, N1) must be (128,0,128), (128,0,256), (256,0,256), (128,256,128) or (256,512,0); stride 1 or 2");
+    if ((res_tiled && P2 > 0) || (out_even && out_tiled) || (out_even && N1 == 0))
+        return fail(AP_ESHAPE, "ap_conv_pair_layout_nhwc: res_tiled needs an identity block, out_even an untiled out and a next conv1");
+    HIP_TRY(launch_conv_pair(t2, wstream, s3, h3, s1, h1, in, out, t1n, N * Ho * Ho, Ho, P2 > 0 ? Ho * stride : 0, P2 > 0 ? stride : 0, P, P2, N1,
+                             PairLayout{t2_tiled != 0, res_tiled != 0, out_tiled != 0, out_even != 0}, precision, ops_range_word(precision),
+                             (hipStream_t)stream));
     return AP_OK;
 }
 

@@ -52,9 +52,9 @@ hipError_t ap_internal::device_cus(int* n) {
     return hipSuccess;
 }
 
+namespace {
 // choose the tile configuration: large tiles need enough tiles to fill 256 CUs (1 workgroup per CU)
-hipError_t ap_internal::dispatch_conv(ConvArgs& a, int prec /* AP_PREC_* */, hipStream_t st, int mode /* conv_mode() */) {
-    const int is_bf16 = prec_kind(prec);                     // storage kind inside the kernel set: K_F32 / K_BF16 (16-bit) / K_SPLIT
+int conv_config(const ConvArgs& a, int is_bf16 /* K_F32 / K_BF16 (16-bit) / K_SPLIT */, int mode /* conv_mode() */) {
     const bool use_slab = mode == -1 || mode == -5, use_lean = mode == -1;
     int cfg = mode < 0 ? -1 : mode;
     if (cfg < 0) {
@@ -81,8 +81,35 @@ hipError_t ap_internal::dispatch_conv(ConvArgs& a, int prec /* AP_PREC_* */, hip
         else if (mt128 * nt64 >= 128) cfg = a.x2 ? (mt128 * nt128 >= 64 ? 11 : 100) : 12;
         else cfg = 100;
     }
+    return cfg;
+}
+}  // namespace
+
+// The forms dispatch_conv cannot run under the configuration `mode` selects, found WITHOUT a launch (NULL: it runs): one rule for
+// the trunk pass and for the operator entries, which turn it into AP_ESHAPE with this text
+const char* ap_internal::conv_refusal(const ConvArgs& a, int prec, int mode) {
+    const int is_bf16 = prec_kind(prec), cfg = conv_config(a, is_bf16, mode);
     // the fragment-tiled output exists in the LDS-staged 16-bit epilogues only (trunk_chunk asks for it in the automatic modes)
-    if (a.y_tiled && (is_bf16 != 1 || cfg == 17 || (cfg >= 4 && cfg <= 7) || (a.Cout & 7))) return hipErrorInvalidValue;
+    if (a.y_tiled && (is_bf16 != 1 || cfg == 17 || (cfg >= 4 && cfg <= 7) || (a.Cout & 7)))
+        return "no fragment-tiled output in this precision / configuration (16-bit only; not 4-7, not 17, which the automatic choice takes for "
+               "1 x 1 / stride 1 with Cin <= 512, Cout >= 256 on 768 or more 128 x 128 tiles)";
+    // (the split-bf16 set ships the configurations the automatic choice uses: 11, 12, 100; 14 and 17 run 11)
+    if (is_bf16 == K_SPLIT && cfg != 11 && cfg != 12 && cfg != 14 && cfg != 17 && cfg != 100) return "split-bf16 runs configurations 11, 12 and 100 only";
+    if (a.x2 && cfg != 100) {
+        // the 64-wide tiles of conv_pipe.hip carry no second K segment (14 and 17 hand such a call to 11)
+        if (cfg == 2 || cfg == 3 || cfg == 6 || cfg == 7 || cfg == 9 || cfg == 12 || cfg == 13)
+            return "no second K segment on the 64-wide tiles (2, 3, 6, 7, 9, 12, 13; the automatic choice takes 12 for Cout <= 64 on 256 or more "
+                   "128-row tiles)";
+        // ... and the ring kernel addresses x2 with 32-bit byte offsets
+        if ((size_t)a.N * a.H2 * a.W2 * a.ldx2 * (is_bf16 == 1 ? 2 : 4) >= 0xffffffffull) return "second K segment of 4 GiB or more";
+    }
+    return nullptr;
+}
+
+hipError_t ap_internal::dispatch_conv(ConvArgs& a, int prec /* AP_PREC_* */, hipStream_t st, int mode /* conv_mode() */) {
+    const int is_bf16 = prec_kind(prec);                     // storage kind inside the kernel set: K_F32 / K_BF16 (16-bit) / K_SPLIT
+    const int cfg = conv_config(a, is_bf16, mode);
+    if (conv_refusal(a, prec, mode)) return hipErrorInvalidValue;
     if (cfg == 100) return H16(prec, ap_launch_conv)(a, is_bf16, st);
     hipError_t e = zero_line(&a.zero);
     if (e != hipSuccess) return e;

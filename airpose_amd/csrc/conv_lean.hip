@@ -211,7 +211,9 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 6)))
             u32x4 o;
             o[0] = pack_bf16x2(a.x, a.y); o[1] = pack_bf16x2(a.z, a.w);
             o[2] = pack_bf16x2(b.x, b.y); o[3] = pack_bf16x2(b.z, b.w);
-            ap_rng_note4(rng, o[0], o[1], o[2], o[3], p.relu != 0);
+            // noted under the condition the stand-alone path stores under: the unused rows of a super-tile, the images past N and the
+            // channel padding are pooled into nothing (!POOL: the `continue` above is that condition)
+            if (!POOL || (mm < p.M && ch < p.Cout && rl < POOL_ROWS)) ap_rng_note4(rng, o[0], o[1], o[2], o[3], p.relu != 0);
             if constexpr (!POOL) {
                 *(u32x4*)(yg + (size_t)mm * p.ldy + ch) = o;
             } else {

@@ -50,13 +50,15 @@ typedef struct ap_net ap_net;     /* ResNet-50 trunk + IEF regressor */
 typedef struct ap_smplx ap_smplx; /* SMPL-X body model */
 
 /* ABI number of this header: bumped whenever an exported signature changes or an entry point is added or removed
- * (12: ap_debug_set_range_hook / ap_debug_range_status -- the fp16 range sentinel of the stand-alone operator entries;
+ * (13: ap_conv2d_fold_nhwc, ap_conv2d_tiled_nhwc, ap_conv2d_pool_nhwc, ap_conv_pair_layout_nhwc -- operator entries for the forms of the
+ *  generic and pair kernels that only a trunk pass selected: second K segment, fragment-tiled output, pooling epilogue, pair layouts;
+ *  12: ap_debug_set_range_hook / ap_debug_range_status -- the fp16 range sentinel of the stand-alone operator entries;
  *  11: ap_stem_pack_bytes / ap_stem_pack / ap_stem_nhwc, ap_maxpool_nhwc, ap_avgpool_nhwc -- operator forms of the stem and pooling kernels;
  *  10: ap_smplx_bwd, ap_batch_rodrigues_bwd -- the adjoints of ap_smplx_fwd and of lbs.batch_rodrigues;
  *  8: round 6 -- ap_net_parity_probe, ap_net_range_peek / _mark_next / _slot, ap_regressor_feat_part / _step_local / _step_finish;
  *  7: ap_conv_pw_*, ap_block_img_*; 6: ap_set_pair_groups removed).  A binding built against another number must refuse to load
  * the library (airpose_amd/_native.py does). */
-#define AP_ABI_VERSION 12
+#define AP_ABI_VERSION 13
 const char* ap_version(void);
 int ap_abi_version(void);
 const char* ap_last_error(void);
@@ -232,6 +234,42 @@ int ap_singleview_reg(ap_net* h, const float* xf, const float* bb, const float* 
 int ap_conv2d_nhwc(int precision, const void* x, const void* w, const float* scale, const float* shift,
                    const void* res, void* y, int N, int H, int W, int Cin, int Cout, int ksize, int stride, int pad,
                    int relu, void* stream);
+/* The forms of those kernels that a trunk pass selects, as entries of their own (the arguments ap_conv2d_nhwc fixes).
+ *   ap_conv2d_tiled_nhwc  ap_conv2d_nhwc with y in the fragment-tiled layout the pair kernel reads (conv2 of every pair block in a
+ *                         pass; ap_net_set_tiled): y [ceil(M / 16)][Cout / 8][16 pixels][8 channels], M = N Ho Wo -- the 8-channel
+ *                         group ch of pixel m at element ((m >> 4) (Cout / 8) + (ch >> 3)) 128 + (m & 15) 8.  The pixels M .. of the
+ *                         last group of 16 are not written.  Same bits as ap_conv2d_nhwc under the same configuration (a pure
+ *                         relayout).  AP_ESHAPE, before any launch and with y untouched: AP_PREC_FP32 and AP_PREC_BF16X2;
+ *                         configurations 4-7 and 17 of ap_set_conv_config (their epilogues have no tiled form) -- and 17 is also what
+ *                         the AUTOMATIC choice (-1) takes for a 1 x 1 / stride 1 convolution with Cin <= 512, Cout >= 256 and
+ *                         ceil(M / 128) ceil(Cout / 128) >= 768 (e.g. 16 images of 56 x 56, 64 -> 256): such a call is refused
+ *                         under -1 and runs under -5, -4 or an explicit configuration.
+ *   ap_conv2d_fold_nhwc   a stage-first block's conv3 with the downsample branch folded in as a second K segment (ap_net_set_fuse_ds)
+ *                         on the generic kernels: y [N][Ho][Ho][Cout] = act(scale * ([t | x2 sampled at (ho stride2, wo stride2)] . w^T)
+ *                         + shift (+ res)); t [N][Ho][Ho][Cin], x2 [N][H2][H2][Cin2], w [Cout_pad][Cin + Cin2] K-contiguous rows,
+ *                         Cout_pad / scale / shift / res / element types as for ap_conv2d_nhwc; Cin2 a multiple of 64 (32) like Cin.
+ *                         AP_EINVAL: stride2 other than 1 or 2.  AP_ESHAPE, before any launch and with y untouched:
+ *                         Ho != (H2 - 1) / stride2 + 1; the configurations with 64-wide tiles (2, 3, 6, 7, 9, 12, 13), which carry no
+ *                         second K segment -- 12 is also what the AUTOMATIC choices (-1, -4, -5) take for Cout <= 64 with
+ *                         ceil(M / 128) >= 256, so such a call is refused there and runs under 11 or 100; an x2 of 4 GiB or more
+ *                         under any configuration but 100 (32-bit byte offsets); AP_PREC_BF16X2 under an explicit configuration
+ *                         other than 11, 14, 17, 100 (that kernel set ships 11, 12 and 100).  14 and 17 run configuration 11.
+ *                         Every accepted configuration gives the same bits.  (conv_pw.hip's ap_conv_pw_ds_nhwc computes the same function; bit-equality with it is not
+ *                         promised.)
+ *   ap_conv2d_pool_nhwc   the last convolution of the trunk with AvgPool2d(7) + view in its epilogue (conv_lean.hip, pooling variant;
+ *                         ap_net_set_fuse_pool): x [N][7][7][Cin], w [Cout_pad][Cin], res [N][7][7][Cout] (required), 16-bit;
+ *                         pool_out [N][Cout] fp32 = mean over the 49 pixels of relu(scale * conv(x) + shift + res) rounded to the
+ *                         storage type.  No y is written.  Where Cout is a multiple of 256, bit-identical to ap_conv2d_nhwc (relu = 1)
+ *                         followed by ap_avgpool_nhwc.  AP_ESHAPE, before any launch: whatever the pooling kernel does not take --
+ *                         AP_PREC_FP32 / AP_PREC_BF16X2, Cin not a multiple of 64, Cout not a multiple of 8, x or w of 4 GiB or more. */
+int ap_conv2d_tiled_nhwc(int precision, const void* x, const void* w, const float* scale, const float* shift,
+                         const void* res, void* y, int N, int H, int W, int Cin, int Cout, int ksize, int stride, int pad,
+                         int relu, void* stream);
+int ap_conv2d_fold_nhwc(int precision, const void* t, const void* x2, const void* w, const float* scale, const float* shift,
+                        const void* res, void* y, int N, int Ho, int H2, int Cin, int Cin2, int Cout, int stride2, int relu,
+                        void* stream);
+int ap_conv2d_pool_nhwc(int precision, const void* x, const void* w, const float* scale, const float* shift, const void* res,
+                        float* pool_out, int N, int Cin, int Cout, void* stream);
 
 /* Fused 64-plane bottleneck (layer1 of the trunk; precision = AP_PREC_BF16 or AP_PREC_F16: the storage type of x, y and the
  * weights): Bottleneck.forward, model_copenet.py:27-47, as ONE kernel with both intermediates resident in LDS.
@@ -360,6 +398,18 @@ int ap_conv_pair_nhwc(int precision, const void* t2, const void* wstream, const 
 int ap_conv_pair_ds_nhwc(int precision, const void* t2, const void* x, const void* wstream, const float* s3, const float* h3,
                          const float* s1, const float* h1, void* out, void* t1n, int N, int Ho, int P, int P2, int stride, int N1,
                          void* stream);
+/* Both forms (P2 = 0: `in` is the residual [N Ho Ho][4P]; P2 > 0: `in` is the block input [N][Ho stride][Ho stride][P2], stride 1 or
+ * 2) with the tensor layouts a trunk pass chooses (ap_net_set_tiled, ap_net_set_even_out); M = N Ho Ho.  A nonzero flag means:
+ *   t2_tiled   t2 is read in the fragment-tiled layout [ceil(M / 16)][P / 8][16][8] (see ap_conv2d_tiled_nhwc)
+ *   res_tiled  the residual likewise, [ceil(M / 16)][4P / 8][16][8]
+ *   out_tiled  out is written in that layout (the pixels M .. of the last group of 16 are not written)
+ *   out_even   out (NHWC) is stored at the pixels with even ho and even wo only; every other pixel is left untouched
+ * t1n is always [M][N1] NHWC rows, complete.  The layouts are a pure relayout: out (where stored) and t1n carry the bits of
+ * ap_conv_pair_nhwc / ap_conv_pair_ds_nhwc on the same values.  AP_ESHAPE for the combinations no pass produces and the kernel
+ * does not define: res_tiled with P2 > 0, out_even with out_tiled, out_even with N1 = 0. */
+int ap_conv_pair_layout_nhwc(int precision, const void* t2, const void* in, const void* wstream, const float* s3, const float* h3,
+                             const float* s1, const float* h1, void* out, void* t1n, int N, int Ho, int P, int P2, int stride, int N1,
+                             int t2_tiled, int res_tiled, int out_tiled, int out_even, void* stream);
 
 /* Tuning/testing knob (process-wide, one atomic word: safe to set while handles run on other threads; a launch sees the
  * old or the new value): tile configuration of the convolution kernels.  -1 = automatic, 0..13 = software-pipelined
@@ -377,7 +427,7 @@ int ap_set_conv_config(int cfg);
 int ap_debug_set_trace(void* device_buf_160_u64);
 /* Test aid: the fp16 range sentinel (see ap_net_set_range_check) of the stand-alone operator entries.  The library owns ONE
  * host-mapped word for the process.  on != 0 clears it and connects it: from then on every operator entry that launches a kernel
- * with a sentinel -- ap_conv2d_nhwc, ap_bottleneck64_nhwc / _tail_nhwc, ap_conv_pw_nhwc / _ds_nhwc / _k3s2_nhwc, ap_block_img_nhwc,
+ * with a sentinel -- ap_conv2d_nhwc / _tiled_nhwc / _fold_nhwc / _pool_nhwc, ap_conv_pair_layout_nhwc, ap_bottleneck64_nhwc / _tail_nhwc, ap_conv_pw_nhwc / _ds_nhwc / _k3s2_nhwc, ap_block_img_nhwc,
  * ap_conv_img3_nhwc, ap_conv_s2p_nhwc, ap_conv_pair_nhwc / _ds_nhwc, ap_stem_nhwc (forms 1 and 2), ap_maxpool_nhwc, ap_avgpool_nhwc --
  * hands that word to its kernel when called with AP_PREC_F16, exactly as a trunk pass hands over its handle's; the kernel sets it
  * when a value it STORES is +-inf or NaN (ap_avgpool_nhwc: when a pooled feature is not finite).  on = 0 (the default) disconnects

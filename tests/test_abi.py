@@ -147,6 +147,70 @@ def test_range_hook_entries_validate_on_the_host():
     assert "sentinel is not connected" not in hdr
 
 
+def test_trunk_form_entries_check_their_arguments():
+    """ABI 13: ap_conv2d_tiled_nhwc / _fold_nhwc / _pool_nhwc and ap_conv_pair_layout_nhwc refuse NULL pointers, a bad precision and
+    every shape or layout combination the header lists, before any launch (host only: no GPU needed)."""
+    from airpose_amd import _native as Nn
+    L = Nn.lib()
+    assert Nn.ABI_VERSION == 13 and L.ap_abi_version() == 13
+    one = ctypes.c_void_p(256)
+    BF, F16, F32, X2 = Nn.AP_PREC_BF16, Nn.AP_PREC_F16, Nn.AP_PREC_FP32, Nn.AP_PREC_BF16X2
+    EINVAL, ESHAPE = -1, -2
+
+    def tiled(prec=BF, x=one, w=one, s=one, h=one, y=one, N=1, H=5, W=5, Cin=64, Cout=8, k=3, st=1, pad=1):
+        return L.ap_conv2d_tiled_nhwc(prec, x, w, s, h, None, y, N, H, W, Cin, Cout, k, st, pad, 1, None)
+    for kw in (dict(prec=7), dict(prec=-1), dict(x=None), dict(w=None), dict(s=None), dict(h=None), dict(y=None), dict(N=0), dict(H=0), dict(k=0),
+               dict(st=0), dict(pad=-1)):
+        assert tiled(**kw) == EINVAL, kw
+    for kw in (dict(Cin=32), dict(Cin=0), dict(Cout=12), dict(prec=F32, Cin=48), dict(prec=F32, Cout=6), dict(H=1, k=5, pad=0)):
+        assert tiled(**kw) == ESHAPE, kw
+
+    def fold(prec=BF, t=one, x2=one, w=one, s=one, h=one, y=one, N=1, Ho=7, H2=14, Cin=64, Cin2=64, Cout=8, s2=2):
+        return L.ap_conv2d_fold_nhwc(prec, t, x2, w, s, h, None, y, N, Ho, H2, Cin, Cin2, Cout, s2, 1, None)
+    for kw in (dict(prec=4), dict(t=None), dict(x2=None), dict(w=None), dict(s=None), dict(h=None), dict(y=None), dict(N=0), dict(Ho=0), dict(H2=0),
+               dict(s2=0), dict(s2=3)):
+        assert fold(**kw) == EINVAL, kw
+    for kw in (dict(Cin=32), dict(Cin2=96), dict(Cin2=0), dict(Cout=4), dict(prec=F32, Cin2=16), dict(H2=12), dict(H2=15), dict(s2=1),
+               dict(Ho=7, H2=8, s2=1)):
+        assert fold(**kw) == ESHAPE, kw                      # (H2 = 13 and 14 are the two sizes stride 2 maps to Ho = 7; stride 1: H2 = Ho)
+
+    # what the configuration cannot run is found before any launch as well: the explicit ones, and the two the AUTOMATIC choice makes
+    big = dict(N=16, H=56, W=56, Cin=64, Cout=256, k=1, st=1, pad=0)     # 1 x 1 on 784 tiles of 128 x 128: conv_lean (17) under -1
+    fbig = dict(N=11, Ho=56, H2=56, s2=1, Cout=64)                        # Cout <= 64 on 270 rows of tiles: the 64-wide tile 12 under -1
+    try:
+        assert tiled(**big) == ESHAPE and b"fragment-tiled" in L.ap_last_error()
+        assert tiled(prec=F32) == ESHAPE and tiled(prec=X2, Cin=32) == ESHAPE
+        assert fold(**fbig) == ESHAPE and b"64-wide" in L.ap_last_error()
+        assert fold(N=512, Ho=64, H2=128, Cin2=256, Cout=136) == ESHAPE and b"4 GiB" in L.ap_last_error()
+        for cfg in (4, 5, 6, 7, 17):
+            assert L.ap_set_conv_config(cfg) == 0 and tiled() == ESHAPE, cfg
+        for cfg in (2, 3, 6, 7, 9, 12, 13):
+            assert L.ap_set_conv_config(cfg) == 0 and fold() == ESHAPE and fold(prec=F32, Cin=32, Cin2=32, Cout=4) == ESHAPE, cfg
+        for cfg in (0, 1, 5, 8, 10, 13):
+            assert L.ap_set_conv_config(cfg) == 0 and fold(prec=X2) == ESHAPE and b"split-bf16" in L.ap_last_error(), cfg
+    finally:
+        assert L.ap_set_conv_config(-1) == 0
+
+    def pool(prec=BF, x=one, w=one, s=one, h=one, res=one, out=one, N=1, Cin=64, Cout=256):
+        return L.ap_conv2d_pool_nhwc(prec, x, w, s, h, res, out, N, Cin, Cout, None)
+    for kw in (dict(prec=5), dict(x=None), dict(w=None), dict(s=None), dict(h=None), dict(res=None), dict(out=None), dict(N=0)):
+        assert pool(**kw) == EINVAL, kw
+    for kw in (dict(prec=F32), dict(prec=X2), dict(Cin=48), dict(Cin=0), dict(Cout=12), dict(Cout=0), dict(prec=F16, Cin=16), dict(Cin=32),
+               dict(Cin=96)):
+        assert pool(**kw) == ESHAPE, kw                      # never a silent y: what the pooling kernel does not take is refused
+
+    def pair(prec=BF, t2=one, inp=one, ws=one, s3=one, h3=one, s1=one, h1=one, out=one, t1n=one, N=1, Ho=7, P=128, P2=0, st=2, N1=128,
+             lay=(0, 0, 0, 0)):
+        return L.ap_conv_pair_layout_nhwc(prec, t2, inp, ws, s3, h3, s1, h1, out, t1n, N, Ho, P, P2, st, N1, lay[0], lay[1], lay[2], lay[3], None)
+    for kw in (dict(prec=F32), dict(prec=X2), dict(prec=9), dict(t2=None), dict(inp=None), dict(ws=None), dict(s3=None), dict(h3=None), dict(out=None),
+               dict(s1=None), dict(h1=None), dict(t1n=None), dict(N=0), dict(Ho=0)):
+        assert pair(**kw) == EINVAL, kw
+    for kw in (dict(P=64), dict(N1=64), dict(P2=256, N1=256), dict(P2=256, st=3), dict(P2=256, st=0), dict(P=256, P2=512, N1=128),
+               dict(P2=256, lay=(0, 1, 0, 0)), dict(lay=(0, 0, 1, 1)), dict(lay=(1, 1, 1, 1)), dict(P=256, P2=512, N1=0, lay=(0, 0, 0, 1))):
+        assert pair(**kw) == ESHAPE, kw
+    assert b"ap_conv_pair_layout_nhwc" in L.ap_last_error()
+
+
 def test_one_library_carries_both_16bit_storage_types():
     """AP_PREC_F16 is a precision of the ONE library (no second .so, no flavour switch): the enum values are distinct, the
     f16 kernel set (namespace k_f16) is linked in, and the host-only entry points validate the precision argument."""

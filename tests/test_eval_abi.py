@@ -111,7 +111,7 @@ def test_abi_numbers_stay():
     G, L = _lib()
     assert int(re.search(r"#define\s+APG_ABI_VERSION\s+(\d+)", open(HEADER).read()).group(1)) == 2
     assert G.ABI_VERSION == 2 and L.apg_abi_version() == 2
-    assert _native.ABI_VERSION == 12
+    assert _native.ABI_VERSION == 13
     assert not any(n.startswith("apg_") for n in _native.SIGNATURES)
 
 

@@ -61,5 +61,5 @@ def test_argument_checks_run_on_the_host():
 
 def test_inference_library_is_untouched_by_the_grad_entry_points():
     from airpose_amd import _native
-    assert _native.ABI_VERSION == 12                                # (12: the range hook of the operator entries; no apg_ entry ever moved it)
+    assert _native.ABI_VERSION == 13                                # (13: the trunk-form operator entries; no apg_ entry ever moved it)
     assert not any(n.startswith("apg_") for n in _native.SIGNATURES)

@@ -12,11 +12,13 @@ Kernel -> test
   conv_pipe_kernel  (conv_pipe.hip)    test_conv2d_sentinel[0 .. 13]    LDS-staged epilogues (0-3, 8-13: 16-bit stage with ReLU and no
                                                                         residual, fp32 stage otherwise) and the register epilogue (4-7)
   conv_slab_kernel  (conv_slab.hip)    test_conv2d_sentinel[14 | -1]    (-1 takes it on the 3 x 3 / 1 / 1 shapes of the silent list)
-  conv_lean_kernel  (conv_lean.hip)    test_conv2d_sentinel[17]
+  conv_lean_kernel  (conv_lean.hip)    test_conv2d_sentinel[17]; pooling variant: test_conv_pool_sentinel[1 | 4 | 6] (ap_conv2d_pool_nhwc)
+  ... fragment-tiled output, second K segment of conv_slab / conv_pipe / conv_igemm     test_conv2d_forms_sentinel[tiled | fold - -1 | 11 | 100]
   conv_igemm_kernel (conv_igemm.hip)   test_conv2d_sentinel[100 | -1]   64 x 64 tiles; test_conv_igemm_large_tiles: 128 x 64, 128 x 128
   conv_pw_kernel    (conv_pw.hip)      test_conv_pw_sentinel[plain | ds | k3s2]
   conv_img3_kernel / conv_s2p_kernel   test_img3_s2p_sentinel[img3 | s2p - NHWC | fragment-tiled]
   conv_pair_kernel  (conv_pair.hip)    test_conv_pair_sentinel[(P, N1) | ds (P, P2, N1)]   `out` and `t1n` isolated
+                                       test_conv_pair_layout_sentinel: the same under the three layout combinations of a trunk pass
   bottleneck2 kernels                  test_bottleneck64_sentinel[identity | downsample | tail | tail y_even]   y, t1n, hidden t1, hidden t2
   block_img_kernel  (block_img.hip)    test_block_img_sentinel          y, hidden t1, hidden t2
   stem_pool_kernel / stem_pool2_kernel test_stem_sentinel[1 | 2]        pooled maxima and the converted crop values
@@ -68,8 +70,18 @@ tests of test_gpu_parity.py and the fp64 files pass -- and the benchmark unchang
      of a 16-slot row; halo row and column 0 / 15 of a 16 x 16 tile, which hold PARTIAL conv2 sums; a padding half image / quarter
      of the last group; t1 of a halo pixel outside the image, noted before it was replaced by zero) went into the maximum.  Fix: a
      per-unit maximum folded in only for stored units, the lane condition applied once at the flush, t1 noted after the zeroing.
-Not reachable through an operator entry and therefore untested here: the pooling variant of conv_lean.hip (ap_net_set_fuse_pool(1),
-off by default) notes the rows of its super-tile past M the same way.
+  4. conv_lean.hip, pooling variant (ap_net_set_fuse_pool(1), off by default; reachable through ap_conv2d_pool_nhwc since ABI 13), false
+     alarm: conv_lean_kernel<true> skipped the row / channel test in front of its note and so noted the 11 unused rows of a 5-image
+     super-tile, the images past N and the channels past Cout -- finding 2 left in the one kernel no entry reached.  Fix: the note
+     stands under the condition the stand-alone path stores under (row < M, channel < Cout, row of the super-tile < 245); pooled
+     values and the stand-alone variant's stored bits are unchanged (the bitwise tests of test_trunk_forms_fp64.py and
+     test_gpu_parity.py::test_fused_pool_is_bit_identical pass).
+
+Not stored, but read by the next stage.  A value that a fused kernel does not store but hands to its next stage counts as stored:
+the hidden t1 / t2 of the bottleneck kernels, y at the odd pixels under y_even (test_bottleneck64_sentinel[tail-1]) and, by the same
+rule, `out` of the pair kernel at the odd pixels under out_even, which feeds conv1 of the next block (test_conv_pair_layout_sentinel):
+nothing stored is non-finite there and the word must still be set.  conv_pair.hip keeps the rule as it is (its note sits in the
+epilogue that packs `out`, before the store's mask).
 
 CPU self-check (no GPU): an fp32 emulation of a tiled epilogue (fma, residual, ReLU, fp16 RNE, note per 16-byte store, flush)
 reproduces the expected word on every case, and five seeded mutations of it are each rejected by the same assertions (MUTATIONS).
@@ -100,6 +112,12 @@ failed at the first launch of their sweep ("word 0, but 1 stored elements are no
 0 stored elements are non-finite" under configurations -1, 0-3, 8-14 and 17 (17 on the stride-2 shape it hands to 11), and with
 the masked-row bait in conv_img3 and conv_s2p (both layouts), all four bottleneck2 variants and block_img.  conv_pw, conv_pair,
 conv_lean, conv_igemm, the stem and the pools passed unchanged.
+The forms of ABI 13 (17 GPU tests, 10.5 s together, the slowest 1.4 s): test_conv_pool_sentinel 24 / 96 / 144 single overflows at N = 1 /
+4 / 6; test_conv2d_forms_sentinel 44-56 per form and configuration; test_conv_pair_layout_sentinel 4100 in out (513 under out_even, odd
+pixels included) and 4099-4100 in t1n per combination, with the full comparison against reference() on every 3001st launch and, for
+the identity form, the residual boundary (65504 + 16 reported, 65504 + RES_LO silent) through the host-tiled residual.  Before the fix of finding 4, with the parent commit's conv_lean.hip in the
+library, test_conv_pool_sentinel failed at its first silent case for N = 1, 4 and 6 alike:
+("conv_pool N=1", "top", "word 1, but 0 stored elements are non-finite"); every other new case passed on the first run.
 """
 
 PREC = "f16"
@@ -959,6 +977,375 @@ def test_conv_pair_sentinel(dev, P, P2, N1):
             hook.word()
             op.launch()
             assert not hook.word() and bool((op.gt.out == F16_MAX).all()) and bool(torch.isfinite(op.go.out).all()), what + " rowbait t1n"
+            op.x.zero_(); op.s1[:] = 1.0; op.h1[:] = 0.0
+            n_t1 = sweep(hook, op, sample("conv_pair_t1n_%d" % N1), what + " t1n", op.s1, full=lambda m, c: op.reference()[1], other=(op.go,))
+        print("%-34s %d single overflows in out, %d in t1n" % (what, n_out, n_t1))
+
+
+# ---- the forms a trunk pass selects (ABI 13): pooling epilogue, fragment-tiled output, second K segment, pair layouts
+class Marked(Guarded):
+    """Guarded whose payload starts as a finite marker instead of NaN, for an output that is written in part (the pixels past M of
+    a fragment-tiled tensor, the odd pixels under out_even): the non-finite counts of sweep() then see stored elements only, and
+    untouched() says whether the elements that must not be written still hold the marker"""
+    MARK = 0.5
+
+    def __init__(self, dev, prec, n):
+        super().__init__(dev, prec, n)
+        self.out.fill_(self.MARK)
+
+    def values(self, shape, what):
+        """the guards are intact and nothing is NaN; the payload flat where `shape` counts the stored elements only"""
+        v = super().values((self.n,), what)
+        n = 1
+        for d in shape:
+            n *= d
+        return v.view(*shape) if n == self.n else v
+
+    def untouched(self, keep):
+        """keep: bool mask over the payload, True where the kernel must not store"""
+        return bool((self.out[keep] == self.MARK).all())
+
+
+class PoolOp(Op):
+    """ap_conv2d_pool_nhwc: N 7 x 7 images, accumulator = x[m][0]; the `stored` elements are the 49 N x Cout values the pooling
+    epilogue rounds to fp16 and sums, the visible output their mean [N][Cout] fp32 (inf as soon as one of them is)"""
+    impulse = 1.0
+
+    def __init__(self, dev, N, Cin, Cout):
+        self.dev, self.N, self.Cin, self.C = dev, N, Cin, Cout
+        self.M = N                                           # rows of the visible output (sweep() sizes its last check with it)
+        self.x = torch.zeros(N * 49, Cin, dtype=torch.float16, device=dev)
+        self.x_flat = self.x.view(-1)
+        w = torch.zeros(Cout, 1, 1, Cin)
+        w[:, 0, 0, 0] = 1.0
+        self.w = _w_dev(w, PREC, dev)
+        self.scale = _pad_rows(torch.ones(Cout), _cpad(Cout), 1.0).to(dev)         # the channel padding computes 1e6, as in Conv2d
+        self.shift = _pad_rows(torch.zeros(Cout), _cpad(Cout), 1.0e6).to(dev)
+        self.res = torch.zeros(N * 49, Cout, dtype=torch.float16, device=dev)
+        self.g = Guarded(dev, "fp32", N * Cout)
+
+    def in_index(self, m):
+        return m * self.Cin
+
+    def out_index(self, m, c):
+        return (m // 49) * self.C + c
+
+    def launch(self):
+        Nn, L = _lib()
+        rc = L.ap_conv2d_pool_nhwc(Nn.PRECISIONS[PREC], _p(self.x), _p(self.w), _p(self.scale), _p(self.shift), _p(self.res), _p(self.g.out),
+                                   self.N, self.Cin, self.C, Nn.stream_ptr(self.dev))
+        assert rc == 0, ("ap_conv2d_pool_nhwc", self.N, self.Cin, self.C, rc)
+
+    def reference(self):
+        """(the 49 N x Cout values the stand-alone path would store: fp64 + one rounding to fp16; their mean, fp32)"""
+        C = self.C
+        v = self.x.cpu().double()[:, :1] * self.scale.cpu().double()[:C] + self.shift.cpu().double()[:C] + self.res.cpu().double()
+        st = v.clamp_min(0).to(torch.float16)
+        return st, (st.double().view(self.N, 49, C).sum(1) / 49.0).float()
+
+
+def pool_strata(N, Cout):
+    """One position per (image, sub-tile of the 128-row halves of a 5-image super-tile, channel tile): pixels 0, 29, 30, 48 of every
+    image (image 2 of a super-tile changes sub-tile between 29 and 30), channels at both ends of every 64-channel half"""
+    cs = sorted({c for c in (0, 63, 64, 127, 128, 191, 192, 255, Cout - 8, Cout - 1) if c < Cout})
+    return [(n * 49 + px, c) for n in range(N) for px in (0, 29, 30, 48) for c in cs]
+
+
+def test_pool_strata_cover_every_stratum():
+    """Host only: the positions of test_conv_pool_sentinel hit every (image of a 5-image super-tile, 128-row sub-tile, 128-channel
+    tile and 64-channel half of it), image 2 on both sides of its split, and the ragged last channel group"""
+    pos = pool_strata(6, 136)
+    rows = {(m // 49 % 5, (m % 245) // 128, c // 64) for m, c in pos}
+    assert rows == {(i, s, h) for i, s in ((0, 0), (1, 0), (2, 0), (2, 1), (3, 1), (4, 1)) for h in (0, 1, 2)}
+    assert {m // 245 for m, _ in pos} == {0, 1} and (5 * 49 + 48, 135) in pos and all(c < 136 for _, c in pos)
+    assert [m for m, _ in pos] == sorted(m for m, _ in pos)                    # sweep() moves the impulse pixel by pixel
+
+
+@gpu
+@pytest.mark.parametrize("N", [1, 4, 6])
+def test_conv_pool_sentinel(dev, N):
+    """conv_lean_kernel<POOL>: silent at the top of the range under the row bait (the rows past N 49, the 11 unused rows of a
+    super-tile: accumulator 0) and the channel-padding bait; one overflow per (image, sub-tile, channel tile) sets the word"""
+    Cin, Cout = 64, 136
+    with Hook(dev) as hook:
+        op = PoolOp(dev, N, Cin, Cout)
+        what = "conv_pool N=%d" % N
+        for kind in SILENT:
+            op.x.zero_(); op.res.zero_()
+            op.scale[:Cout] = 1.0; op.shift[:Cout] = 0.0
+            if kind == "top":
+                op.x[:, 0] = 1.0; op.scale[:Cout] = TOP
+            elif kind == "rowbait":
+                op.x[:, 0] = 1.0; op.scale[:Cout] = -16.0; op.shift[:Cout] = OVF
+            else:
+                for m in (0, N * 49 - 1):
+                    op.x[m, 0] = 1.0; op.res[m] = -16.0
+                op.scale[:Cout] = OVF
+            hook.word()
+            op.launch()
+            w = hook.word()
+            st, pooled = op.reference()
+            nbad = int((~torch.isfinite(st.float())).sum())
+            assert nbad == 0 and float(st.max()) == F16_MAX
+            got = op.g.values((N, Cout), what).cpu()
+            assert torch.equal(got, pooled), (what, kind, "pooled features differ from the mean of the reference's stored values")
+            assert bool(w) == bool(nbad), (what, kind, "word %d, but %d stored elements are non-finite" % (int(w), nbad))
+        op.x.zero_(); op.res.zero_()
+        op.scale[:Cout] = 1.0; op.shift[:Cout] = 0.0
+        n = sweep(hook, op, pool_strata(N, Cout), what, op.scale)
+    print("%-34s %d single overflows, 3 silent cases" % (what, n))
+
+
+class Conv2dTiled(Conv2d):
+    """ap_conv2d_tiled_nhwc on a ragged M: the pixels M .. ceil16(M) - 1 of the last micro-tile must keep the marker"""
+    out_layout = "tiled"
+
+    def __init__(self, dev, shp):
+        super().__init__(dev, shp)
+        self.g = Marked(dev, PREC, (self.M + 15) // 16 * 16 * self.C)
+        m, c = torch.arange(self.M, device=dev)[:, None], torch.arange(self.C, device=dev)[None, :]
+        self.idx = self.out_index(m, c)
+
+    def launch(self):
+        Nn, L = _lib()
+        name, N, H, W, Cin, Cout, k, s, p = self.shp
+        rc = L.ap_conv2d_tiled_nhwc(Nn.PRECISIONS[PREC], _p(self.x), _p(self.w), _p(self.scale), _p(self.shift),
+                                    _p(self.res) if self.use_res else None, _p(self.g.out), N, H, W, Cin, Cout, k, s, p, self.relu,
+                                    Nn.stream_ptr(self.dev))
+        assert rc == 0, (self.shp, "ap_conv2d_tiled_nhwc status %d" % rc)
+
+    def stored(self, what):
+        self.g.values((self.g.n,), what)
+        keep = torch.ones(self.g.n, dtype=torch.bool, device=self.dev)
+        keep[self.idx.reshape(-1)] = False
+        assert self.g.untouched(keep), (what, "a pixel past M of the last micro-tile was written")
+        return self.g.out[self.idx].cpu()
+
+
+class Conv2dFold(Op):
+    """ap_conv2d_fold_nhwc: accumulator = t[m][0] + x2[sampled pixel of m][0] (w = 1 on the first channel of either segment)"""
+    impulse = 1.0
+
+    def __init__(self, dev, N, Ho, Cin, Cin2, Cout, s2):
+        self.dev, self.N, self.Ho, self.Cin, self.Cin2, self.s2 = dev, N, Ho, Cin, Cin2, s2
+        self.H2 = 2 * Ho - 1 if s2 == 2 else Ho
+        self.M, self.C = N * Ho * Ho, Cout
+        self.x = torch.zeros(self.M, Cin, dtype=torch.float16, device=dev)           # t
+        self.x_flat = self.x.view(-1)
+        self.x2 = torch.zeros(N, self.H2, self.H2, Cin2, dtype=torch.float16, device=dev)
+        w = torch.zeros(Cout, 1, 1, Cin + Cin2)
+        w[:, 0, 0, 0] = w[:, 0, 0, Cin] = 1.0
+        self.w = _w_dev(w, PREC, dev)
+        self.scale = _pad_rows(torch.ones(Cout), _cpad(Cout), 1.0).to(dev)
+        self.shift = _pad_rows(torch.zeros(Cout), _cpad(Cout), 1.0e6).to(dev)
+        self.g = Guarded(dev, PREC, self.M * Cout)
+
+    def in_index(self, m):
+        return m * self.Cin
+
+    def fill_alt(self):
+        """x2: image k all +4, image k + 1 all -4 (the "alt" family, sampled and unsampled pixels alike); t = 1 - x2 at the sampled
+        pixel, so the accumulator of every stored row is exactly 1 -- and that of a masked row which aliases a row of x2 is not"""
+        sign = torch.tensor([4.0 if n % 2 == 0 else -4.0 for n in range(self.N)], device=self.dev)
+        self.x2[..., 0] = sign.view(-1, 1, 1).to(torch.float16)
+        self.x.view(self.N, self.Ho * self.Ho, self.Cin)[:, :, 0] = (1.0 - sign).view(-1, 1).to(torch.float16)
+
+    def launch(self):
+        Nn, L = _lib()
+        rc = L.ap_conv2d_fold_nhwc(Nn.PRECISIONS[PREC], _p(self.x), _p(self.x2), _p(self.w), _p(self.scale), _p(self.shift), None, _p(self.g.out),
+                                   self.N, self.Ho, self.H2, self.Cin, self.Cin2, self.C, self.s2, 1, Nn.stream_ptr(self.dev))
+        assert rc == 0, ("ap_conv2d_fold_nhwc", rc)
+
+
+FORM_CFGS = (-1, 11, 100)
+TILED_SENTINEL_SHAPES = ("p1_m129", "r3_5x9")                # M = 129 and 90: ragged for the 16-pixel micro-tile and for every tile
+FOLD_SENTINEL_SHAPES = ((3, 7, 64, 64, 136, 2), (3, 5, 128, 64, 72, 1))   # (N, Ho, Cin, Cin2, Cout, stride2): M = 147 and 75
+
+
+@gpu
+@pytest.mark.parametrize("cfg", FORM_CFGS)
+@pytest.mark.parametrize("form", ["tiled", "fold"])
+def test_conv2d_forms_sentinel(dev, form, cfg):
+    """The fragment-tiled output and the second K segment of the generic kernels on two ragged shapes each: silent at the top of the
+    range under the baits, one overflow at a time over the probes of the configuration's tile"""
+    Nn, L = _lib()
+    rows, width = PIPE_TILES[cfg]
+    Nn.check(L.ap_set_conv_config(cfg), "ap_set_conv_config")
+    n = 0
+    try:
+        with Hook(dev) as hook:
+            if form == "tiled":
+                for shp in [s for s in SHAPES if s[0] in TILED_SENTINEL_SHAPES]:
+                    op = Conv2dTiled(dev, shp)
+                    what = "tiled cfg=%d %s" % (cfg, shp[0])
+                    for kind in SILENT:
+                        run_case(hook, op, conv_case(shp, kind), "%s %s" % (what, kind), key=(shp[0], kind))
+                    n += sweep(hook, op, probes(op.M, op.C, rows, width), what, op.scale)
+                    op.stored(what)
+            else:
+                for N, Ho, Cin, Cin2, Cout, s2 in FOLD_SENTINEL_SHAPES:
+                    op = Conv2dFold(dev, N, Ho, Cin, Cin2, Cout, s2)
+                    what = "fold cfg=%d M=%d" % (cfg, op.M)
+                    op.fill_alt()
+                    for sc, sh in ((TOP, 0.0), (-16.0, OVF)):                        # top; rowbait
+                        op.scale[:Cout] = sc; op.shift[:Cout] = sh
+                        hook.word()
+                        op.launch()
+                        w = hook.word()
+                        st = op.g.values((op.M, Cout), what)
+                        assert bool((st == F16_MAX).all()), (what, sc, "a stored value is not 65504")
+                        assert not w, (what, sc, "word 1, but 0 stored elements are non-finite")
+                    op.x.zero_(); op.x2.zero_()
+                    op.scale[:Cout] = 1.0; op.shift[:Cout] = 0.0
+                    n += sweep(hook, op, probes(op.M, op.C, rows, width), what, op.scale)
+    finally:
+        L.ap_set_conv_config(-1)
+    print("%-34s %d single overflows" % ("generic kernels, %s form, cfg=%d" % (form, cfg), n))
+
+
+class PairL(Pair):
+    """Pair through ap_conv_pair_layout_nhwc with the layouts of one plan combination (t2_tiled, res_tiled, out_tiled, out_even).
+    Tiled inputs are laid out on the host; a partly written `out` starts as Marked"""
+
+    def __init__(self, dev, P, P2, N1, which, lay):
+        super().__init__(dev, P, P2, N1, which)
+        self.lay, C3 = lay, 4 * P
+        if lay[0]:
+            self.x = torch.zeros(256 * P, dtype=torch.float16, device=dev)
+            self.x_flat = self.x
+        if lay[1]:
+            self.res = torch.zeros(256 * C3, dtype=torch.float16, device=dev)
+        if lay[2] or lay[3]:
+            self.go = Marked(dev, PREC, (256 if lay[2] else 245) * C3)
+        self.g = self.go if which == "out" else self.gt
+        if which == "out" and lay[2]:
+            self.out_layout = "tiled"
+        m = torch.arange(245, device=dev)
+        self.in0 = (((m >> 4) * (P >> 3)) * 128 + (m & 15) * 8) if lay[0] else m * P                  # channel 0 of every pixel of t2
+        c = torch.arange(C3, device=dev)[None, :]
+        mm = m[:, None]
+        self.oidx = (((mm >> 4) * (C3 >> 3) + (c >> 3)) * 128 + (mm & 15) * 8 + (c & 7)) if lay[2] else mm * C3 + c
+        self.even = ((m % 49) // 7 % 2 == 0) & ((m % 7) % 2 == 0)                                       # pixels out_even stores
+        k = torch.arange(P, device=dev)[None, :]
+        self.xidx = (((mm >> 4) * (P >> 3) + (k >> 3)) * 128 + (mm & 15) * 8 + (k & 7)) if lay[0] else mm * P + k
+        self.ridx = (((mm >> 4) * (C3 >> 3) + (c >> 3)) * 128 + (mm & 15) * 8 + (c & 7)) if lay[1] else mm * C3 + c
+
+    def reference(self):
+        """Pair.reference on the NHWC rows the (host-tiled) inputs stand for"""
+        x, res = self.x, self.res
+        self.x, self.res = x.view(-1)[self.xidx], res.view(-1)[self.ridx]
+        try:
+            return Pair.reference(self)
+        finally:
+            self.x, self.res = x, res
+
+    def set_res(self, m, c, v):
+        self.res.view(-1)[int(self.ridx[m, c])] = v
+
+    def stored(self, what):
+        """[245][C] float16 on the host (not for `out` under out_even, whose odd pixels are not stored)"""
+        if self.which == "out":
+            assert not self.lay[3]
+            return self.out_rows(what).cpu()
+        return self.gt.values((245, self.N1), what).cpu().to(torch.float16)
+
+    def in_index(self, m):
+        return int(self.in0[m])
+
+    def set_all(self, v):
+        self.x_flat[self.in0] = v
+
+    def launch(self):
+        Nn, L = _lib()
+        n1 = self.N1 > 0
+        rc = L.ap_conv_pair_layout_nhwc(Nn.PRECISIONS[PREC], _p(self.x), _p(self.x2 if self.P2 else self.res), _p(self.ws), _p(self.s3), _p(self.h3),
+                                        _p(self.s1) if n1 else None, _p(self.h1) if n1 else None, _p(self.go.out), _p(self.gt.out) if n1 else None,
+                                        5, 7, self.P, self.P2, 2, self.N1, self.lay[0], self.lay[1], self.lay[2], self.lay[3], Nn.stream_ptr(self.dev))
+        assert rc == 0, ("ap_conv_pair_layout_nhwc", self.P, self.P2, self.N1, self.lay, rc)
+
+    def out_rows(self, what):
+        """the stored pixels of `out` as rows [.][C3]; the elements that must not be written still hold the marker"""
+        self.go.values((self.go.n,), what)
+        rows = self.go.out[self.oidx]
+        if isinstance(self.go, Marked):
+            keep = torch.ones(self.go.n, dtype=torch.bool, device=self.dev)
+            keep[(self.oidx[self.even] if self.lay[3] else self.oidx).reshape(-1)] = False
+            assert self.go.untouched(keep), (what, "an element of out that must not be stored was written")
+        return rows[self.even] if self.lay[3] else rows
+
+
+PAIR_PLAN = [(128, 256, 128, (1, 0, 1, 0)), (256, 512, 0, (1, 0, 1, 0)),
+             (128, 0, 128, (1, 1, 1, 0)), (128, 0, 256, (1, 1, 1, 0)), (256, 0, 256, (1, 1, 1, 0)),
+             (128, 0, 128, (1, 1, 0, 1)), (128, 0, 256, (1, 1, 0, 1)), (256, 0, 256, (1, 1, 0, 1))]
+
+
+@gpu
+@pytest.mark.parametrize("P,P2,N1,lay", PAIR_PLAN, ids=lambda v: "".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_conv_pair_layout_sentinel(dev, P, P2, N1, lay):
+    """test_conv_pair_sentinel's `out` / `t1n` isolation under the three layout combinations plan_pass produces (ds form:
+    t2_tiled + out_tiled; identity form: t2_tiled + res_tiled + out_tiled, and + out_even).
+    The rule for out_even is the one this file applies to hidden intermediates and to y_even of test_bottleneck64_sentinel[tail-1]: a
+    value that is not stored but is the operand of the kernel's next stage counts as stored.  An odd pixel of `out` is not written,
+    yet its packed value feeds conv1 of the next block: nothing stored is non-finite there (t1n = relu(-inf) = 0), and the word
+    must still be set."""
+    C3 = 4 * P
+    with Hook(dev) as hook:
+        what = "conv_pair layout (%d, %d, %d) %s" % (P, P2, N1, lay)
+        op = PairL(dev, P, P2, N1, "out", lay)
+        op.set_all(1.0)
+        for s, h in ((TOP, 0.0), (-16.0, OVF)):              # top; rowbait (a masked pixel of the ragged tile with accumulator 0: 65520)
+            op.s3[:] = s; op.h3[:] = h
+            hook.word()
+            op.launch()
+            assert not hook.word(), (what, s, "word 1, but 0 stored elements are non-finite")
+            assert bool((op.out_rows(what) == F16_MAX).all()) and bool(torch.isfinite(op.gt.out[:245 * N1]).all()), (what, s)
+        op.x.zero_(); op.s3[:] = 1.0; op.h3[:] = 0.0
+        pos = sample("conv_pair_%d" % C3)
+        if not lay[3]:
+            n_out = sweep(hook, op, pos, what + " out", op.s3, full=lambda m, c: op.reference()[0], other=(op.gt,) if N1 else ())
+            op.out_rows(what)
+        else:
+            pos = pos[::8]
+            assert any(bool(op.even[m]) for m, _ in pos) and any(not bool(op.even[m]) for m, _ in pos)
+            for m, c in pos:
+                op.x_flat[op.in_index(m)] = 1.0; op.s3[c] = OVF
+                hook.word()
+                op.launch()
+                assert hook.word(), (what, "out overflow at pixel %d (even pixels stored) not reported" % m)
+                bad = ~torch.isfinite(op.go.out)
+                even = bool(op.even[m])
+                assert int(bad.sum()) == int(even) and (not even or bool(bad[m * C3 + c])), (what, m, c, int(bad.sum()))
+                assert bool(torch.isfinite(op.gt.out).all()), (what, m, c, "t1n holds non-finite values")
+                op.x_flat[op.in_index(m)] = 0.0; op.s3[c] = 1.0
+            op.launch()
+            op.out_rows(what)
+            n_out = len(pos)
+        if not P2:
+            # the residual add at the boundary, as in test_conv_pair_sentinel: with res_tiled the only sentinel check of the tiled read
+            few = [q for q in probes(245, C3, 64, 128) if not lay[3] or bool(op.even[q[0]])]
+            assert len(few) >= 8
+            for sval, word, nbad in ((16.0, True, 1), (RES_LO, False, 0)):
+                def setup(m, c):
+                    op.set_res(m, c, F16_MAX)
+                    op.s3[c] = sval
+
+                    def undo():
+                        op.set_res(m, c, 0.0)
+                        op.s3[c] = 1.0
+                    return undo
+                one_by_one(hook, op, few, "%s res + %r" % (what, sval), setup, word, nbad, other=(op.gt,))
+            op.launch()
+            op.out_rows(what)
+        n_t1 = 0
+        if N1:
+            op = PairL(dev, P, P2, N1, "t1n", lay)
+            op.set_all(1.0)
+            for s, h in ((TOP, 0.0), (-16.0, OVF)):
+                op.s1[:N1] = s; op.h1[:N1] = h
+                hook.word()
+                op.launch()
+                assert not hook.word(), (what, s, "t1n: word 1, but 0 stored elements are non-finite")
+                assert bool((op.gt.values((245, N1), what) == F16_MAX).all()) and bool(torch.isfinite(op.go.out).all()), (what, s)
             op.x.zero_(); op.s1[:] = 1.0; op.h1[:] = 0.0
             n_t1 = sweep(hook, op, sample("conv_pair_t1n_%d" % N1), what + " t1n", op.s1, full=lambda m, c: op.reference()[1], other=(op.go,))
         print("%-34s %d single overflows in out, %d in t1n" % (what, n_out, n_t1))

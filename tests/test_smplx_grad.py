@@ -87,7 +87,7 @@ def _oracle_rotmat(model):
 # ------------------------------------------------------------------------------------------------ CPU
 def test_binding_exposes_the_backward_entry_points():
     from airpose_amd import _native
-    assert _native.ABI_VERSION == 12                                # (the backward entry points came with 10; 11: the stem / pool operators; 12: the range hook)
+    assert _native.ABI_VERSION == 13                                # (the backward entry points came with 10; 11: the stem / pool operators; 12: the range hook; 13: the trunk-form operators)
     for name in ("ap_smplx_bwd", "ap_batch_rodrigues_bwd"):
         assert name in _native.SIGNATURES
     res, args = _native.SIGNATURES["ap_smplx_bwd"]
