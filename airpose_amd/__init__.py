@@ -18,6 +18,8 @@ Public mirrors of the reference interfaces:
                                           detections in, the batch dict of TwoViewInference / RealDataLoss out, boxes kept on the device
   SyntheticBatches (synth_batches.py)  <- copenet/src/copenet/dsets/aerialpeople.py __getitem__: AerialPeople records and images in,
                                           the batch dict of the trainers, TrainingLoss, EvalMetrics and MeshMetrics out
+  CropAugment (augment.py)             <- the imgaug list commented out at copenet/src/copenet/dsets/aerialpeople.py:72-76: blur, colour,
+                                          gamma, noise and occluders on the crops of the two batch classes (imgaug parity UNPINNED)
 The compute lives in libairpose_hip.so (include/airpose_hip.h); nothing here falls back to CPU.
 """
 __version__ = "0.1.0"
@@ -55,4 +57,7 @@ def __getattr__(name):
     if name == "SyntheticBatches":                                        # likewise (synth_batches.py)
         from .synth_batches import SyntheticBatches
         return SyntheticBatches
+    if name == "CropAugment":                                             # likewise (augment.py)
+        from .augment import CropAugment
+        return CropAugment
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

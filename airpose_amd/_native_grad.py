@@ -96,7 +96,13 @@ SIGNATURES = {
     # synthetic-data batches (synth_batch.hip): 9 inputs and 14 outputs, all device pointers
     "apg_synth_batch": (_i, [_i] * 11 + [_f, _f, _u64, _i] + [_vp] * 9 + [_vp] * 14 + [_vp]),
     "apg_synth_crops": (_i, [_i] * 4 + [_vp] * 6 + [_vp]),
+    # crop augmentation (augment.hip); cfg is a HOST array of AUG_CFG floats
+    "apg_augment_draw": (_i, [_i, _u64, _i, _vp, _vp, _i, _c.POINTER(_f)] + [_vp] * 7 + [_vp]),
+    "apg_augment_crops": (_i, [_i, _u64, _i, _vp, _vp, _i] + [_vp] * 10 + [_vp]),
 }
+# include/airpose_grad.h: APG_AUG_*; the last four are the bits of status
+AUG_TILE, AUG_THREADS, AUG_MAX_RADIUS, AUG_MAX_RECTS, AUG_CFG = 32, 256, 6, 4, 18
+AUG_BLUR_CLAMPED, AUG_NONFINITE, AUG_RECT_CLIPPED, AUG_BAD_BOX = 1, 2, 4, 8
 SYNTH_ORIGINS = {"region": 0, "frame": 1}                    # include/airpose_grad.h: APG_SYNTH_ORIGIN_*
 SYNTH_CLAMPED, SYNTH_WIDENED, SYNTH_OUTSIDE = 1, 2, 4        # include/airpose_grad.h: APG_SYNTH_*, the bits of status
 SYNTH_THREADS = 128      # include/airpose_grad.h: APG_SYNTH_THREADS

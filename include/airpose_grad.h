@@ -824,6 +824,91 @@ int apg_synth_batch(int n, int V, int J, int H, int W, int Hc, int Wc, int margi
 int apg_synth_crops(int n, int Hc, int Wc, int bgr, const unsigned char* frames, const int* crops, const int* flip, float* im,
                     float* scale, int* pad, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Crop augmentation (augment.hip): blur, colour, gamma, noise and occluders on the (2, n, 3, 224, 224) crops that apg_synth_crops and
+ * ap_preprocess_crops write, without leaving the device.  The reference's dataset lists its augmentations, commented out, at
+ * copenet/src/copenet/dsets/aerialpeople.py:72-76 (imgaug: brightness, hue and saturation, colour temperature, per-channel gamma,
+ * grayscale); parity with imgaug is UNPINNED -- THIS TEXT is the contract.  apg_augment_draw writes a parameter set from stateless
+ * draws; apg_augment_crops applies a parameter set (drawn or planted) in ONE launch for both views and all n images, the image read
+ * once and written once.  Additive under ABI 2: a binding tells a library that has them by looking up apg_augment_crops.  Stateless,
+ * no workspace; all pointers are device pointers to contiguous arrays, 4-byte aligned, except cfg, a HOST array.
+ *
+ * The parameter set, per (suffix s, sample i):
+ *   blur_taps (2, n, 7) fp32: the half kernel w0 .. w6 of a normalised, symmetric, separable blur.  The radius r is the index of the
+ *     last non-zero tap; r = 0 skips the stage (w0 is then not read).
+ *   color (2, n, 3, 4) fp32 = [M | b], row-major.  Exactly [I | 0] skips the stage.
+ *   gamma (2, n, 3) fp32, per channel; exactly 1 skips that channel.
+ *   noise_sigma (2, n) fp32; 0 skips the stage.
+ *   rects (2, n, 4, 4) int32 = y0, y1, x0, x1 in crop pixels (rows and columns of the 224 x 224 image); y1 <= y0 or x1 <= x0: empty.
+ *   rect_rgb (2, n, 4, 3) fp32: the fill colours, clamped to [0, 1] when they are used.
+ *
+ * apg_augment_crops, per image, on de-normalised RGB v = x * std + mean (mean 0.485, 0.456, 0.406, std 0.229, 0.224, 0.225), every
+ * product, sum and quotient below rounded to fp32 once, in the order written (no fused multiply-add); clamp(t) = min(max(t, 0), 1):
+ *   The content rectangle is recomputed from crops (2, n, 4) int32 = y0, y1, x0, x1 exactly as preprocess_px.inc computes it: h = y1 -
+ *     y0, w = x1 - x0, scale = 224.0 / (double)max(h, w), dw = (int)(scale * w), dh = (int)(scale * h), top = (224 - dh) / 2, left =
+ *     (224 - dw) / 2: rows top .. top + dh - 1, columns left .. left + dw - 1.  Every other pixel is padding.
+ *   Padding pixels are copied bit for bit, always.  With dw == 0 or dh == 0, or a box with y1 <= y0 or x1 <= x0 (APG_AUG_BAD_BOX), the
+ *     whole image is copied.  An image whose stages are all skipped is copied bit for bit: no de-normalise / re-normalise round trip.
+ *   0. v = x * std + mean.
+ *   1. Blur (r > 0): a horizontal pass, then a vertical pass over its result; each pass t = w_r p(-r), then t = t + w_|k| p(k) for k =
+ *      -r + 1 .. r in that order, p(k) the pixel k columns (rows) away with its coordinate clamped to the content rectangle, so
+ *      that padding never bleeds in.
+ *   2. Colour (not [I | 0]): v'_c = clamp(((M_c0 v_0 + M_c1 v_1) + M_c2 v_2) + b_c).
+ *   3. Gamma (gamma_c != 1): v_c = powf(clamp(v_c), gamma_c); the clamp keeps a de-normalised -1e-8 from becoming a NaN.
+ *   4. Noise (sigma != 0): v_c = clamp(v_c + sigma * z_c).  ONE Philox4x32-10 call per pixel, key = (seed's low word, seed's high
+ *      word), counter = (index[i], epoch, camera, 0x80000000 | (row * 224 + column)); words (0, 1) and (2, 3) go through Box-Muller with
+ *      u1 = ((w >> 8) + 1) * 2^-24 of the first word and u2 = (w >> 8) * 2^-24 of the second: rho = sqrtf(-2 * logf(u1)), phi =
+ *      6.2831855f * u2, (rho * cosf(phi), rho * sinf(phi)); z_R, z_G = the pair of words (0, 1), z_B = the cosine of words (2, 3).
+ *   5. Occluders: rects 0 .. 3 in that order (a later one covers an earlier one); a pixel of the content rectangle inside rect k
+ *      takes clamp(rect_rgb[k]).  A rect reaching outside the content rectangle is clipped to it (APG_AUG_RECT_CLIPPED).
+ *   6. out = (v - mean) / std.
+ *   The camera of (s, i) is (cam[i] & 1) ^ s with cam (n) int32 on the device (SyntheticBatches' cam0), or cam_all ^ s when cam is
+ *     NULL (cam_all = 0 or 1: RealSequenceBatches' first_cam).  index (n) int32: the samples' dataset indices.
+ *   Values checked on the device, each reported in status (2, n) int32 and treated as NEUTRAL (APG_AUG_NONFINITE): a non-finite tap
+ *     (r = 0), a non-finite entry of color ([I | 0]), a gamma that is non-finite or negative (1), a non-finite noise_sigma (0), a
+ *     non-finite rect_rgb (that rect is empty).  With the 7 taps the radius cannot pass APG_AUG_MAX_RADIUS.
+ *   One workgroup of APG_AUG_THREADS threads per APG_AUG_TILE x APG_AUG_TILE tile; with r > 0 the tile and its halo of r are staged
+ *     de-normalised in LDS and every later stage runs while the pixel is in registers.  A thread's own four pixels move as 16-byte
+ *     loads and stores where im and out are 16-byte aligned, as 4-byte ones otherwise; the halo is staged with 4-byte loads.  out must not overlap im: a blur in place would race across tile seams.
+ *
+ * apg_augment_draw: one launch, one thread per (s, i), writes the whole parameter set and status.  Philox4x32-10, the key as above,
+ * counter = (index[i], epoch, camera, k) with k >= 1; apg_synth_batch's jitter and flip use k = 0 and the noise k >= 2^31, so no two
+ * streams collide under one seed.  A uniform draw is u = (word >> 8) * 2^-24, exact in fp32; "lo .. hi" below is lo + u * (hi - lo),
+ * each operation rounded to fp32.  A gate is on when u < p.  cfg is a HOST array of APG_AUG_CFG floats, all finite:
+ *     0 p | 1, 2 blur sigma | 3 brightness B | 4 hue H (degrees) | 5, 6 saturation | 7, 8 channel gain | 9, 10 gamma | 11, 12 grayscale
+ *     | 13, 14 noise sigma | 15 occluders (0 .. 4) | 16, 17 occluder side (fractions of 224).
+ *   A stage whose range is neutral (sigma 0 .. 0, B = 0, H = 0, 1 .. 1 for saturation, gain and gamma, 0 .. 0 for grayscale and noise,
+ *   0 occluders) is off: it leaves its exact neutral value whatever its gate.  Word w of block k:
+ *     k = 1: gate blur, sigma, gate brightness, beta = -B .. B          k = 2: gate hue, theta = -H .. H, gate saturation, s
+ *     k = 3: gate gain, gain R, G, B                                    k = 4: gate gamma, gamma R, G, B
+ *     k = 5: gate grayscale, alpha, gate noise, sigma                   k = 6: gate occluders
+ *     k = 7 + j: rect j: side along y, side along x, centre y, centre x k = 11 + j: rect j's colour R, G, B (u itself)
+ *   blur_taps: in fp64, r = min(ceil(3 sigma), 6) (APG_AUG_BLUR_CLAMPED where the minimum acts), w_k = exp(-k^2 / (2 sigma^2)) / (w_0
+ *     + 2 sum w_k), k <= r, rounded to fp32 once; sigma <= 0 gives 1, 0, ..
+ *   color: M composed in fp64 and rounded once: M = diag(gain); M = Hue(theta) M; M = ((1 - s) L + s I) M; M = (alpha L + (1 - alpha) I) M,
+ *     each only where its gate is on, L the matrix whose rows are (0.299, 0.587, 0.114).  Hue(theta) = L + cos(theta) (I - L) +
+ *     sin(theta) K is the rotation of the I-Q plane of YIQ, K = ((0.168, 0.330, -0.497), (-0.328, 0.035, 0.292), (1.25, -1.05, -0.203)).
+ *     b = (beta, beta, beta).  All gates off leaves exactly [I | 0].
+ *   rects: for j < occluders, sides hy = (int)(f_y * 224), hx = (int)(f_x * 224) with f = lo .. hi, centres cy = (int)(u * 224), cx
+ *     likewise: y0 = cy - hy / 2, y1 = y0 + hy, x0 = cx - hx / 2, x1 = x0 + hx (crop pixels, not clipped here); the others 0, 0, 0, 0.
+ * A draw depends on (seed, index, epoch, camera) and cfg alone: not on the batch, the row or the camera shuffle.
+ * APG_EINVAL before any GPU call, the message naming the argument: n outside 1 .. 65535, a NULL or misaligned pointer (cam may be
+ * NULL), cam_all outside 0 .. 1, a cfg entry that is not finite or outside its range, out overlapping im. */
+#define APG_AUG_TILE 32
+#define APG_AUG_THREADS 256
+#define APG_AUG_MAX_RADIUS 6
+#define APG_AUG_MAX_RECTS 4
+#define APG_AUG_CFG 18
+#define APG_AUG_BLUR_CLAMPED 1
+#define APG_AUG_NONFINITE 2
+#define APG_AUG_RECT_CLIPPED 4
+#define APG_AUG_BAD_BOX 8
+int apg_augment_draw(int n, uint64_t seed, int epoch, const int* index, const int* cam, int cam_all, const float* cfg,
+                     float* blur_taps, float* color, float* gamma, float* noise_sigma, int* rects, float* rect_rgb, int* status, void* stream);
+int apg_augment_crops(int n, uint64_t seed, int epoch, const int* index, const int* cam, int cam_all, const float* im,
+                      const int* crops, const float* blur_taps, const float* color, const float* gamma, const float* noise_sigma, const int* rects,
+                      const float* rect_rgb, float* out, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
