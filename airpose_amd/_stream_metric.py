@@ -4,6 +4,8 @@ classes' base and the evaluate loop.
 """
 import torch
 
+from . import _args as A
+
 KINDS = ("twoview", "singleview", "hmr", "muhmr")
 VIEWS = {"twoview": 2, "singleview": 1, "hmr": 1, "muhmr": 2}
 
@@ -11,8 +13,7 @@ VIEWS = {"twoview": 2, "singleview": 1, "hmr": 1, "muhmr": 2}
 def check_what(owner, t, shape, name):
     """what a tensor must be, wherever it lives: a tensor, of `shape`, floating point; anything else is refused by name, in owner's
     name.  shape: a tuple, or the owner's own rule: a function of the tensor's shape -> what it should have been, None where it fits"""
-    if not torch.is_tensor(t):
-        raise RuntimeError("%s: %s must be a tensor, got %s" % (owner, name, type(t).__name__))
+    A.is_tensor(owner, t, name)
     want = shape(tuple(t.shape)) if callable(shape) else (None if tuple(t.shape) == tuple(shape) else tuple(shape))
     if want is not None:
         raise RuntimeError("%s: %s must be %s, got %s" % (owner, name, want, tuple(t.shape)))
@@ -23,10 +24,7 @@ def check_what(owner, t, shape, name):
 def check_where(owner, t, dev, name, anchor):
     """where a tensor must live: on the GPU, on dev (None: any CUDA device), which is where `anchor` ("the metrics") lives
     -> fp32, detached, contiguous"""
-    if not t.is_cuda:
-        raise RuntimeError("%s: %s lives on %s; it must be a CUDA (ROCm) tensor, there is no CPU path" % (owner, name, t.device))
-    if dev is not None and t.device != dev:
-        raise RuntimeError("%s: %s lives on %s, %s on %s" % (owner, name, t.device, anchor, dev))
+    A.lives_on(owner, t, dev, name, anchor)
     if t.dtype != torch.float32:
         t = t.float()
     return t.detach().contiguous()
@@ -53,11 +51,7 @@ class StreamMetric(object):
             raise ValueError("%s: kind must be one of %s, got %r" % (self.NAME, ", ".join(KINDS), kind))
         self.kind, self.views, self.per_sample = kind, VIEWS[kind], bool(per_sample)
         self._configure(*own)                                    # (between the two: a call with two mistakes hears of the same one)
-        self.device = torch.device(device) if device is not None else torch.device("cuda")
-        if self.device.type != "cuda":
-            raise RuntimeError("%s: device must be a CUDA (ROCm) device, got %s; there is no CPU path" % (self.NAME, self.device))
-        if self.device.index is None:                            # (a given index constructs without a GPU)
-            self.device = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        self.device = A.cuda_device(self.NAME, device)
         self._acc = self._ws = None
         self.reset()
 

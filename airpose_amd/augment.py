@@ -15,10 +15,10 @@ tested.  There is no CPU path and no fallback: a missing library is an error.
 """
 import ctypes
 import math
-import operator
 
 import torch
 
+from . import _args as A
 from . import _native_grad as G
 
 NAME = "CropAugment"
@@ -88,11 +88,7 @@ class CropAugment:
     def __init__(self, seed=0, p=0.5, blur_sigma=(0.0, 2.0), brightness=30 / 255, hue_deg=35.0, saturation=(0.6, 1.4),
                  channel_gain=(0.8, 1.2), gamma=(0.5, 2.0), grayscale=(0.0, 1.0), noise_sigma=(0.0, 0.03), occluders=2,
                  occluder_side=(0.1, 0.4), device=None):
-        self.device = torch.device(device) if device is not None else torch.device("cuda")
-        if self.device.type != "cuda":
-            raise RuntimeError("%s: device must be a CUDA (ROCm) device, got %s; there is no CPU path" % (NAME, self.device))
-        if self.device.index is None:                        # (a given index constructs without a GPU)
-            self.device = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        self.device = A.cuda_device(NAME, device)
         if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
             raise ValueError("%s: seed must be a whole number in 0 .. 2^64 - 1, got %r" % (NAME, seed))
         self.seed = seed
@@ -120,21 +116,9 @@ class CropAugment:
         self.status = None
 
     # ---------------------------------------------------------------------------------------- the arguments
-    def _epoch(self, epoch):
-        try:
-            epoch = operator.index(epoch)
-        except TypeError:
-            raise RuntimeError("%s: epoch must be an integer, got %s" % (NAME, type(epoch).__name__)) from None
-        if not 0 <= epoch < 2 ** 31:
-            raise RuntimeError("%s: epoch must be in 0 .. 2^31 - 1, got %r" % (NAME, epoch))
-        return epoch
-
     def _index_cam(self, index, cam, n=None):
         """-> n, the device tensors to check, cam as (tensor or None, whole-batch camera)"""
-        if not torch.is_tensor(index):
-            raise RuntimeError("%s: index must be a tensor, got %s" % (NAME, type(index).__name__))
-        if index.dtype != torch.int32:
-            raise RuntimeError("%s: index must be int32 (nothing is cast), got %s" % (NAME, index.dtype))
+        A.exact_tensor(NAME, index, torch.int32, "index")
         if index.dim() != 1 or index.shape[0] < 1 or (n is not None and index.shape[0] != n):
             raise RuntimeError("%s: index must be (n,)%s, got %s" % (NAME, "" if n is None else " with n = %d" % n, tuple(index.shape)))
         n = int(index.shape[0])
@@ -144,8 +128,7 @@ class CropAugment:
         if cam is None:
             return n, ten, (None, 0)
         if torch.is_tensor(cam):
-            if cam.dtype != torch.int32:
-                raise RuntimeError("%s: cam must be int32 (nothing is cast), got %s" % (NAME, cam.dtype))
+            A.exact_tensor(NAME, cam, torch.int32, "cam")
             if tuple(cam.shape) != (n,):
                 raise RuntimeError("%s: cam must be (n,) with n = %d, got %s" % (NAME, n, tuple(cam.shape)))
             ten["cam"] = cam
@@ -156,15 +139,12 @@ class CropAugment:
 
     def _devices(self, ten):
         for name, t in ten.items():
-            if not t.is_cuda:
-                raise RuntimeError("%s: %s lives on %s; it must be a CUDA (ROCm) tensor, there is no CPU path" % (NAME, name, t.device))
-            if t.device != self.device:
-                raise RuntimeError("%s: %s lives on %s, the augmentation on %s" % (NAME, name, t.device, self.device))
+            A.lives_on(NAME, t, self.device, name, "the augmentation")
 
     # ---------------------------------------------------------------------------------------- the draws
     def draw(self, index, epoch=0, cam=None):
         n, ten, (cam_t, cam_all) = self._index_cam(index, cam)
-        epoch = self._epoch(epoch)
+        epoch = A.epoch_index(NAME, epoch)
         self._devices(ten)
         dev = self.device
         index = index.contiguous()
@@ -179,19 +159,13 @@ class CropAugment:
 
     # ---------------------------------------------------------------------------------------- the images
     def apply(self, im, crops, params, index, epoch=0, cam=None, out=None):
-        if not torch.is_tensor(im):
-            raise RuntimeError("%s: im must be a tensor, got %s" % (NAME, type(im).__name__))
-        if im.dtype != torch.float32:
-            raise RuntimeError("%s: im must be float32 (nothing is cast), got %s" % (NAME, im.dtype))
+        A.exact_tensor(NAME, im, torch.float32, "im")
         if im.dim() != 5 or im.shape[0] != 2 or im.shape[1] < 1 or tuple(im.shape[2:]) != (3, IMG, IMG):
             raise RuntimeError("%s: im must be (2, n, 3, %d, %d), got %s" % (NAME, IMG, IMG, tuple(im.shape)))
         n = int(im.shape[1])
         n, ten, (cam_t, cam_all) = self._index_cam(index, cam, n)
         ten["im"] = im
-        if not torch.is_tensor(crops):
-            raise RuntimeError("%s: crops must be a tensor, got %s" % (NAME, type(crops).__name__))
-        if crops.dtype != torch.int32:
-            raise RuntimeError("%s: crops must be int32 (nothing is cast), got %s" % (NAME, crops.dtype))
+        A.exact_tensor(NAME, crops, torch.int32, "crops")
         if tuple(crops.shape) != (2, n, 4):
             raise RuntimeError("%s: crops must be (2, n, 4) with n = %d, got %s" % (NAME, n, tuple(crops.shape)))
         ten["crops"] = crops
@@ -201,10 +175,7 @@ class CropAugment:
             if k not in params:
                 raise RuntimeError("%s: params has no %r" % (NAME, k))
             t = params[k]
-            if not torch.is_tensor(t):
-                raise RuntimeError("%s: params[%r] must be a tensor, got %s" % (NAME, k, type(t).__name__))
-            if t.dtype != dt:
-                raise RuntimeError("%s: params[%r] must be %s (nothing is cast), got %s" % (NAME, k, str(dt).replace("torch.", ""), t.dtype))
+            A.exact_tensor(NAME, t, dt, "params[%r]" % k)
             if tuple(t.shape) != (2, n) + tail:
                 want = "(" + ", ".join(("2", "n") + tuple(map(str, tail))) + ")"
                 raise RuntimeError("%s: params[%r] must be %s with n = %d, got %s" % (NAME, k, want, n, tuple(t.shape)))
@@ -213,7 +184,7 @@ class CropAugment:
             if not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != tuple(im.shape) or not out.is_contiguous():
                 raise RuntimeError("%s: out must be a contiguous float32 tensor of im's shape %s" % (NAME, tuple(im.shape)))
             ten["out"] = out
-        epoch = self._epoch(epoch)
+        epoch = A.epoch_index(NAME, epoch)
         self._devices(ten)
         dev = self.device
         im, crops, index = im.detach().contiguous(), crops.contiguous(), index.contiguous()
@@ -250,8 +221,7 @@ class CropAugment:
         for k in ("im0", "im1", "crops0", "crops1"):
             if k not in batch:
                 raise RuntimeError("%s: batch has no %r" % (NAME, k))
-            if not torch.is_tensor(batch[k]):
-                raise RuntimeError("%s: batch[%r] must be a tensor, got %s" % (NAME, k, type(batch[k]).__name__))
+            A.is_tensor(NAME, batch[k], "batch[%r]" % k)
         for v in (0, 1):
             t = batch["im%d" % v]
             if t.dim() != 4 or tuple(t.shape[1:]) != (3, IMG, IMG) or t.shape != batch["im0"].shape:

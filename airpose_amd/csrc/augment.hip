@@ -43,20 +43,8 @@ struct CropArgs {
     int* status;
 };
 
-// Philox4x32-10 of Random123, as in synth_batch.hip: ten rounds, the key bumped by the Weyl constants between them
-struct U4 { uint32_t w[4]; };
-__device__ __forceinline__ U4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return U4{{c0, c1, c2, c3}};
-}
+#include "draws.inc"
 
-__device__ __forceinline__ float uni(uint32_t w) { return (float)(w >> 8) * (1.0f / 16777216.0f); }
 __device__ __forceinline__ float range(uint32_t w, float lo, float hi) { return lo + uni(w) * (hi - lo); }
 __device__ __forceinline__ float clamp01(float t) { return fminf(fmaxf(t, 0.f), 1.f); }
 __device__ __forceinline__ bool is_fin(float t) { return fabsf(t) < INFINITY; }
@@ -369,16 +357,6 @@ __global__ void __launch_bounds__(NT) augment_crops_kernel(const CropArgs a) {
     }
 }
 
-struct Ptr { const void* p; const char* name; };
-
-int check_ptrs(const std::string& f, const Ptr* ps, int count) {
-    for (int k = 0; k < count; ++k) {
-        if (!ps[k].p) return apg_fail(APG_EINVAL, f + ps[k].name + " is NULL");
-        if ((uintptr_t)ps[k].p & 3u) return apg_fail(APG_EINVAL, f + ps[k].name + " is not 4-byte aligned");
-    }
-    return APG_OK;
-}
-
 int check_n_cam(const std::string& f, int n, const int* cam, int cam_all) {
     if (n < 1 || n > MAX_N) return apg_fail(APG_EINVAL, f + "n must be in 1 .. " + std::to_string(MAX_N));
     if ((uintptr_t)cam & 3u) return apg_fail(APG_EINVAL, f + "cam is not 4-byte aligned");
@@ -392,9 +370,9 @@ extern "C" int apg_augment_draw(int n, uint64_t seed, int epoch, const int* inde
                                 const float* cfg, float* blur_taps, float* color, float* gamma, float* noise_sigma, int* rects,
                                 float* rect_rgb, int* status, void* stream) {
     const std::string f = "apg_augment_draw: ";
-    const Ptr ps[] = {{index, "index"}, {cfg, "cfg"}, {blur_taps, "blur_taps"}, {color, "color"}, {gamma, "gamma"},
-                      {noise_sigma, "noise_sigma"}, {rects, "rects"}, {rect_rgb, "rect_rgb"}, {status, "status"}};
-    if (int rc = check_ptrs(f, ps, 9)) return rc;
+    const ApgPtr ps[] = {{index, "index", 4}, {cfg, "cfg", 4}, {blur_taps, "blur_taps", 4}, {color, "color", 4}, {gamma, "gamma", 4},
+                         {noise_sigma, "noise_sigma", 4}, {rects, "rects", 4}, {rect_rgb, "rect_rgb", 4}, {status, "status", 4}};
+    if (int rc = apg_check_ptrs(f, ps, 9)) return rc;
     if (int rc = check_n_cam(f, n, cam, cam_all)) return rc;
     DrawArgs k = {n, cam_all, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)epoch, index, cam, {}, blur_taps, color, gamma,
                   noise_sigma, rect_rgb, rects, status};
@@ -416,9 +394,10 @@ extern "C" int apg_augment_crops(int n, uint64_t seed, int epoch, const int* ind
                                  const float* noise_sigma, const int* rects, const float* rect_rgb, float* out, int* status,
                                  void* stream) {
     const std::string f = "apg_augment_crops: ";
-    const Ptr ps[] = {{index, "index"}, {im, "im"}, {crops, "crops"}, {blur_taps, "blur_taps"}, {color, "color"}, {gamma, "gamma"},
-                      {noise_sigma, "noise_sigma"}, {rects, "rects"}, {rect_rgb, "rect_rgb"}, {out, "out"}, {status, "status"}};
-    if (int rc = check_ptrs(f, ps, 11)) return rc;
+    const ApgPtr ps[] = {{index, "index", 4}, {im, "im", 4}, {crops, "crops", 4}, {blur_taps, "blur_taps", 4}, {color, "color", 4},
+                         {gamma, "gamma", 4}, {noise_sigma, "noise_sigma", 4}, {rects, "rects", 4}, {rect_rgb, "rect_rgb", 4},
+                         {out, "out", 4}, {status, "status", 4}};
+    if (int rc = apg_check_ptrs(f, ps, 11)) return rc;
     if (int rc = check_n_cam(f, n, cam, cam_all)) return rc;
     const uintptr_t bytes = (uintptr_t)2 * n * 3 * IMG * IMG * sizeof(float), i0 = (uintptr_t)im, o0 = (uintptr_t)out;
     if (i0 < o0 + bytes && o0 < i0 + bytes) return apg_fail(APG_EINVAL, f + "out must not overlap im");

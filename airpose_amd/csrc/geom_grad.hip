@@ -140,6 +140,15 @@ int apg_fail(int code, const std::string& msg) {
     return code;
 }
 
+int apg_check_ptrs(const std::string& f, const ApgPtr* ps, int count) {
+    for (int k = 0; k < count; ++k) {
+        if (!ps[k].p) return apg_fail(APG_EINVAL, f + ps[k].name + " is NULL");
+        if ((uintptr_t)ps[k].p & (uintptr_t)(ps[k].align - 1))
+            return apg_fail(APG_EINVAL, f + ps[k].name + " is not " + std::to_string(ps[k].align) + "-byte aligned");
+    }
+    return APG_OK;
+}
+
 #define APG_CHECK_LAUNCH(what)                                                                      \
     do {                                                                                            \
         hipError_t _e = hipGetLastError();                                                          \

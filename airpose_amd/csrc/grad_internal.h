@@ -1,6 +1,7 @@
 // Internal helpers shared by the sources of libairpose_grad.so (head_mlp.hip, head_grad.hip, head_local_grad.hip, geom_grad.hip,
 // trunk_grad.hip, trunk_grad_bf16.hip, loss_grad.hip, loss_real_grad.hip, optim.hip, eval_metrics.hip, render.hip, eval_align.hip, xview_metrics.hip, seq_fit.hip, seq_batch.hip, synth_batch.hip, augment.hip).  Texts that only some of them share are includes of their own: trunk_elem.inc
-// and trunk_walk.inc (the two trunks), loss_common.inc (the losses and geom_grad.hip), metric_common.inc (eval_metrics.hip, eval_align.hip, xview_metrics.hip).
+// and trunk_walk.inc (the two trunks), loss_common.inc (the losses and geom_grad.hip), metric_common.inc (eval_metrics.hip, eval_align.hip, xview_metrics.hip),
+// draws.inc (synth_batch.hip, augment.hip), preprocess_px.inc (synth_batch.hip, and stem.hip of libairpose_hip.so).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,6 +12,11 @@
 
 // records the thread-local message apg_last_error() returns; returns code
 __attribute__((visibility("hidden"))) int apg_fail(int code, const std::string& msg);
+
+// every pointer present and aligned (align a power of two), in list order, or APG_EINVAL naming the first that is not:
+// "<f><name> is NULL", "<f><name> is not <align>-byte aligned"
+struct ApgPtr { const void* p; const char* name; int align; };
+__attribute__((visibility("hidden"))) int apg_check_ptrs(const std::string& f, const ApgPtr* ps, int count);
 
 // returns from the calling entry point with the HIP error code of `expr` and a message naming it
 #define APG_TRY(expr)                                                                               \

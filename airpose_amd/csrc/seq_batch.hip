@@ -131,12 +131,9 @@ extern "C" int apg_real_batch(int L, int a, int n, const float* det, const float
                               int border, float* j2d, int* crops, int* crop_info, float* bb, float* j2d_crop, int* status,
                               void* stream) {
     const std::string f = "apg_real_batch: ";
-    const struct { const void* p; const char* name; } ps[] = {{det, "det"}, {principal, "principal"}, {size, "size"}, {j2d, "j2d"},
-        {crops, "crops"}, {crop_info, "crop_info"}, {bb, "bb"}, {j2d_crop, "j2d_crop"}, {status, "status"}};
-    for (const auto& p : ps) {
-        if (!p.p) return apg_fail(APG_EINVAL, f + p.name + " is NULL");
-        if ((uintptr_t)p.p & 3u) return apg_fail(APG_EINVAL, f + p.name + " is not 4-byte aligned");
-    }
+    const ApgPtr ps[] = {{det, "det", 4}, {principal, "principal", 4}, {size, "size", 4}, {j2d, "j2d", 4}, {crops, "crops", 4},
+                         {crop_info, "crop_info", 4}, {bb, "bb", 4}, {j2d_crop, "j2d_crop", 4}, {status, "status", 4}};
+    if (int rc = apg_check_ptrs(f, ps, 9)) return rc;
     if (L < 1 || L > MAX_L) return apg_fail(APG_EINVAL, f + "L must be in 1 .. " + std::to_string(MAX_L));
     if (n < 1) return apg_fail(APG_EINVAL, f + "n must be at least 1");
     if (a < 0) return apg_fail(APG_EINVAL, f + "a must not be negative");

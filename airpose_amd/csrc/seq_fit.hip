@@ -268,18 +268,6 @@ __global__ void __launch_bounds__(NT) seq_export_kernel(const ExportArgs a) {
 static_assert(SR * 64 + SR * 2 <= NT && SR * 2 * NJ2 <= NT && NT % 64 == 0, "seq_init_kernel's thread roles");
 static_assert(SR * NZ + SR * 2 <= NT && SR * NB <= 128 && 128 + SR <= NT && NOUT <= 128, "seq_export_kernel's thread roles");
 
-struct Ptr { const void* p; const char* name; int align; };
-
-// every pointer present and aligned, or APG_EINVAL naming the first that is not
-int pointers_ok(const std::string& f, const Ptr* ps, int n) {
-    for (int i = 0; i < n; ++i) {
-        if (!ps[i].p) return apg_fail(APG_EINVAL, f + ps[i].name + " is NULL");
-        if ((uintptr_t)ps[i].p & (uintptr_t)(ps[i].align - 1))
-            return apg_fail(APG_EINVAL, f + ps[i].name + " is not " + std::to_string(ps[i].align) + "-byte aligned");
-    }
-    return APG_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -289,10 +277,10 @@ int apg_seq_init(int L, const float* angles0, const float* angles1, const float*
                  float* phi, float* tau, float* j2d, int* robust, void* stream) {
     const std::string f = "apg_seq_init: ";
     if (L < 1 || L > MAX_L) return apg_fail(APG_EINVAL, f + "L must be in 1 .. " + std::to_string(MAX_L));
-    const Ptr ps[] = {{angles0, "angles0", 4}, {angles1, "angles1", 4}, {trans0, "trans0", 4}, {trans1, "trans1", 4}, {det, "det", 4},
+    const ApgPtr ps[] = {{angles0, "angles0", 4}, {angles1, "angles1", 4}, {trans0, "trans0", 4}, {trans1, "trans1", 4}, {det, "det", 4},
                       {W1, "W1", 4}, {b1, "b1", 4}, {Wmu, "Wmu", 16}, {bmu, "bmu", 4}, {z, "z", 4}, {phi, "phi", 4}, {tau, "tau", 4},
                       {j2d, "j2d", 4}, {robust, "robust", 4}};
-    if (int rc = pointers_ok(f, ps, (int)(sizeof(ps) / sizeof(ps[0])))) return rc;
+    if (int rc = apg_check_ptrs(f, ps, (int)(sizeof(ps) / sizeof(ps[0])))) return rc;
     if (!std::isfinite(agreement_px) || agreement_px < 0.f)
         return apg_fail(APG_EINVAL, f + "agreement_px must be finite and not negative");
     if (!std::isfinite(robust_conf)) return apg_fail(APG_EINVAL, f + "robust_conf must be finite");
@@ -308,10 +296,10 @@ int apg_seq_export(int L, const float* z, const float* phi, const float* tau, co
                    float* cam1_wrt_cam0, void* stream) {
     const std::string f = "apg_seq_export: ";
     if (L < 1 || L > MAX_L) return apg_fail(APG_EINVAL, f + "L must be in 1 .. " + std::to_string(MAX_L));
-    const Ptr ps[] = {{z, "z", 4}, {phi, "phi", 4}, {tau, "tau", 4}, {w1, "w1", 16}, {b1, "b1", 4}, {w2, "w2", 16}, {b2, "b2", 4},
+    const ApgPtr ps[] = {{z, "z", 4}, {phi, "phi", 4}, {tau, "tau", 4}, {w1, "w1", 16}, {b1, "b1", 4}, {w2, "w2", 16}, {b2, "b2", 4},
                       {w3, "w3", 16}, {b3, "b3", 4}, {thetas, "thetas", 4}, {root_rot, "root_rot", 4},
                       {smpl_wrt_cam, "smpl_wrt_cam", 4}, {cam1_wrt_cam0, "cam1_wrt_cam0", 4}};
-    if (int rc = pointers_ok(f, ps, (int)(sizeof(ps) / sizeof(ps[0])))) return rc;
+    if (int rc = apg_check_ptrs(f, ps, (int)(sizeof(ps) / sizeof(ps[0])))) return rc;
     ExportArgs a = {L, z, phi, tau, w1, b1, w2, b2, w3, b3, thetas, root_rot, smpl_wrt_cam, cam1_wrt_cam0};
     hipLaunchKernelGGL(seq_export_kernel, dim3((unsigned)((L + SR - 1) / SR)), dim3(NT), 0, (hipStream_t)stream, a);
     APG_TRY(hipGetLastError());

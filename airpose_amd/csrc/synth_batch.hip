@@ -42,18 +42,7 @@ struct SynthArgs {
     float *bb, *intr_out, *extr_out, *verts_rel, *joints_rel, *orient_rel, *trans_rel, *j2d, *j2d_crop, *pose_rotmat;
 };
 
-// Philox4x32-10 of Random123: ten rounds, the key bumped by the Weyl constants between them
-struct U4 { uint32_t w[4]; };
-__device__ __forceinline__ U4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return U4{{c0, c1, c2, c3}};
-}
+#include "draws.inc"
 
 __device__ __forceinline__ int sample_flip(const SynthArgs& a, int i) {
     if (!a.shuffle) return 0;
@@ -202,16 +191,6 @@ __global__ void __launch_bounds__(256) synth_crops_kernel(int n, int Hc, int Wc,
     preprocess_px(frames + ((size_t)c * n + i) * Hc * Wc * 3, Wc, bgr, cr, im + f * 3 * IMG * IMG, scale + f, pad + f * 2, px);
 }
 
-struct Ptr { const void* p; const char* name; };
-
-int check_ptrs(const std::string& f, const Ptr* ps, int count) {
-    for (int k = 0; k < count; ++k) {
-        if (!ps[k].p) return apg_fail(APG_EINVAL, f + ps[k].name + " is NULL");
-        if ((uintptr_t)ps[k].p & 3u) return apg_fail(APG_EINVAL, f + ps[k].name + " is not 4-byte aligned");
-    }
-    return APG_OK;
-}
-
 }  // namespace
 
 extern "C" int apg_synth_batch(int n, int V, int J, int H, int W, int Hc, int Wc, int margin, int origin, int jitter, int shuffle,
@@ -221,14 +200,14 @@ extern "C" int apg_synth_batch(int n, int V, int J, int H, int W, int Hc, int Wc
                                float* extr_out, float* verts_rel, float* joints_rel, float* orient_rel, float* trans_rel, float* j2d,
                                float* j2d_crop, float* pose_rotmat, void* stream) {
     const std::string f = "apg_synth_batch: ";
-    const Ptr in[] = {{index, "index"}, {bb_in, "bb_in"}, {intr, "intr"}, {extr, "extr"}, {pose, "pose"}, {verts, "verts"},
-                      {joints, "joints"}, {orient, "orient"}, {trans, "trans"}};
-    const Ptr out[] = {{crops, "crops"}, {crop_info, "crop_info"}, {status, "status"}, {flip, "flip"}, {bb, "bb"},
-                       {intr_out, "intr_out"}, {extr_out, "extr_out"}, {verts_rel, "verts_rel"}, {joints_rel, "joints_rel"},
-                       {orient_rel, "orient_rel"}, {trans_rel, "trans_rel"}, {j2d, "j2d"}, {j2d_crop, "j2d_crop"},
-                       {pose_rotmat, "pose_rotmat"}};
-    if (int rc = check_ptrs(f, in, 9)) return rc;
-    if (int rc = check_ptrs(f, out, 14)) return rc;
+    const ApgPtr in[] = {{index, "index", 4}, {bb_in, "bb_in", 4}, {intr, "intr", 4}, {extr, "extr", 4}, {pose, "pose", 4},
+                         {verts, "verts", 4}, {joints, "joints", 4}, {orient, "orient", 4}, {trans, "trans", 4}};
+    const ApgPtr out[] = {{crops, "crops", 4}, {crop_info, "crop_info", 4}, {status, "status", 4}, {flip, "flip", 4}, {bb, "bb", 4},
+                          {intr_out, "intr_out", 4}, {extr_out, "extr_out", 4}, {verts_rel, "verts_rel", 4},
+                          {joints_rel, "joints_rel", 4}, {orient_rel, "orient_rel", 4}, {trans_rel, "trans_rel", 4}, {j2d, "j2d", 4},
+                          {j2d_crop, "j2d_crop", 4}, {pose_rotmat, "pose_rotmat", 4}};
+    if (int rc = apg_check_ptrs(f, in, 9)) return rc;
+    if (int rc = apg_check_ptrs(f, out, 14)) return rc;
     if (n < 1 || n > MAX_N) return apg_fail(APG_EINVAL, f + "n must be in 1 .. " + std::to_string(MAX_N));
     if (V < 1 || V > MAX_V) return apg_fail(APG_EINVAL, f + "V must be in 1 .. " + std::to_string(MAX_V));
     if (J < 1 || J > MAX_J) return apg_fail(APG_EINVAL, f + "J must be in 1 .. " + std::to_string(MAX_J));
@@ -258,8 +237,8 @@ extern "C" int apg_synth_crops(int n, int Hc, int Wc, int bgr, const unsigned ch
                                float* im, float* scale, int* pad, void* stream) {
     const std::string f = "apg_synth_crops: ";
     if (!frames) return apg_fail(APG_EINVAL, f + "frames is NULL");
-    const Ptr ps[] = {{crops, "crops"}, {flip, "flip"}, {im, "im"}, {scale, "scale"}, {pad, "pad"}};
-    if (int rc = check_ptrs(f, ps, 5)) return rc;
+    const ApgPtr ps[] = {{crops, "crops", 4}, {flip, "flip", 4}, {im, "im", 4}, {scale, "scale", 4}, {pad, "pad", 4}};
+    if (int rc = apg_check_ptrs(f, ps, 5)) return rc;
     if (n < 1 || n > MAX_N) return apg_fail(APG_EINVAL, f + "n must be in 1 .. " + std::to_string(MAX_N));
     if (Hc < 1 || Hc > MAX_SIDE) return apg_fail(APG_EINVAL, f + "Hc must be in 1 .. " + std::to_string(MAX_SIDE));
     if (Wc < 1 || Wc > MAX_SIDE) return apg_fail(APG_EINVAL, f + "Wc must be in 1 .. " + std::to_string(MAX_SIDE));

@@ -18,6 +18,7 @@ import operator
 
 import torch
 
+from . import _args as A
 from . import _native as N
 from . import _native_grad as G
 
@@ -49,11 +50,7 @@ class RealSequenceBatches:
     """
 
     def __init__(self, detections, intr, device=None, first_cam=0, agreement_px=AGREEMENT_PX, border=BORDER):
-        self.device = torch.device(device) if device is not None else torch.device("cuda")
-        if self.device.type != "cuda":
-            raise RuntimeError("%s: device must be a CUDA (ROCm) device, got %s; there is no CPU path" % (NAME, self.device))
-        if self.device.index is None:                        # (a given index constructs without a GPU)
-            self.device = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        self.device = A.cuda_device(NAME, device)
         if first_cam not in (0, 1):
             raise ValueError("%s: first_cam must be 0 or 1, got %r" % (NAME, first_cam))
         if not isinstance(agreement_px, (int, float)) or not 0 <= agreement_px < float("inf"):
@@ -61,18 +58,13 @@ class RealSequenceBatches:
         if not isinstance(border, int) or isinstance(border, bool) or border < 0:
             raise ValueError("%s: border must be a whole number of pixels that is not negative, got %r" % (NAME, border))
         for t, nd, tail, name, what in ((detections, 5, (2, 24, 3), "detections", "(2, L, 2, 24, 3)"), (intr, 3, (3, 3), "intr", "(2, 3, 3)")):
-            if not torch.is_tensor(t):
-                raise RuntimeError("%s: %s must be a tensor, got %s" % (NAME, name, type(t).__name__))
+            A.is_tensor(NAME, t, name)
             if not t.is_floating_point():
                 raise RuntimeError("%s: %s must be a floating-point tensor, got %s" % (NAME, name, t.dtype))
             if t.dim() != nd or t.shape[0] != 2 or tuple(t.shape[-len(tail):]) != tail or t.shape[1] < 1:
                 raise RuntimeError("%s: %s must be %s, got %s" % (NAME, name, what, tuple(t.shape)))
-        if detections.dtype != torch.float32:
-            raise RuntimeError("%s: detections must be float32 (nothing is cast), got %s" % (NAME, detections.dtype))
-        if not detections.is_cuda:
-            raise RuntimeError("%s: detections lives on %s; it must be a CUDA (ROCm) tensor, there is no CPU path" % (NAME, detections.device))
-        if detections.device != self.device:
-            raise RuntimeError("%s: detections lives on %s, the batches on %s" % (NAME, detections.device, self.device))
+        A.exact_tensor(NAME, detections, torch.float32, "detections")
+        A.lives_on(NAME, detections, self.device, "detections", "the batches")
         self.first_cam, self.agreement_px, self.border = int(first_cam), float(agreement_px), border
         self.detections = detections.detach().contiguous()
         self.L = int(detections.shape[1])
@@ -86,8 +78,7 @@ class RealSequenceBatches:
     def _frames(self, frames0, frames1, start):
         fs = (frames0, frames1)
         for v, t in enumerate(fs):
-            if not torch.is_tensor(t):
-                raise RuntimeError("%s: frames%d must be a tensor, got %s" % (NAME, v, type(t).__name__))
+            A.is_tensor(NAME, t, "frames%d" % v)
             if t.dtype != torch.uint8:
                 raise RuntimeError("%s: frames%d must be uint8, got %s" % (NAME, v, t.dtype))
             if t.dim() != 4 or t.shape[3] != 3 or min(t.shape[:3]) < 1:
@@ -104,10 +95,7 @@ class RealSequenceBatches:
             raise RuntimeError("%s: frames [start, start + n) must lie in the sequence's %d frames, got start = %r, n = %d" %
                                (NAME, self.L, start, n))
         for v, t in enumerate(fs):
-            if not t.is_cuda:
-                raise RuntimeError("%s: frames%d lives on %s; it must be a CUDA (ROCm) tensor, there is no CPU path" % (NAME, v, t.device))
-            if t.device != self.device:
-                raise RuntimeError("%s: frames%d lives on %s, the batches on %s" % (NAME, v, t.device, self.device))
+            A.lives_on(NAME, t, self.device, "frames%d" % v, "the batches")
         return [t.contiguous() for t in fs], n, start
 
     def batch(self, frames0, frames1, start, bgr=True):

@@ -20,6 +20,7 @@ iteration 0.  Each window has a shape vector of its own: `beta` is (n_chunks, 10
 """
 import torch
 
+from . import _args as A
 from . import _native as N
 from . import _native_grad as G
 from .fitting import SWITCH_ITER, AirPosePlusFitter
@@ -76,11 +77,7 @@ class AirPosePlusSequence:
     """
 
     def __init__(self, vposer, body, device=None, chunk=2000):
-        self.device = torch.device(device) if device is not None else torch.device("cuda")
-        if self.device.type != "cuda":
-            raise RuntimeError("%s: device must be a CUDA (ROCm) device, got %s; there is no CPU path" % (NAME, self.device))
-        if self.device.index is None:                        # (a given index constructs without a GPU)
-            self.device = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        self.device = A.cuda_device(NAME, device)
         windows(1, chunk)
         self.chunk, self.body = int(chunk), body
         sd = _strip(vposer)
@@ -120,18 +117,14 @@ class AirPosePlusSequence:
         """items: (tensor, shape with None = any extent, name) -> fp32 contiguous tensors.  Every item's type and shape are looked at
         first, then every item's device; anything else is refused by name"""
         for t, shape, name in items:
-            if not torch.is_tensor(t):
-                raise RuntimeError("%s: %s must be a tensor, got %s" % (NAME, name, type(t).__name__))
+            A.is_tensor(NAME, t, name)
             if not t.is_floating_point():
                 raise RuntimeError("%s: %s must be a floating-point tensor, got %s" % (NAME, name, t.dtype))
             if t.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, t.shape)):
                 raise RuntimeError("%s: %s must be (%s), got %s" % (NAME, name, ", ".join("L" if s is None else str(s) for s in shape),
                                                                     tuple(t.shape)))
         for t, _, name in items:
-            if not t.is_cuda:
-                raise RuntimeError("%s: %s lives on %s; it must be a CUDA (ROCm) tensor, there is no CPU path" % (NAME, name, t.device))
-            if t.device != self.device:
-                raise RuntimeError("%s: %s lives on %s, the fitter on %s" % (NAME, name, t.device, self.device))
+            A.lives_on(NAME, t, self.device, name, "the fitter")
         return [N.f32c(t.detach()) for t, _, _ in items]
 
     # ---------------------------------------------------------------------------------------- the three steps

@@ -14,10 +14,9 @@ stateless (Philox4x32-10 keyed by seed, counted by dataset index, epoch and came
 on the batch it arrives in, and they are not numpy's: the reference's np.random stream is not reproduced.  Parity of the images with
 cv2's resize is UNPINNED, as for ap_preprocess_crops.  There is no CPU path and no fallback: a missing library is an error.
 """
-import operator
-
 import torch
 
+from . import _args as A
 from . import _native_grad as G
 from .pipeline import FOCAL_LENGTH
 from .smplx import SMPLX
@@ -71,11 +70,7 @@ class SyntheticBatches:
 
     def __init__(self, smplx_models, device=None, frame_size=(1080, 1920), margin=200, focal_length=FOCAL_LENGTH, seed=0,
                  jitter=True, shuffle=True):
-        self.device = torch.device(device) if device is not None else torch.device("cuda")
-        if self.device.type != "cuda":
-            raise RuntimeError("%s: device must be a CUDA (ROCm) device, got %s; there is no CPU path" % (NAME, self.device))
-        if self.device.index is None:                        # (a given index constructs without a GPU)
-            self.device = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        self.device = A.cuda_device(NAME, device)
         if not isinstance(smplx_models, dict) or not smplx_models:
             raise TypeError("%s: smplx_models must be a non-empty dict of %s -> airpose_amd.SMPLX" % (NAME, " / ".join(GENDERS)))
         for g, m in smplx_models.items():
@@ -110,10 +105,7 @@ class SyntheticBatches:
         ten["frames"] = (frames, None, torch.uint8, "(2, n, Hc, Wc, 3)")
         ten["index"] = (index, None, torch.int32, "(n,)")
         for name, (t, _, dt, what) in ten.items():
-            if not torch.is_tensor(t):
-                raise RuntimeError("%s: %s must be a tensor, got %s" % (NAME, name, type(t).__name__))
-            if t.dtype != dt:
-                raise RuntimeError("%s: %s must be %s (nothing is cast), got %s" % (NAME, name, str(dt).replace("torch.", ""), t.dtype))
+            A.exact_tensor(NAME, t, dt, name)
         bb = records["bb"]
         n = int(bb.shape[0]) if bb.dim() else 0
         for k, (what, tail, _) in FIELDS.items():
@@ -132,12 +124,7 @@ class SyntheticBatches:
         genders = records["smplgender"]
         if not isinstance(genders, (list, tuple)) or len(genders) != n or not all(isinstance(g, str) for g in genders):
             raise RuntimeError("%s: records['smplgender'] must be a host list of n = %d strings" % (NAME, n))
-        try:
-            epoch = operator.index(epoch)
-        except TypeError:
-            raise RuntimeError("%s: epoch must be an integer, got %s" % (NAME, type(epoch).__name__)) from None
-        if not 0 <= epoch < 2 ** 31:
-            raise RuntimeError("%s: epoch must be in 0 .. 2^31 - 1, got %r" % (NAME, epoch))
+        epoch = A.epoch_index(NAME, epoch)
         if origin not in G.SYNTH_ORIGINS:
             raise RuntimeError("%s: origin must be 'region' or 'frame', got %r" % (NAME, origin))
         rows = {}
@@ -148,10 +135,7 @@ class SyntheticBatches:
             if g not in self.models:
                 raise RuntimeError("%s: sample %d is %s and smplx_models has no %r model" % (NAME, rows[g][0], g, g))
         for name, (t, _, _, _) in ten.items():
-            if not t.is_cuda:
-                raise RuntimeError("%s: %s lives on %s; it must be a CUDA (ROCm) tensor, there is no CPU path" % (NAME, name, t.device))
-            if t.device != self.device:
-                raise RuntimeError("%s: %s lives on %s, the batches on %s" % (NAME, name, t.device, self.device))
+            A.lives_on(NAME, t, self.device, name, "the batches")
         return n, epoch, rows
 
     def _constants(self):

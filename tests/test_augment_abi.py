@@ -3,10 +3,10 @@ bound for apg_augment_*, the ABI number stays 2, every refusal of the two entrie
 made-up addresses that are never dereferenced -- and names its argument, no kernel of the new source holds packed fp32 math, the
 oracle and the restatement of augment_util.py hold on their own, and CropAugment refuses its arguments by name."""
 import ctypes
+import json
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -134,21 +134,21 @@ def test_crops_refusals_happen_on_the_host_and_name_the_argument(over, names):
     assert msg.startswith("apg_augment_crops: ") and names in msg[len("apg_augment_crops: "):], msg
 
 
-def test_no_packed_fp32_math_in_any_kernel_of_the_new_source():
-    """the source is outside GRAD_SRCS (csrc/Makefile says why), so the committed scan does not see it: this one does"""
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    try:
-        import packed_math_scan
-    finally:
-        sys.path.pop(0)
-    rows = packed_math_scan.scan_sources(["augment"])
+def test_the_source_is_one_of_grad_srcs_and_the_committed_scan_lists_its_kernels():
+    """augment.hip is a source like the others: tests/test_packed_math_scan.py holds the committed rows below to the live scan, and
+    the source, one of its GUARDED, to "no packed fp32 math with the flag, some without it" """
+    text = open(os.path.join(REPO, "airpose_amd", "csrc", "Makefile")).read()
+    grad = re.search(r"^GRAD_SRCS\s*=\s*(.*)$", text, re.M).group(1).split()
+    assert "augment.hip" in grad and "AUG_SRCS" not in text
+    with open(os.path.join(REPO, "tests", "packed_math_scan.json")) as f:
+        d = json.load(f)
+    rows = [dict(zip(d["columns"], r)) for r in d["kernels"] if r[0] == "augment.hip"]
     assert sorted(r["kernel"] for r in rows) == ["augment_crops_kernel", "augment_draw_kernel"]
     for r in rows:
         assert r["flags"] == "-ffp-contract=off -fno-slp-vectorize" and r["packed"] == 0 and r["op_sel"] == 0, r
     assert max(r["ds_reads"] for r in rows) > 0              # (the scan did read the tile kernel's body)
-    text = open(os.path.join(REPO, "airpose_amd", "csrc", "Makefile")).read()
-    grad = re.search(r"^GRAD_SRCS\s*=\s*(.*)$", text, re.M).group(1).split()
-    assert "augment.hip" not in grad and re.search(r"^AUG_SRCS\s*=\s*augment\.hip$", text, re.M) and "$(AUG_SRCS:.hip=.o)" in text
+    import test_packed_math_scan                             # (beside this file, as augment_util is)
+    assert "augment" in test_packed_math_scan.GUARDED
 
 
 # ------------------------------------------------------------------------------------------------ the oracle, on the CPU

@@ -2,12 +2,12 @@
 
 csrc/Makefile (FLAGS_smplx) records a wrong-answer hazard that was never root-caused: where hipcc SLP-vectorises fp32 dot products
 on LDS operands into v_pk_fma_f32 with op_sel, smplx_prep_kernel returned wrong joints in lanes 48-63 while waves of another kernel
-shared the SIMD, never alone.  The cure is -fno-slp-vectorize on the six GUARDED sources.  tools/packed_math_scan.py compiles every
+shared the SIMD, never alone.  The cure is -fno-slp-vectorize on the seven GUARDED sources.  tools/packed_math_scan.py compiles every
 kernel source device-only with its Makefile flags and counts, per kernel, the v_pk_{fma,mul,add}_f32 instructions, those with
 op_sel, and the LDS reads; tests/packed_math_scan.json is its output for this tree (python tools/packed_math_scan.py --write).
 
 What the tests hold
-  * the list is the scan of THIS tree: live, for every source outside the trunk's 16-bit set (20 sources, a few seconds of hipcc),
+  * the list is the scan of THIS tree: live, for every source outside the trunk's 16-bit set (21 sources, a few seconds of hipcc),
     kernel by kernel and count by count; for the trunk's sources by their flags;
   * the guarded sources have no packed fp32 math with their flag, and the scan does see packed math in them without it (live: the
     detector is not blind, and the flag is what removes it) -- dropping a flag fails here, on the CPU machine;
@@ -24,8 +24,8 @@ The list of this tree (kernels with the signature; packed / with op_sel / LDS re
   render.hip         render_large 17 / 1 / 9
   packed math without the signature (no op_sel, or no LDS read): optim.hip adam_kernel 196 / 92 / 0 and 200 / 96 / 0, preprocess_kernel
   6 / 6 / 0, the other render kernels, rot6d_bwd, fit_adam, loss_grad.hip, regressor.hip, and every conv / bottleneck kernel of the
-  trunk (up to 448 per kernel, none with op_sel).  None at all: head_mlp, head_grad, head_local_grad, eval_align and the six guarded
-  sources; without their flag those have 1274 (smplx), 243 (smplx_bwd), 115 (loss_real_grad), 154 (seq_fit), 8 and 53.
+  trunk (up to 448 per kernel, none with op_sel).  None at all: head_mlp, head_grad, head_local_grad, eval_align and the seven guarded
+  sources; without their flag those have 1274 (smplx), 243 (smplx_bwd), 115 (loss_real_grad), 154 (seq_fit), 8, 53 and 282.
 
 NOT HELD HERE: whether a SUSPECT kernel gives other bits beside a co-running kernel.  That takes a GPU test which runs each entry
 while a second stream is busy.  A first version of that test ended in a GPU memory-access fault on its first run, its cause was not
@@ -46,8 +46,8 @@ REPO = os.path.dirname(HERE)
 sys.path.insert(0, os.path.join(REPO, "tools"))
 import packed_math_scan as S  # noqa: E402
 
-# -fno-slp-vectorize because of the hazard (Makefile); seq_batch and synth_batch carry it beside -ffp-contract=off
-GUARDED = ("smplx", "smplx_bwd", "loss_real_grad", "seq_fit", "seq_batch", "synth_batch")
+# -fno-slp-vectorize because of the hazard (Makefile); seq_batch, synth_batch and augment carry it beside -ffp-contract=off
+GUARDED = ("smplx", "smplx_bwd", "loss_real_grad", "seq_fit", "seq_batch", "synth_batch", "augment")
 SUSPECT = {
     ("fitting.hip", "fit_decode_kernel"), ("fitting.hip", "fit_backprop_adam_kernel"), ("fitting.hip", "fit_frame_kernel"),
     ("eval_metrics.hip", "eval_main_kernel"),
