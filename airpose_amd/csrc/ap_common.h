@@ -125,6 +125,16 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
     asm(AP_CVTPK_ASM " %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
     return r;
 }
+// ReLU on two packed 16-bit values: as signed 16-bit integers negative values (sign bit set, -0 included) are below zero, positive
+// ones keep their order -- max(x, 0) per half; rounding is monotonic and keeps the sign, so relu-then-round == round-then-relu
+__device__ __forceinline__ uint32_t ap_relu_pk(uint32_t u) {
+    uint32_t r;
+    asm("v_pk_max_i16 %0, %1, 0" : "=v"(r) : "v"(u));
+    return r;
+}
+// (conv_slab.hip and conv_pipe.hip apply the same instruction in place to the halves of a uint2, asm("v_pk_max_i16 %0, %0, 0" :
+// "+v"(o.x)): that form stays where it is -- through this function, or through one that takes the element by reference, the
+// compiler allocates those epilogues differently and the whole kernel's schedule moves)
 __device__ __forceinline__ void unpack_bf16x2(uint32_t u, float& lo, float& hi) {
 #ifdef AP_F16
     lo = bf16_to_f32((bf16_t)(u & 0xffffu));

@@ -40,7 +40,7 @@ constexpr int BI_SLOTS_TOTAL = BI_STEPS12 + 32;              // + conv3: 64 step
 constexpr size_t BI_WAVE_BYTES = (size_t)BI_SLOTS_TOTAL * 4096;   // 557 056 per wave, 2 228 224 per block
 static_assert(BI_XS + 2 * BI_XS_STAGE <= 241 * 512, "the staging ring stays clear of the zero rows");
 
-#include "bi_helpers.inc"
+#include "conv_prims.inc"
 
 // weight stream: wave w -> [conv1: 32 steps][conv2: 72 steps (64-channel chunk, tap, K half)] of 4 fragments (64 rows) + [conv3: 8 chunks x 8 steps] of
 // 2 fragments (32 rows); fragment = [lane 64][8 K values]: row lane & 15, K columns 8 (lane >> 4) .. + 7 of the step's 32
@@ -54,7 +54,7 @@ __global__ void __launch_bounds__(256) blk_img_pack_kernel(const bf16_t* __restr
     const bf16_t* src;
     if (p < BI_STEPS12 * 256) {
         const int step = p >> 8, f = (p >> 6) & 3, lane = p & 63;
-        const int ch = w * 64 + bi_row_channel(f * 16 + (lane & 15));
+        const int ch = w * 64 + ap_row_channel(f * 16 + (lane & 15));
         if (step < 32) src = w1 + (size_t)ch * BI_C + step * 32 + (lane >> 4) * 8;
         else {                                               // conv2 in the slab kernel's K order: 64-channel chunk, tap, K half
             const int s2 = step - 32, c64 = s2 / 18, tap = (s2 % 18) >> 1, ks = s2 & 1;
@@ -63,7 +63,7 @@ __global__ void __launch_bounds__(256) blk_img_pack_kernel(const bf16_t* __restr
     } else {
         const int q = p - BI_STEPS12 * 256, step = q >> 7, f = (q >> 6) & 1, lane = q & 63;
         const int chunk = step >> 3, ks = step & 7;
-        const int ch = chunk * 128 + w * 32 + bi_row_channel(f * 16 + (lane & 15));     // (f < 2: channels 0 .. 31 of the tile)
+        const int ch = chunk * 128 + w * 32 + ap_row_channel(f * 16 + (lane & 15));     // (f < 2: channels 0 .. 31 of the tile)
         src = w3 + (size_t)ch * BI_P + ks * 32 + (lane >> 4) * 8;
     }
     *(u32x4*)(dst + idx * 16) = *(const u32x4*)src;
@@ -99,7 +99,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     // zero rows (slots 0 .. 16 and 241 .. 257): written once, never touched again (the staging ring lies between them)
     for (int idx = tid; idx < 34 * 32; idx += 256) {
         const int s = idx >> 5, c = idx & 31, u = s < 17 ? s : 241 + (s - 17);
-        bi_sts(smem, u * 512 + c * 16, u32x4{0u, 0u, 0u, 0u});
+        ap_lds_assign(smem, u * 512 + c * 16, u32x4{0u, 0u, 0u, 0u});
     }
 
     const unsigned char* const xg = (const unsigned char*)a.x;
@@ -118,8 +118,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     u32x4 ar[4][4];
     auto refill = [&](auto SL, u32x4 (&r)[4][4]) __attribute__((always_inline)) {           // ring slot SL <- the next piece of the stream
         constexpr int sl = decltype(SL)::value;
-        bi_gld<0>(r[sl][0], wlane, wp); bi_gld<1024>(r[sl][1], wlane, wp);
-        bi_gld<2048>(r[sl][2], wlane, wp); bi_gld<3072>(r[sl][3], wlane, wp);
+        ap_gld_sbase_pad<0>(r[sl][0], wlane, wp); ap_gld_sbase_pad<1024>(r[sl][1], wlane, wp);
+        ap_gld_sbase_pad<2048>(r[sl][2], wlane, wp); ap_gld_sbase_pad<3072>(r[sl][3], wlane, wp);
         wp += 4096;
         if (++wcnt == BI_SLOTS_TOTAL) { wcnt = 0; wp = wsb; }
     };
@@ -165,19 +165,19 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             const unsigned char* sp = c < 16 ? ximg + c * 128 : xg;
             const uint32_t vo = c < 16 ? xoff : 0u;
             const uint32_t st = c < 16 ? 2 * BI_HW * BI_C * 2 : 0;
-            bi_gld<0>(r[0], vo, sp); bi_gld<0>(r[1], vo, sp + st); bi_gld<0>(r[2], vo, sp + 2 * st); bi_gld<0>(r[3], vo, sp + 3 * st);
-            bi_gld<0>(r[4], vo, sp + 4 * st); bi_gld<0>(r[5], vo, sp + 5 * st); bi_gld<0>(r[6], vo, sp + 6 * st);
+            ap_gld_sbase_pad<0>(r[0], vo, sp); ap_gld_sbase_pad<0>(r[1], vo, sp + st); ap_gld_sbase_pad<0>(r[2], vo, sp + 2 * st); ap_gld_sbase_pad<0>(r[3], vo, sp + 3 * st);
+            ap_gld_sbase_pad<0>(r[4], vo, sp + 4 * st); ap_gld_sbase_pad<0>(r[5], vo, sp + 5 * st); ap_gld_sbase_pad<0>(r[6], vo, sp + 6 * st);
         };
         auto xstore = [&](u32x4 (&r)[7], int stage) __attribute__((always_inline)) {
 #pragma unroll
             for (int j = 0; j < 7; ++j) {
                 asm volatile("" : "+v"(r[j]));
-                bi_sts(smem, xs_w + stage * BI_XS_STAGE + j * (32 * 128), r[j]);
+                ap_lds_assign(smem, xs_w + stage * BI_XS_STAGE + j * (32 * 128), r[j]);
             }
         };
         xload(xa, 0);
         xload(xb, 1);
-        bi_wait_vm<7>();                                     // chunk 0 (and everything older: the ring, the last image's stores)
+        ap_wait_vm<7>();                                     // chunk 0 (and everything older: the ring, the last image's stores)
         __syncthreads();                                     // every wave is done with the image region (last image's conv3)
         xstore(xa, 0);
         xload(xa, 2);
@@ -187,15 +187,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             constexpr int stage = decltype(STAGE)::value, sl0 = decltype(SL0)::value;
             constexpr bool first = decltype(FIRST)::value != 0;
             const uint32_t ra = xs_r + stage * BI_XS_STAGE, rb = ra ^ 64u;
-            bi_pipe<28, 7>(b,
-                [&](auto I, u32x4& d) __attribute__((always_inline)) { constexpr int n = decltype(I)::value, ks = n / 14, g = n % 14; bi_ldsr<g * 2048>(d, ks ? rb : ra); },
+            ap_frag_pipe<28, 7>(b,
+                [&](auto I, u32x4& d) __attribute__((always_inline)) { constexpr int n = decltype(I)::value, ks = n / 14, g = n % 14; ap_lds_read_to<g * 2048>(d, ks ? rb : ra); },
                 [&](auto I, u32x4& d) __attribute__((always_inline)) {
                     constexpr int n = decltype(I)::value, ks = n / 14, g = n % 14, sl = sl0 + ks;
-                    if constexpr (g == 0 && !first) bi_wait_vm<26>();
+                    if constexpr (g == 0 && !first) ap_wait_vm<26>();
 #pragma unroll
                     for (int f = 0; f < 4; ++f) {
-                        if constexpr (first && stage == 0 && ks == 0) bi_mma0(ac[f][g], r[sl][f], d);
-                        else bi_mma(ac[f][g], r[sl][f], d);
+                        if constexpr (first && stage == 0 && ks == 0) ap_mfma_zero_a(ac[f][g], r[sl][f], d);
+                        else ap_mfma_acc_a(ac[f][g], r[sl][f], d);
                     }
                     if constexpr (g == 13) refill(std::integral_constant<int, sl>{}, r);
                 });
@@ -203,12 +203,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         auto c1_iter = [&](int c, auto FIRST) __attribute__((always_inline)) {
             constexpr bool first = decltype(FIRST)::value != 0;
             // chunk c from stage 0; chunk c + 1 -> stage 1 (free since the barrier that ended chunk c - 1); then chunk c + 3 requested
-            bi_wait_vm<(first ? 7 : 23)>();
+            ap_wait_vm<(first ? 7 : 23)>();
             xstore(xb, 1);
             xload(xb, c + 3);
             c1_pair(I0{}, I0{}, FIRST, bf, ar, acc);
             __syncthreads();
-            bi_wait_vm<(first ? 15 : 23)>();
+            ap_wait_vm<(first ? 15 : 23)>();
             if (c + 2 < 16) xstore(xa, 0);
             xload(xa, c + 4);
             c1_pair(I1{}, I2{}, I0{}, bf, ar, acc);
@@ -221,12 +221,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         // The staging loads of the last iterations fetch nothing that is used (chunks 16 .. 18 do not exist: they keep the queue
         // uniform).  Their destinations must nevertheless stay allocated until they have landed: a register the compiler
         // believes dead is handed to the next value, and the late load then overwrites it (seen: one output row wrong now and then).
-        bi_wait_vm<8>();                                     // behind the last staging load: the ring loads of the last two K steps
+        ap_wait_vm<8>();                                     // behind the last staging load: the ring loads of the last two K steps
 #pragma unroll
         for (int j = 0; j < 7; ++j) asm volatile("" : "+v"(xa[j]), "+v"(xb[j]));
         BISTAMP(3);
-        bi_settle28(acc[0], acc[1]);                         // the last MFMA results settle before VALU reads them
-        bi_settle28(acc[2], acc[3]);
+        ap_settle(acc[0], acc[1]);                         // the last MFMA results settle before VALU reads them
+        ap_settle(acc[2], acc[3]);
         // t1 = relu(bn1(.)) -> image region (every wave is past the last barrier: nobody reads the staging ring any more)
         auto to_lds = [&](const float* sc, const float* sh) __attribute__((always_inline)) {
             sfor<0, 2>([&](auto Q) __attribute__((always_inline)) {
@@ -236,9 +236,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
                 const f32x4 h0 = *(const f32x4*)(sh + ch), h1 = *(const f32x4*)(sh + ch + 4);
 #pragma unroll
                 for (int g = 0; g < 14; ++g) {
-                    u32x4 o = bi_bn8(acc[2 * q][g], acc[2 * q + 1][g], s0, s1, h0, h1, nullptr, rng);
+                    u32x4 o = ap_bn8(acc[2 * q][g], acc[2 * q + 1][g], s0, s1, h0, h1, nullptr, rng);
                     if (li >= BI_HW) o = u32x4{0u, 0u, 0u, 0u};          // the zero columns = horizontal padding of conv2
-                    bi_sts(smem, twr(g, wave * 8 + q * 4 + kq), o);
+                    ap_lds_assign(smem, twr(g, wave * 8 + q * 4 + kq), o);
                 }
             });
         };
@@ -248,8 +248,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 #pragma unroll
             for (int g = 0; g < 14; ++g) acc[f][g] = f32x4{0.f, 0.f, 0.f, 0.f};
         __syncthreads();
-        bi_settle28(acc[0], acc[1]);                         // (v_accvgpr_write -> MFMA source: the same pad, generously)
-        bi_settle28(acc[2], acc[3]);
+        ap_settle(acc[0], acc[1]);                         // (v_accvgpr_write -> MFMA source: the same pad, generously)
+        ap_settle(acc[2], acc[3]);
         BISTAMP(4);
 
         // ================================================================ conv2: 4 channel chunks x 9 taps x 2 K halves, no barrier
@@ -261,24 +261,24 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { tl[d][j] = tb + tpos(d - 1, j); th[d][j] = tl[d][j] + 65536u; }
             }
-            bi_pipe<480, 7>(bf,
+            ap_frag_pipe<480, 7>(bf,
                 [&](auto I, u32x4& d) __attribute__((always_inline)) {
                     constexpr BiP2 q = bi_p2(decltype(I)::value);
                     constexpr int R = q.g + q.dr + 1, j = 2 * q.cpar + q.ks;
-                    bi_ldsr<(R & 7) * 8192>(d, R < 8 ? tl[q.dc + 1][j] : th[q.dc + 1][j]);
+                    ap_lds_read_to<(R & 7) * 8192>(d, R < 8 ? tl[q.dc + 1][j] : th[q.dc + 1][j]);
                 },
                 [&](auto I, u32x4& d) __attribute__((always_inline)) {
                     constexpr BiP2 q = bi_p2(decltype(I)::value);
                     constexpr int sl = q.step & 3;
-                    if constexpr (q.gi == 0) bi_wait_vm<12>();
+                    if constexpr (q.gi == 0) ap_wait_vm<12>();
 #pragma unroll
-                    for (int f = 0; f < 4; ++f) bi_mma(acc[f][q.g], ar[sl][f], d);
+                    for (int f = 0; f < 4; ++f) ap_mfma_acc_a(acc[f][q.g], ar[sl][f], d);
                     if constexpr (q.gi == q.ng - 1) refill(std::integral_constant<int, sl>{}, ar);
                 });
         }
         BISTAMP(5);
-        bi_settle28(acc[0], acc[1]);
-        bi_settle28(acc[2], acc[3]);
+        ap_settle(acc[0], acc[1]);
+        ap_settle(acc[2], acc[3]);
         __syncthreads();                                     // every wave is done reading t1
         to_lds(bs2, bh2);
         __syncthreads();
@@ -298,45 +298,45 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             auto chunk_fn = [&](int chunk, auto FIRSTC) __attribute__((always_inline)) {
                 constexpr bool firstc = decltype(FIRSTC)::value != 0;
                 const unsigned char* isb = ximg + chunk * 256;
-                bi_gld<0>(idr[0], idoff, isb); bi_gld<0>(idr[1], idoff, isb + 28672); bi_gld<0>(idr[2], idoff, isb + 2 * 28672);
-                bi_gld<0>(idr[3], idoff, isb + 3 * 28672); bi_gld<0>(idr[4], idoff, isb + 4 * 28672); bi_gld<0>(idr[5], idoff, isb + 5 * 28672);
-                bi_gld<0>(idr[6], idoff, isb + 6 * 28672); bi_gld<0>(idr[7], idoff, isb + 7 * 28672); bi_gld<0>(idr[8], idoff, isb + 8 * 28672);
-                bi_gld<0>(idr[9], idoff, isb + 9 * 28672); bi_gld<0>(idr[10], idoff, isb + 10 * 28672); bi_gld<0>(idr[11], idoff, isb + 11 * 28672);
-                bi_gld<0>(idr[12], idoff, isb + 12 * 28672); bi_gld<0>(idr[13], idoff, isb + 13 * 28672);
-                bi_gld<0>(bnr[0], (uint32_t)kq * 32u, bs3 + chunk * 512); bi_gld<16>(bnr[1], (uint32_t)kq * 32u, bs3 + chunk * 512);
-                bi_gld<0>(bnr[2], (uint32_t)kq * 32u, bh3 + chunk * 512); bi_gld<16>(bnr[3], (uint32_t)kq * 32u, bh3 + chunk * 512);
+                ap_gld_sbase_pad<0>(idr[0], idoff, isb); ap_gld_sbase_pad<0>(idr[1], idoff, isb + 28672); ap_gld_sbase_pad<0>(idr[2], idoff, isb + 2 * 28672);
+                ap_gld_sbase_pad<0>(idr[3], idoff, isb + 3 * 28672); ap_gld_sbase_pad<0>(idr[4], idoff, isb + 4 * 28672); ap_gld_sbase_pad<0>(idr[5], idoff, isb + 5 * 28672);
+                ap_gld_sbase_pad<0>(idr[6], idoff, isb + 6 * 28672); ap_gld_sbase_pad<0>(idr[7], idoff, isb + 7 * 28672); ap_gld_sbase_pad<0>(idr[8], idoff, isb + 8 * 28672);
+                ap_gld_sbase_pad<0>(idr[9], idoff, isb + 9 * 28672); ap_gld_sbase_pad<0>(idr[10], idoff, isb + 10 * 28672); ap_gld_sbase_pad<0>(idr[11], idoff, isb + 11 * 28672);
+                ap_gld_sbase_pad<0>(idr[12], idoff, isb + 12 * 28672); ap_gld_sbase_pad<0>(idr[13], idoff, isb + 13 * 28672);
+                ap_gld_sbase_pad<0>(bnr[0], (uint32_t)kq * 32u, bs3 + chunk * 512); ap_gld_sbase_pad<16>(bnr[1], (uint32_t)kq * 32u, bs3 + chunk * 512);
+                ap_gld_sbase_pad<0>(bnr[2], (uint32_t)kq * 32u, bh3 + chunk * 512); ap_gld_sbase_pad<16>(bnr[3], (uint32_t)kq * 32u, bh3 + chunk * 512);
 #ifndef BI_LA3
 #define BI_LA3 7
 #endif
 #ifndef BI_STAUX
 #define BI_STAUX 0                                           // cache policy of the output stores (A/B): 2 = nt
 #endif
-                bi_pipe<112, BI_LA3>(bf,
+                ap_frag_pipe<112, BI_LA3>(bf,
                     [&](auto I, u32x4& d) __attribute__((always_inline)) {
                         constexpr int n = decltype(I)::value, ks = n / 14, g = n % 14, R = g + 1;
-                        bi_ldsr<(R & 7) * 8192 + (ks >> 2) * 256>(d, R < 8 ? tl[ks & 3] : th[ks & 3]);
+                        ap_lds_read_to<(R & 7) * 8192 + (ks >> 2) * 256>(d, R < 8 ? tl[ks & 3] : th[ks & 3]);
                     },
                     [&](auto I, u32x4& d) __attribute__((always_inline)) {
                         constexpr int n = decltype(I)::value, ks = n / 14, g = n % 14, sl = ks >> 1, fo = (ks & 1) * 2;
                         // slot sl was refilled one chunk ago: behind it 12 more ring loads, 14 stores, this chunk's 18 loads
-                        if constexpr (g == 0 && (ks & 1) == 0) bi_wait_vm<(firstc ? 30 : 44)>();
-                        if constexpr (ks == 0) { bi_mma0(acc[0][g], ar[sl][fo], d); bi_mma0(acc[1][g], ar[sl][fo + 1], d); }
-                        else { bi_mma(acc[0][g], ar[sl][fo], d); bi_mma(acc[1][g], ar[sl][fo + 1], d); }
+                        if constexpr (g == 0 && (ks & 1) == 0) ap_wait_vm<(firstc ? 30 : 44)>();
+                        if constexpr (ks == 0) { ap_mfma_zero_a(acc[0][g], ar[sl][fo], d); ap_mfma_zero_a(acc[1][g], ar[sl][fo + 1], d); }
+                        else { ap_mfma_acc_a(acc[0][g], ar[sl][fo], d); ap_mfma_acc_a(acc[1][g], ar[sl][fo + 1], d); }
                         if constexpr (g == 13 && (ks & 1)) refill(std::integral_constant<int, sl>{}, ar);
                     });
                 if (chunk == 1) BISTAMP(8);
-                bi_wait_vm<16>();                            // identity + BatchNorm rows (behind them: this chunk's 16 ring loads)
+                ap_wait_vm<16>();                            // identity + BatchNorm rows (behind them: this chunk's 16 ring loads)
                 if (chunk == 1) BISTAMP(9);
 #pragma unroll
                 for (int g = 0; g < 14; ++g) asm volatile("" : "+v"(idr[g]));
                 asm volatile("" : "+v"(bnr[0]), "+v"(bnr[1]), "+v"(bnr[2]), "+v"(bnr[3]));
-                bi_settle28(acc[0], acc[1]);
+                ap_settle(acc[0], acc[1]);
                 const f32x4 s0 = __builtin_bit_cast(f32x4, bnr[0]), s1 = __builtin_bit_cast(f32x4, bnr[1]);
                 const f32x4 h0 = __builtin_bit_cast(f32x4, bnr[2]), h1 = __builtin_bit_cast(f32x4, bnr[3]);
                 const uint32_t so = img_off + chunk * 256;
 #pragma unroll
                 for (int g = 0; g < 14; ++g) {
-                    const u32x4 o = bi_bn8(acc[0][g], acc[1][g], s0, s1, h0, h1, &idr[g], rng);
+                    const u32x4 o = ap_bn8(acc[0][g], acc[1][g], s0, s1, h0, h1, &idr[g], rng);
                     const uint32_t vo = li < BI_HW ? so + g * 28672 + idoff : 0xffffff00u;      // (junk columns: dropped by the range check)
                     __builtin_amdgcn_raw_buffer_store_b128(o, yrsrc, vo, 0, BI_STAUX);
                 }
@@ -345,7 +345,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 #define BI_EXP 0
 #endif
             if (BI_EXP & 1) { __syncthreads(); asm volatile("s_sleep 30" ::: "memory"); __syncthreads(); }
-            if (BI_EXP & 2) { bi_wait_vm<0>(); chunk_fn(0, I0{}); } else
+            if (BI_EXP & 2) { ap_wait_vm<0>(); chunk_fn(0, I0{}); } else
             chunk_fn(0, I1{});
             BISTAMP(7);
             for (int c = 1; c < 8; ++c) { chunk_fn(c, I0{}); if (c == 1) BISTAMP(10); }
@@ -355,7 +355,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         ++img_no;
 #endif
     }
-    bi_wait_vm<0>();                                         // (the ring ran ahead into the next image: nothing may land after the exit)
+    ap_wait_vm<0>();                                         // (the ring ran ahead into the next image: nothing may land after the exit)
 #pragma unroll
     for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(ar[j][0]), "+v"(ar[j][1]), "+v"(ar[j][2]), "+v"(ar[j][3]));
     // slots 14, 15 of a row are the zero columns: what those lanes compute (relu(shift), partial conv2 sums) is replaced by zeros in

@@ -33,9 +33,6 @@
 
 AP_NS_BEGIN
 
-#ifndef B2_SAFE
-#define B2_SAFE 0
-#endif
 // timing-only builds (results wrong): 1 no x loads after the prologue | 2 no stores | 4 no W3 DMA | 8 no MFMAs | 16 no epilogue math |
 // 32 every store is issued out of range (dropped: no write traffic) | 64 stores as 8 consecutive lanes per 128-byte line
 #ifndef B2_ABLATE
@@ -67,70 +64,13 @@ template <bool DS, bool TAIL = false> struct B2Map {
 };
 constexpr int T_S1 = 0, T_H1 = 256, T_S2 = 512, T_H2 = 768, T_S3 = 1024, T_H3 = 2048, T_S1N = 3072, T_H1N = 3584;
 
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(B2_SAFE ? 0 : N) : "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-template <int N> __device__ __forceinline__ void wait_lgkmcnt() {
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-template <int OFF> __device__ __forceinline__ u32x4 lds_read_b128(uint32_t addr) {
-    u32x4 r;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-    return r;
-}
-template <int OFF> __device__ __forceinline__ f32x4 lds_read_f32x4(uint32_t addr) {
-    f32x4 r;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-    return r;
-}
-template <int OFF> __device__ __forceinline__ void lds_write_b128(uint32_t addr, const u32x4& v) {
-    asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory");
-}
-template <int OFF> __device__ __forceinline__ u32x4 gload_b128(const unsigned char* p) {
-    u32x4 r;
-    asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(r) : "v"(p), "n"(OFF) : "memory");
-    return r;
-}
-// SGPR base + 32-bit lane offset (one VGPR per address instead of two; the launcher keeps every tensor below 4 GB)
-template <int OFF> __device__ __forceinline__ u32x4 gload_b128_s(uint32_t off, const unsigned char* base) {
-    u32x4 r;
-    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(r) : "v"(off), "s"(base), "n"(OFF) : "memory");
-    return r;
-}
-template <int OFF> __device__ __forceinline__ void gstore_b128_s(uint32_t off, unsigned char* base, const u32x4& v) {
-    asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3" ::"v"(off), "v"(v), "s"(base), "n"(OFF) : "memory");
-}
-template <int I, int N, typename F> __device__ __forceinline__ void sfor(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        sfor<I + 1, N>(f);
-    }
-}
+#include "conv_prims.inc"
+
 __device__ __forceinline__ void mm(f32x4& c, const u32x4& w, const u32x4& x) {
     if (B2_ABLATE & 8) asm volatile("" : "+v"(c) : "v"(w), "v"(x));
-    else c = ap_mfma16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c);
+    else c = ap_mfma_frag(w, x, c);
 }
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-__device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
-    uint32_t r;
-    asm(AP_CVTPK_ASM " %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ uint32_t relu_pk_bf16(uint32_t u) {
-    uint32_t r;
-    asm("v_pk_max_i16 %0, %1, 0" : "=v"(r) : "v"(u));
-    return r;
-}
-// channel (within its 64) of row rho of a 64-row weight tile: fragment f = rho >> 4, row i of it; lane group g4 of fragment
-// pair q = f >> 1 owns channels q*32 + g4*8 .. + 7 (conv_pair.hip: pr_row_channel)
-__host__ __device__ __forceinline__ int b2_row_channel(int rho) {
-    const int f = rho >> 4, i = rho & 15;
-    return (f >> 1) * 32 + (i >> 2) * 8 + (f & 1) * 4 + (i & 3);
-}
-// BN (+ identity) + ReLU + bf16 of the 8 consecutive channels a lane holds in fragments (2q, 2q+1): the expression of the
-// stand-alone kernels' epilogue (fma, add, max, round), two values per instruction
+// ap_bn8 (conv_prims.inc), or the timing-only stub
 __device__ __forceinline__ u32x4 bn8(const f32x4& lo, const f32x4& hi, const f32x4& s0, const f32x4& s1, const f32x4& h0,
                                      const f32x4& h1, const u32x4* res, uint32_t& rng) {
     if (B2_ABLATE & 16) {
@@ -138,27 +78,7 @@ __device__ __forceinline__ u32x4 bn8(const f32x4& lo, const f32x4& hi, const f32
         asm volatile("" : "+v"(o) : "v"(lo), "v"(hi), "v"(s0), "v"(s1), "v"(h0), "v"(h1));
         return o;
     }
-    f32x2 v0 = __builtin_elementwise_fma(lo.xy, s0.xy, h0.xy), v1 = __builtin_elementwise_fma(lo.zw, s0.zw, h0.zw);
-    f32x2 v2 = __builtin_elementwise_fma(hi.xy, s1.xy, h1.xy), v3 = __builtin_elementwise_fma(hi.zw, s1.zw, h1.zw);
-    if (res) {
-        const uint32_t r0 = (*res).x, r1 = (*res).y, r2 = (*res).z, r3 = (*res).w;
-#ifdef AP_F16
-        { float a_ = v0.x, b_ = v0.y; ap_res_add2(a_, b_, r0); v0 = f32x2{a_, b_}; }
-        { float a_ = v1.x, b_ = v1.y; ap_res_add2(a_, b_, r1); v1 = f32x2{a_, b_}; }
-        { float a_ = v2.x, b_ = v2.y; ap_res_add2(a_, b_, r2); v2 = f32x2{a_, b_}; }
-        { float a_ = v3.x, b_ = v3.y; ap_res_add2(a_, b_, r3); v3 = f32x2{a_, b_}; }
-#else
-        { float a_, b_; unpack_bf16x2(r0, a_, b_); v0 += f32x2{a_, b_}; }
-        { float a_, b_; unpack_bf16x2(r1, a_, b_); v1 += f32x2{a_, b_}; }
-        { float a_, b_; unpack_bf16x2(r2, a_, b_); v2 += f32x2{a_, b_}; }
-        { float a_, b_; unpack_bf16x2(r3, a_, b_); v3 += f32x2{a_, b_}; }
-#endif
-    }
-    u32x4 o;
-    o.x = relu_pk_bf16(cvt_pk_bf16(v0.x, v0.y)); o.y = relu_pk_bf16(cvt_pk_bf16(v1.x, v1.y));
-    o.z = relu_pk_bf16(cvt_pk_bf16(v2.x, v2.y)); o.w = relu_pk_bf16(cvt_pk_bf16(v3.x, v3.y));
-    ap_rng_note2(rng, o.x, o.y); ap_rng_note2(rng, o.z, o.w);   // fp16 range sentinel (ap_common.h)
-    return o;
+    return ap_bn8(lo, hi, s0, s1, h0, h1, res, rng);
 }
 
 template <bool DS, bool TAIL>
@@ -178,17 +98,17 @@ bneck2_kernel(const BneckArgs a) {
     uint32_t rng = 0u, rngq[2] = {0u, 0u};
 
     // ---------------------------------------------------------------- once per workgroup: W1, W2, BatchNorm tables -> LDS
-    // tile = 64 rows x 128 B, row rho = channel b2_row_channel(rho), 16-byte chunk c at position c ^ (rho & 7)
+    // tile = 64 rows x 128 B, row rho = channel ap_row_channel(rho), 16-byte chunk c at position c ^ (rho & 7)
     {
         const unsigned char* w1 = (const unsigned char*)a.w1;
         const unsigned char* w2 = (const unsigned char*)a.w2;
         for (int idx = tid; idx < CIN * 8; idx += 512) {
             const int kc = idx >> 9, rho = (idx >> 3) & 63, c = (idx & 7) ^ (rho & 7);
-            *(u32x4*)(smem + L_W1 + idx * 16) = *(const u32x4*)(w1 + ((size_t)b2_row_channel(rho) * CIN + kc * 64 + c * 8) * 2);
+            *(u32x4*)(smem + L_W1 + idx * 16) = *(const u32x4*)(w1 + ((size_t)ap_row_channel(rho) * CIN + kc * 64 + c * 8) * 2);
         }
         for (int idx = tid; idx < 4608; idx += 512) {
             const int tap = idx >> 9, rho = (idx >> 3) & 63, c = (idx & 7) ^ (rho & 7);
-            *(u32x4*)(smem + L_W2 + idx * 16) = *(const u32x4*)(w2 + ((size_t)b2_row_channel(rho) * 576 + tap * 64 + c * 8) * 2);
+            *(u32x4*)(smem + L_W2 + idx * 16) = *(const u32x4*)(w2 + ((size_t)ap_row_channel(rho) * 576 + tap * 64 + c * 8) * 2);
         }
         float* tb = (float*)(smem + L_TAB);
         if (tid < 64) {
@@ -201,7 +121,7 @@ bneck2_kernel(const BneckArgs a) {
     // W3 by LDS-DMA: chunk cc = channels cc*64 .. +63 (rows permuted); per 64-wide K half one 1-KB piece (8 rows) per wave
     const int prow = lane >> 3;
     const unsigned char* w3src =
-        (const unsigned char*)a.w3 + ((size_t)b2_row_channel(wave * 8 + prow) * K3 + (((lane & 7) ^ prow) * 8)) * 2;
+        (const unsigned char*)a.w3 + ((size_t)ap_row_channel(wave * 8 + prow) * K3 + (((lane & 7) ^ prow) * 8)) * 2;
     auto dma3 = [&](auto CC) {
         constexpr int cc = CC;
         if (B2_ABLATE & 4) return;
@@ -214,7 +134,7 @@ bneck2_kernel(const BneckArgs a) {
     // tail variant: conv1 of the next block, W1' [128][256], in eight 8-KB units of the W3 chunk shape: unit u = output channels
     // (u / 4) * 64 .. + 63 (rows permuted like every tile here), K columns (u % 4) * 64 .. + 63; one 1-KB piece per wave and unit.
     // Units pass through the six 8-KB slots S0, S1 (the W3 slots) and T0 .. T3 (the t1 buffer) behind the W3 chunks
-    const uint32_t w1noff = (uint32_t)((b2_row_channel(wave * 8 + prow) * 256 + (((lane & 7) ^ prow) * 8)) * 2);
+    const uint32_t w1noff = (uint32_t)((ap_row_channel(wave * 8 + prow) * 256 + (((lane & 7) ^ prow) * 8)) * 2);
     auto dmaU = [&](auto UU, auto SL) {                      // SL: 0, 1 = S0, S1; 2 .. 5 = T0 .. T3
         constexpr int u = UU, sl = SL;
         if (B2_ABLATE & 4) return;
@@ -279,7 +199,7 @@ bneck2_kernel(const BneckArgs a) {
     auto xone = [&](u32x4 (&xs)[NX], uint32_t (&xp)[2], auto II) {      // load i: fragment i/2 of row i%2
         constexpr int i = decltype(II)::value, k = i / 2, g = i % 2;
         if (B2_ABLATE & 1) return;
-        xs[g * NK1 + k] = gload_b128_s<k * 64>(xp[g], xg);
+        xs[g * NK1 + k] = ap_gld_sbase<k * 64>(xp[g], xg);
     };
     // where the output rows of tile T go.  Stores go through a buffer descriptor over y: lanes that have
     // nothing to store -- junk columns (lane 0 / 15), junk rows (halo row 0 / 15) -- carry an offset behind
@@ -300,15 +220,15 @@ bneck2_kernel(const BneckArgs a) {
         }
     };
     auto rdA = [&](u32x4 (&w)[4], uint32_t addr) {
-        w[0] = lds_read_b128<0>(addr); w[1] = lds_read_b128<2048>(addr);
-        w[2] = lds_read_b128<4096>(addr); w[3] = lds_read_b128<6144>(addr);
+        w[0] = ap_lds_read<0>(addr); w[1] = ap_lds_read<2048>(addr);
+        w[2] = ap_lds_read<4096>(addr); w[3] = ap_lds_read<6144>(addr);
     };
 
     // scale / shift of the 8 channels a lane holds in fragment pair q: t = {s[0..3], s[4..7], h[0..3], h[4..7]}
     auto rdT = [&](f32x4 (&t)[4], uint32_t tabq, auto OS, auto OH) {
         constexpr int os = decltype(OS)::value, oh = decltype(OH)::value;
-        t[0] = lds_read_f32x4<os>(tabq); t[1] = lds_read_f32x4<os + 16>(tabq);
-        t[2] = lds_read_f32x4<oh>(tabq); t[3] = lds_read_f32x4<oh + 16>(tabq);
+        t[0] = ap_lds_read_f32x4<os>(tabq); t[1] = ap_lds_read_f32x4<os + 16>(tabq);
+        t[2] = ap_lds_read_f32x4<oh>(tabq); t[3] = ap_lds_read_f32x4<oh + 16>(tabq);
     };
     // ---------------------------------------------------------------- one tile.  xc: its x fragments (requested a tile ago),
     // xn: the set the next tile's are requested into
@@ -354,7 +274,7 @@ bneck2_kernel(const BneckArgs a) {
         B2STAMP(0);
         auto xwait = [](u32x4 (&xc)[NX], auto KK) {      // (the array as a parameter: asm operands on a captured array reference do not compile)
             constexpr int k = decltype(KK)::value;
-            wait_vmcnt<Q - 2 - k>();                         // behind loads 2k, 2k+1 of the last tile: Q - 2k - 2 of that tile, k of this one
+            ap_wait_vm<Q - 2 - k>();                         // behind loads 2k, 2k+1 of the last tile: Q - 2k - 2 of that tile, k of this one
             asm volatile("" : "+v"(xc[k]), "+v"(xc[NK1 + k]));
         };
 
@@ -368,8 +288,8 @@ bneck2_kernel(const BneckArgs a) {
             constexpr int k = K;
             if constexpr (k + 1 < NK1) {
                 rdA(wf[(k + 1) & 1], (aW1 + ((k + 1) >> 1) * 8192) ^ (((k + 1) & 1) ? 64u : 0u));
-                wait_lgkmcnt<4>();
-            } else wait_lgkmcnt<0>();
+                ap_wait_lgkm<4>();
+            } else ap_wait_lgkm<0>();
             xwait(xc, K);
 #pragma unroll
             for (int f = 0; f < 4; ++f) { mm(acc[f], wf[k & 1][f], xc[k]); mm(acc[4 + f], wf[k & 1][f], xc[NK1 + k]); }
@@ -384,17 +304,17 @@ bneck2_kernel(const BneckArgs a) {
         sfor<0, 2>([&](auto Q) {                             // (one table read serves both pixel rows)
             constexpr int q = Q;
             rdT(tq, tab, std::integral_constant<int, T_S1 + q * 128>{}, std::integral_constant<int, T_H1 + q * 128>{});
-            wait_lgkmcnt<0>();
+            ap_wait_lgkm<0>();
             sfor<0, 2>([&](auto GG) {
                 constexpr int g = GG;
                 uint32_t unused = 0u;
                 u32x4 o = bn8(acc[g * 4 + 2 * q], acc[g * 4 + 2 * q + 1], tq[0], tq[1], tq[2], tq[3], nullptr, unused);
                 if (!inimg[g]) o = u32x4{0u, 0u, 0u, 0u};    // conv2 pads t1 with zeros, not with conv1 of zeros
                 ap_rng_note2(rng, o.x, o.y); ap_rng_note2(rng, o.z, o.w);   // (the value conv2 reads: not relu(shift) of a pixel outside the image)
-                lds_write_b128<g * 2048>(q ? tw ^ 64u : tw, o);
+                ap_lds_write<g * 2048>(q ? tw ^ 64u : tw, o);
             });
         });
-        wait_lgkmcnt<0>();
+        ap_wait_lgkm<0>();
         B2STAMP(3);
         __builtin_amdgcn_s_barrier();                        // t1 complete
         B2STAMP(4);
@@ -404,8 +324,8 @@ bneck2_kernel(const BneckArgs a) {
         u32x4 bfr[2][2];
         auto rdB = [&](u32x4 (&b)[2], auto TT, auto SS) {
             constexpr int t = TT, s = SS, dr = t / 3 - 1, dc = t % 3 - 1;
-            b[0] = lds_read_b128<0>((tbc[dc + 1] + rowoff[dr + 1]) ^ (s ? 64u : 0u));
-            b[1] = lds_read_b128<0>((tbc[dc + 1] + rowoff[dr + 2]) ^ (s ? 64u : 0u));
+            b[0] = ap_lds_read<0>((tbc[dc + 1] + rowoff[dr + 1]) ^ (s ? 64u : 0u));
+            b[1] = ap_lds_read<0>((tbc[dc + 1] + rowoff[dr + 2]) ^ (s ? 64u : 0u));
         };
 #pragma unroll
         for (int i = 0; i < 8; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -417,8 +337,8 @@ bneck2_kernel(const BneckArgs a) {
                 constexpr int t1 = (j + 1) >> 1, s1 = (j + 1) & 1;
                 rdA(wf[(j + 1) & 1], (aW2 + t1 * 8192) ^ (s1 ? 64u : 0u));
                 rdB(bfr[(j + 1) & 1], std::integral_constant<int, t1>{}, std::integral_constant<int, s1>{});
-                wait_lgkmcnt<6>();
-            } else wait_lgkmcnt<0>();
+                ap_wait_lgkm<6>();
+            } else ap_wait_lgkm<0>();
 #pragma unroll
             for (int f = 0; f < 4; ++f) { mm(acc[f], wf[j & 1][f], bfr[j & 1][0]); mm(acc[4 + f], wf[j & 1][f], bfr[j & 1][1]); }
             __builtin_amdgcn_sched_barrier(0);
@@ -429,7 +349,7 @@ bneck2_kernel(const BneckArgs a) {
         sfor<0, 2>([&](auto Q) {
             constexpr int q = Q;
             rdT(tq, tab, std::integral_constant<int, T_S2 + q * 128>{}, std::integral_constant<int, T_H2 + q * 128>{});
-            wait_lgkmcnt<0>();
+            ap_wait_lgkm<0>();
             y[q] = bn8(acc[2 * q], acc[2 * q + 1], tq[0], tq[1], tq[2], tq[3], nullptr, rngq[0]);
             y[2 + q] = bn8(acc[4 + 2 * q], acc[4 + 2 * q + 1], tq[0], tq[1], tq[2], tq[3], nullptr, rngq[1]);
         });
@@ -438,7 +358,7 @@ bneck2_kernel(const BneckArgs a) {
         // own pieces of W3 chunks 0, 1 (requested in the last tile, behind them: 8 stores, NX x loads); the barrier also says
         // every wave is done reading t1
         B2STAMP(6);
-        wait_vmcnt<(TAIL ? 4 : 8) + NX>();                  // (tail variant: behind them the 4 stores of the last conv1' chunk)
+        ap_wait_vm<(TAIL ? 4 : 8) + NX>();                  // (tail variant: behind them the 4 stores of the last conv1' chunk)
         __builtin_amdgcn_s_barrier();
         B2STAMP(7);
         dma3(I2{}); dma3(I3{});
@@ -449,7 +369,7 @@ bneck2_kernel(const BneckArgs a) {
             if constexpr (cc == 3) B2STAMP(11);
             if constexpr (cc == 2) {
                 B2STAMP(9);
-                wait_vmcnt<TAIL ? 10 : 8>();                 // own pieces of chunks 2, 3; behind them the stores of chunks 0, 1 (+ units 0, 1)
+                ap_wait_vm<TAIL ? 10 : 8>();                 // own pieces of chunks 2, 3; behind them the stores of chunks 0, 1 (+ units 0, 1)
                 __builtin_amdgcn_s_barrier();                // ... everybody's; and the slots of chunks 0, 1 are free
                 if constexpr (TAIL) { dmaU(I2{}, I0{}); dmaU(I3{}, I1{}); }   // units 2, 3 -> S0, S1
                 else { dma3(I0{}); dma3(I1{}); }             // for the next tile
@@ -466,7 +386,7 @@ bneck2_kernel(const BneckArgs a) {
             rdA(wf[1], base ^ 64u);
             sfor<0, NG>([&](auto S) {
                 constexpr int sg = S;
-                if constexpr (sg + 1 < NG) wait_lgkmcnt<4>(); else wait_lgkmcnt<0>();     // younger: the next group's fragments
+                if constexpr (sg + 1 < NG) ap_wait_lgkm<4>(); else ap_wait_lgkm<0>();     // younger: the next group's fragments
 #pragma unroll
                 for (int f = 0; f < 4; ++f) {
                     if constexpr (sg < 2) { mm(acc[f], wf[sg & 1][f], y[sg]); mm(acc[4 + f], wf[sg & 1][f], y[2 + sg]); }
@@ -480,7 +400,7 @@ bneck2_kernel(const BneckArgs a) {
                 constexpr int q = Q;
                 constexpr int to = cc * 256 + q * 128;
                 rdT(tq, tab, std::integral_constant<int, T_S3 + to>{}, std::integral_constant<int, T_H3 + to>{});
-                wait_lgkmcnt<0>();
+                ap_wait_lgkm<0>();
                 if constexpr (cc == 1) B2STAMP(14 + 2 * q);
                 sfor<0, 2>([&](auto GG) {
                     constexpr int g = GG;
@@ -509,7 +429,7 @@ bneck2_kernel(const BneckArgs a) {
                 rdA(wf[1], base ^ 64u);
                 sfor<0, 4>([&](auto S) {
                     constexpr int sg = S;
-                    if constexpr (sg + 1 < 4) wait_lgkmcnt<4>(); else wait_lgkmcnt<0>();
+                    if constexpr (sg + 1 < 4) ap_wait_lgkm<4>(); else ap_wait_lgkm<0>();
 #pragma unroll
                     for (int f = 0; f < 4; ++f) { mm(acc[f], wf[sg & 1][f], xc[kb + sg]); mm(acc[4 + f], wf[sg & 1][f], xc[NK1 + kb + sg]); }
                     __builtin_amdgcn_sched_barrier(0);
@@ -522,7 +442,7 @@ bneck2_kernel(const BneckArgs a) {
                     constexpr int q = Q;
                     constexpr int to = cb * 256 + q * 128;
                     rdT(tq, tab, std::integral_constant<int, T_S1N + to>{}, std::integral_constant<int, T_H1N + to>{});
-                    wait_lgkmcnt<0>();
+                    ap_wait_lgkm<0>();
                     sfor<0, 2>([&](auto GG) {
                         constexpr int g = GG;
                         const u32x4 o = bn8(acc[g * 4 + 2 * q], acc[g * 4 + 2 * q + 1], tq[0], tq[1], tq[2], tq[3], nullptr, rngq[g]);
@@ -531,24 +451,24 @@ bneck2_kernel(const BneckArgs a) {
                     });
                 });
             };
-            wait_vmcnt<18>();                                // own pieces of units 0, 1
+            ap_wait_vm<18>();                                // own pieces of units 0, 1
             __builtin_amdgcn_s_barrier();                    // ... everybody's; T0, T1 (W3 chunks 2, 3) are free
             dmaU(I4{}, I2{}); dmaU(I5{}, I3{});              // units 4, 5 -> T0, T1
 #pragma unroll
             for (int i = 0; i < 8; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
             sub(I0{}, aW3b + 16384);                         // chunk A, K groups 0-3 (T2, T3)
-            wait_vmcnt<10>();                                // units 2, 3
+            ap_wait_vm<10>();                                // units 2, 3
             __builtin_amdgcn_s_barrier();                    // T2, T3 free
             dmaU(I6{}, I4{}); dmaU(I7{}, I5{});              // units 6, 7 -> T2, T3
             sub(I4{}, aW3);                                  // chunk A, K groups 4-7 (S0, S1)
             epi(I0{});
-            wait_vmcnt<6>();                                 // units 4, 5
+            ap_wait_vm<6>();                                 // units 4, 5
             __builtin_amdgcn_s_barrier();                    // S0, S1 free
             dma3(I0{}); dma3(I1{});                          // W3 chunks 0, 1 of the next tile
 #pragma unroll
             for (int i = 0; i < 8; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
             sub(I0{}, aW3b);                                 // chunk B, K groups 0-3 (T0, T1)
-            wait_vmcnt<6>();                                 // units 6, 7
+            ap_wait_vm<6>();                                 // units 6, 7
             __builtin_amdgcn_s_barrier();
             sub(I4{}, aW3b + 16384);                         // chunk B, K groups 4-7 (T2, T3)
             epi(I1{});
@@ -579,7 +499,7 @@ bneck2_kernel(const BneckArgs a) {
         sfor<0, NX>([&](auto II) { xone(xa, xp0, II); });
     }
     dma3(I0{}); dma3(I1{});
-    wait_vmcnt<0>();
+    ap_wait_vm<0>();
     __syncthreads();
     while (true) {
         int Tn = T + G;
@@ -591,7 +511,7 @@ bneck2_kernel(const BneckArgs a) {
         if (!more) break;
         T = Tn;
     }
-    wait_vmcnt<0>();                                         // no LDS-DMA may be in flight when the LDS is released
+    ap_wait_vm<0>();                                         // no LDS-DMA may be in flight when the LDS is released
     if (lr >= 1 && lr <= 14) {
         if (wave != 0) ap_rng_note2(rng, rngq[0], rngq[0]);
         if (wave != 7) ap_rng_note2(rng, rngq[1], rngq[1]);

@@ -35,7 +35,7 @@ constexpr int CI_LDS = CI_SLOTS * 256;                       // 123 392
 constexpr int CI_STEPS = 36;                                 // K steps of 32: 2 channel chunks x 9 taps x 2 K halves
 constexpr size_t CI_WAVE_BYTES = (size_t)CI_STEPS * 4096;    // per channel half: 147 456; the layer: 294 912
 
-#include "bi_helpers.inc"
+#include "conv_prims.inc"
 
 // Timing-only builds (results WRONG, times valid): -DCI_ABLATE=<bits>: 1 no image DMA after the first | 2 no output stores | 4 no MFMAs
 #ifndef CI_ABLATE
@@ -54,7 +54,7 @@ __global__ void __launch_bounds__(256) conv_img3_pack_kernel(const bf16_t* __res
     const int cw = (int)(idx / per_half);
     const int p = (int)(idx - (size_t)cw * per_half);
     const int step = p >> 8, f = (p >> 6) & 3, lane = p & 63;
-    const int ch = cw * 64 + bi_row_channel(f * 16 + (lane & 15));
+    const int ch = cw * 64 + ap_row_channel(f * 16 + (lane & 15));
     const int c64 = step / 18, tap = (step % 18) >> 1, ks = step & 1;
     const bf16_t* src = w2 + (size_t)ch * (9 * CI_P) + tap * CI_P + c64 * 64 + ks * 32 + (lane >> 4) * 8;
     *(u32x4*)(dst + idx * 16) = *(const u32x4*)src;
@@ -84,7 +84,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     // zero rows (slots 0 .. 15 and 464 .. 481): written once, never touched again
     for (int idx = tid; idx < 34 * 16; idx += 256) {
         const int s = idx >> 4, c = idx & 15, u = s < 16 ? s : 464 + (s - 16);
-        bi_sts(smem, u * 256 + c * 16, u32x4{0u, 0u, 0u, 0u});
+        ap_lds_assign(smem, u * 256 + c * 16, u32x4{0u, 0u, 0u, 0u});
     }
 
     const unsigned char* const xg = (const unsigned char*)a.x;
@@ -109,8 +109,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     u32x4 ar[CI_RING][4];
     auto refill = [&](auto SL, u32x4 (&r)[CI_RING][4]) __attribute__((always_inline)) {           // ring slot SL <- the next piece of the stream
         constexpr int sl = decltype(SL)::value;
-        bi_gld<0>(r[sl][0], wlane, wp); bi_gld<1024>(r[sl][1], wlane, wp);
-        bi_gld<2048>(r[sl][2], wlane, wp); bi_gld<3072>(r[sl][3], wlane, wp);
+        ap_gld_sbase_pad<0>(r[sl][0], wlane, wp); ap_gld_sbase_pad<1024>(r[sl][1], wlane, wp);
+        ap_gld_sbase_pad<2048>(r[sl][2], wlane, wp); ap_gld_sbase_pad<3072>(r[sl][3], wlane, wp);
         wp += 4096;
         if (++wcnt == CI_STEPS) { wcnt = 0; wp = wsb; }
     };
@@ -140,7 +140,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             for (int i = 0; i < 7; ++i) {
                 const int row = wave + 4 * i;
                 const uint32_t m0v = lds0 + (uint32_t)((16 * (row + 1) + 4 * j) * 256);
-                asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(m0v), "v"(src) : "memory", "m0");
+                ap_dma_lds_m0(m0v, src);
                 src += 4 * (size_t)rstep;
             }
         }
@@ -169,33 +169,33 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 
     int hi = blockIdx.x;
     if (hi < nhalf) dma_half(hi);
-    bi_wait_vm<0>();
+    ap_wait_vm<0>();
     __syncthreads();
     for (; hi < nhalf; hi += gridDim.x) {
         int img, half;
         half_of(hi, img, half);
         // ================================================================ 36 K steps x 14 pixel rows, no barrier
-        bi_pipe<CI_STEPS * 14, 7>(bf,
+        ap_frag_pipe<CI_STEPS * 14, 7>(bf,
             [&](auto I, u32x4& d) __attribute__((always_inline)) {
                 constexpr int n = decltype(I)::value, g = n % 14;
                 constexpr CiStep q = ci_step(n / 14);
-                bi_ldsr<(g + q.dr + 1) * 4096>(d, tl[q.dc + 1][2 * q.c64 + q.ks]);
+                ap_lds_read_to<(g + q.dr + 1) * 4096>(d, tl[q.dc + 1][2 * q.c64 + q.ks]);
             },
             [&](auto I, u32x4& d) __attribute__((always_inline)) {
                 constexpr int n = decltype(I)::value, step = n / 14, g = n % 14, sl = step % CI_RING;
                 // the ring pieces of steps 0 .. 3 were requested during the previous half image and are older than its DMA and stores: the
                 // wait behind those covered them; from step 4 on: the piece of this step, three younger pieces behind it
-                if constexpr (g == 0 && step >= CI_RING) bi_wait_vm<4 * (CI_RING - 1)>();
+                if constexpr (g == 0 && step >= CI_RING) ap_wait_vm<4 * (CI_RING - 1)>();
 #pragma unroll
                 for (int f = 0; f < 4; ++f) {
                     if constexpr ((CI_ABLATE & 4) != 0 && step != 0) asm volatile("" : "+a"(acc[f][g]) : "v"(ar[sl][f]), "v"(d));
-                    else if constexpr (step == 0) bi_mma0(acc[f][g], ar[sl][f], d);
-                    else bi_mma(acc[f][g], ar[sl][f], d);
+                    else if constexpr (step == 0) ap_mfma_zero_a(acc[f][g], ar[sl][f], d);
+                    else ap_mfma_acc_a(acc[f][g], ar[sl][f], d);
                 }
                 if constexpr (g == 13) refill(std::integral_constant<int, sl>{}, ar);
             });
-        bi_settle28(acc[0], acc[1]);
-        bi_settle28(acc[2], acc[3]);
+        ap_settle(acc[0], acc[1]);
+        ap_settle(acc[2], acc[3]);
         __syncthreads();                                     // every wave is done reading this half image
         const int hn = hi + (int)gridDim.x;
         if (hn < nhalf && !(CI_ABLATE & 1)) dma_half(hn);    // the next one: in flight under the epilogue
@@ -208,7 +208,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             const int ch = cw * 64 + q * 32 + kq * 8;
 #pragma unroll
             for (int g = 0; g < 14; ++g) {
-                const u32x4 o = bi_bn8(acc[2 * q][g], acc[2 * q + 1][g], bs[q][0], bs[q][1], bh[q][0], bh[q][1], nullptr, rngu);
+                const u32x4 o = ap_bn8(acc[2 * q][g], acc[2 * q + 1][g], bs[q][0], bs[q][1], bh[q][0], bh[q][1], nullptr, rngu);
                 const uint32_t m = ((uint32_t)img * CI_H + (uint32_t)(rh * CI_HALF + g)) * CI_H + col;     // linear pixel index
                 const uint32_t off = a.y_tiled ? (uint32_t)(((m >> 4) * (CI_P >> 3) + (uint32_t)(ch >> 3)) * 256u + (m & 15u) * 16u)
                                                : (uint32_t)(m * (CI_P * 2u) + (uint32_t)ch * 2u);
@@ -217,10 +217,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         }
         if (img < a.N) ap_rng_note2(rng, rngu, rngu);        // (a padding half image of the last group computes relu(shift) and stores nothing)
         // the next half image has landed: vector-memory operations retire in order and only this wave's 28 stores are younger than its DMA
-        bi_wait_vm<28>();
+        ap_wait_vm<28>();
         __syncthreads();
     }
-    bi_wait_vm<0>();                                         // (the ring ran ahead: nothing may land after the exit)
+    ap_wait_vm<0>();                                         // (the ring ran ahead: nothing may land after the exit)
 #pragma unroll
     for (int j = 0; j < CI_RING; ++j) asm volatile("" : "+v"(ar[j][0]), "+v"(ar[j][1]), "+v"(ar[j][2]), "+v"(ar[j][3]));
     ap_rng_flush(a.range_flag, li < CI_HALF ? rng : 0u);    // (slots 14, 15 of a row are the halo / padding columns: computed, never stored)

@@ -21,6 +21,8 @@
 // avgpool_kernel (stem.hip): eight partitions p, p + 8, ... summed serially, then the partitions in order, / 49 -- so the features
 // are bit-identical to conv + avgpool_kernel, for every batch size and position of the image in the batch.  The image that
 // straddles the two sub-tiles (rows 98..146) carries its eight partial sums in LDS from the first sub-tile to the second.
+#include <type_traits>
+
 #include "ap_common.h"
 #include "kernels.h"
 
@@ -41,19 +43,7 @@ constexpr int CARRY_BYTES = 2 * 8 * HALF * 4;                                   
 static_assert(PSUM_OFF + PSUM_BYTES <= LDS_BYTES, "partial sums fit behind the stage");
 static_assert(3 * (LDS_BYTES + CARRY_BYTES) <= 160 * 1024, "three workgroups per CU");
 
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void wait_lgkmcnt() {
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-template <int OFF> __device__ __forceinline__ u32x4 lds_read_b128(uint32_t addr) {
-    u32x4 r;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-    return r;
-}
-__device__ __forceinline__ void mfma_acc(f32x4& c, const u32x4& w, const u32x4& x) {
-    asm volatile(AP_MFMA16_ASM " %0, %1, %2, %0" : "+v"(c) : "v"(w), "v"(x));
-}
+#include "conv_prims.inc"
 
 template <bool POOL>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 6))) conv_lean_kernel(const ConvArgs p) {
@@ -115,34 +105,34 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 6)))
     // wait for tile k+1 (tile k+2 stays in flight) -> barrier.
     issue_tile(0);
     if (KT > 1) issue_tile(1);
-    if (KT > 1) wait_vmcnt<2>();
-    else wait_vmcnt<0>();
+    if (KT > 1) ap_wait_vm_bare<2>();
+    else ap_wait_vm_bare<0>();
     __builtin_amdgcn_s_barrier();
     int slot = 0;
     for (int k = 0; k < KT; ++k) {
         const uint32_t so = slot * TILE_BYTES;
         u32x4 xf[FM], wf[FN];
-        xf[0] = lds_read_b128<0>(xa + so);
-        xf[1] = lds_read_b128<1024>(xa + so);
-        xf[2] = lds_read_b128<2048>(xa + so);
-        xf[3] = lds_read_b128<3072>(xa + so);
-        wf[0] = lds_read_b128<0>(wa + so);
-        wf[1] = lds_read_b128<1024>(wa + so);
+        xf[0] = ap_lds_read<0>(xa + so);
+        xf[1] = ap_lds_read<1024>(xa + so);
+        xf[2] = ap_lds_read<2048>(xa + so);
+        xf[3] = ap_lds_read<3072>(xa + so);
+        wf[0] = ap_lds_read<0>(wa + so);
+        wf[1] = ap_lds_read<1024>(wa + so);
         if (k + 2 < KT) issue_tile(slot == 0 ? 2 : slot - 1);   // (k + 2) % 3
         __builtin_amdgcn_sched_barrier(0);
-        wait_lgkmcnt<0>();
+        ap_wait_lgkm<0>();
 #pragma unroll
         for (int fm = 0; fm < FM; ++fm)
 #pragma unroll
-            for (int fn = 0; fn < FN; ++fn) mfma_acc(acc[fm][fn], wf[fn], xf[fm]);
+            for (int fn = 0; fn < FN; ++fn) ap_mfma_acc_v(acc[fm][fn], wf[fn], xf[fm]);
         if (k + 1 < KT) {
-            if (k + 2 < KT) wait_vmcnt<2>();
-            else wait_vmcnt<0>();
+            if (k + 2 < KT) ap_wait_vm_bare<2>();
+            else ap_wait_vm_bare<0>();
             __builtin_amdgcn_s_barrier();
         }
         slot = slot == 2 ? 0 : slot + 1;
     }
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");          // last MFMA results settle before the epilogue's VALU reads them
+    ap_settle_bare();                                        // last MFMA results settle before the epilogue's VALU reads them
 
     // ---------------------------------------------------------------- epilogue in two halves of 64 channels (as
     // conv_pipe.hip: fp32 stage in LDS, BatchNorm + residual + ReLU, 16-byte coalesced stores)

@@ -24,7 +24,7 @@
 // fetched by LDS-DMA into a 4-slot ring, 4 pieces per wave and tile issued between the MFMA groups; one raw s_barrier per
 // tile, every wait counted by hand (vmcnt retires in order; loads, LDS-DMA pieces and stores of a wave share the counter:
 // a wait for "at most N younger operations" is exact when only DMA pieces follow and conservative when epilogue loads /
-// stores sit among them).  -DPR_SAFE=1 turns every counted vmcnt into vmcnt(0) for cross-checking.
+// stores sit among them).  -DAP_SAFE=1 turns every counted vmcnt into vmcnt(0) for cross-checking.
 // Two workgroups (8 waves, <= 256 VGPRs) per CU: the waves of a SIMD belong to different workgroups and drift apart, so one
 // wave's epilogue (VALU + HBM latency) runs under the other's MFMA groups.
 #include <type_traits>
@@ -34,82 +34,24 @@
 
 AP_NS_BEGIN
 
-#ifndef PR_SAFE
-#define PR_SAFE 0
-#endif
-
 namespace {
 
 constexpr int PR_TILE = 16384;
 
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PR_SAFE ? 0 : N) : "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-template <int N> __device__ __forceinline__ void wait_lgkmcnt() {
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-    __builtin_amdgcn_sched_barrier(0);                       // register-only MFMAs ignore "memory": keep them below the wait
-}
-template <int OFF> __device__ __forceinline__ u32x4 lds_read_b128(uint32_t addr) {
-    u32x4 r;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-    return r;
-}
-// (fp32 table rows are read as f32x4 at once: __builtin_bit_cast applied to ONE ELEMENT of an integer vector mis-compiles
-// with this hipcc -- every element but the first comes out wrong; conv_pipe.hip's epilogue carries the same note)
-template <int OFF> __device__ __forceinline__ f32x4 lds_read_f32x4(uint32_t addr) {
-    f32x4 r;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-    return r;
-}
-// register load the compiler does not count (a load it counts is answered with vmcnt(0) beside LDS-DMA and would drain the
-// weight ring): the destination is valid only behind the hand-placed wait that names it
+#include "conv_prims.inc"
+
 // cache policy of the activation traffic: bit 0 = streaming (nt) loads of t2 / identity / x2 (each byte is read once; measured
 // +0.3 % on the whole bench, 5 interleaved pairs), bit 1 = nt stores (measured -0.5 %: off)
 #ifndef PR_NT
 #define PR_NT 1
 #endif
 template <int OFF> __device__ __forceinline__ u32x4 gload_b128(const unsigned char* p) {
-    u32x4 r;
-    if (PR_NT & 1) asm volatile("global_load_dwordx4 %0, %1, off offset:%2 nt" : "=v"(r) : "v"(p), "n"(OFF) : "memory");
-    else asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(r) : "v"(p), "n"(OFF) : "memory");
-    return r;
+    if (PR_NT & 1) return ap_gld_nt<OFF>(p);
+    else return ap_gld<OFF>(p);
 }
 __device__ __forceinline__ void gstore_b128(unsigned char* p, const u32x4& v) {
     if (PR_NT & 2) __builtin_nontemporal_store(v, (u32x4*)p);
     else *(u32x4*)p = v;
-}
-template <int I, int N, typename F> __device__ __forceinline__ void sfor(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        sfor<I + 1, N>(f);
-    }
-}
-__device__ __forceinline__ f32x4 mfma16(const u32x4& w, const u32x4& x, const f32x4& c) {
-    return ap_mfma16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c);
-}
-
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-// two fp32 -> one dword of two bf16 (round to nearest even: the instruction the compiler emits for a (__bf16) cast, but
-// once per PAIR -- the cast gives one v_cvt_pk per value plus shifts / ors to merge)
-__device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
-    uint32_t r;
-    asm(AP_CVTPK_ASM " %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// ReLU on two packed bf16: as signed 16-bit integers negative values (sign bit set, -0 included) are below zero, positive
-// ones keep their order -- max(x, 0) per half; rounding is monotonic and keeps the sign, so relu-then-round == round-then-relu
-__device__ __forceinline__ uint32_t relu_pk_bf16(uint32_t u) {
-    uint32_t r;
-    asm("v_pk_max_i16 %0, %1, 0" : "=v"(r) : "v"(u));
-    return r;
-}
-
-// channel (within its 128) of row rho of a weight tile: lane group g4 of fragment pair q = f >> 1 owns channels
-// q*32 + g4*8 .. + 7 (fragment f = 2q + e holds e*4 .. e*4 + 3 of them)
-__host__ __device__ __forceinline__ int pr_row_channel(int rho) {
-    const int f = rho >> 4, i = rho & 15;
-    return (f >> 1) * 32 + (i >> 2) * 8 + (f & 1) * 4 + (i & 3);
 }
 
 // weight stream: for every 128-channel chunk nb of conv3: P/64 tiles of conv3 (K steps of 64), then for each 64-deep half
@@ -121,7 +63,7 @@ __global__ void __launch_bounds__(256) pair_pack_kernel(const bf16_t* __restrict
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= T * 1024) return;
     const int t = idx >> 10, rho = (idx >> 3) & 127, c = (idx & 7) ^ (rho & 7);
-    const int nb = t / SPC, j = t - nb * SPC, chl = pr_row_channel(rho);
+    const int nb = t / SPC, j = t - nb * SPC, chl = ap_row_channel(rho);
     const bf16_t* src;
     if (j < KP) {
         src = w3 + (size_t)(nb * 128 + chl) * KA + j * 64 + c * 8;
@@ -210,7 +152,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3 
                                              (__attribute__((address_space(3))) void*)(smem + si + (wave * LPW + i) * 1024), 16, 0, 0);
     };
     auto mm = [&](f32x4& c, const u32x4& w, const u32x4& x) {
-        if (PR_ABLATE & 8) asm volatile("" : "+v"(c) : "v"(w), "v"(x)); else c = mfma16(w, x, c);
+        if (PR_ABLATE & 8) asm volatile("" : "+v"(c) : "v"(w), "v"(x)); else c = ap_mfma_frag(w, x, c);
     };
     // Fragment k of a tile (k = 8 s + f: row fragment f, K half s) lives in wf[k % D].  The fragment reads run D fragments
     // AHEAD of the MFMAs and straight across tile boundaries and barriers: the barrier of step t also covers tile t+1 (each
@@ -222,8 +164,8 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3 
         constexpr int g = G;
         const uint32_t b = g >= 2 ? a ^ 64u : a;
         constexpr int o = (g & 1) * 8192;
-        wf[(4 * g) % D] = lds_read_b128<o>(b); wf[(4 * g + 1) % D] = lds_read_b128<o + 2048>(b);
-        wf[(4 * g + 2) % D] = lds_read_b128<o + 4096>(b); wf[(4 * g + 3) % D] = lds_read_b128<o + 6144>(b);
+        wf[(4 * g) % D] = ap_lds_read<o>(b); wf[(4 * g + 1) % D] = ap_lds_read<o + 2048>(b);
+        wf[(4 * g + 2) % D] = ap_lds_read<o + 4096>(b); wf[(4 * g + 3) % D] = ap_lds_read<o + 6144>(b);
     };
     // one weight tile: 16 MFMAs (8 row fragments x 2 K halves) on each 16-pixel group of this wave (acc[pg]: its 8 accumulators,
     // bb[pg][0 / 1]: its B fragments of the two K halves); the wave's LPW DMA pieces go out between the MFMA groups (a piece costs
@@ -233,7 +175,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3 
         const uint32_t a0 = fb0 + so, an = fb0 + ((so + PR_TILE) & (RING - 1));
         sfor<0, 4>([&](auto G) {
             constexpr int g = G;
-            if (pre) wait_lgkmcnt<D - 4>(); else wait_lgkmcnt<0>();     // (last tile: nothing younger follows its fragments)
+            if (pre) ap_wait_lgkm<D - 4>(); else ap_wait_lgkm<0>();     // (last tile: nothing younger follows its fragments)
 #pragma unroll
             for (int f = 0; f < 4; ++f)
 #pragma unroll
@@ -253,7 +195,11 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3 
         si = (si + PR_TILE) & (RING - 1);
     };
     uint32_t rng = 0u;                                       // fp16 range sentinel (ap_common.h); nothing in the bf16 set
-    // BN + (identity) + ReLU + bf16 of the 8 consecutive channels a lane holds in fragments (2q, 2q+1); sc / sh: their tables
+    // This kernel's own copy of ap_bn8 (conv_prims.inc: the same text), behind the timing-only stub.  Calling ap_bn8 here -- from
+    // this lambda, from a file-scope wrapper, by value or by reference, defined in the header or in front of the kernel -- gives
+    // the same per-mnemonic instruction counts, register counts, spills and LDS for all five kernels, but not the same assembly:
+    // register numbers and the order of independent instructions move (about 460 of 16 900 lines), and the change has not been
+    // timed against the copy.  Until it has (tools/pair_bench.py, interleaved), the copy stays
     auto bn8 = [&](const f32x4& lo, const f32x4& hi, const f32x4& s0, const f32x4& s1, const f32x4& h0, const f32x4& h1,
                    const u32x4* res) -> u32x4 {
         if (PR_ABLATE & 16) {
@@ -261,23 +207,6 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3 
             asm volatile("" : "+v"(o) : "v"(lo), "v"(hi), "v"(s0), "v"(s1), "v"(h0), "v"(h1));
             return o;
         }
-        // two values per instruction (v_pk_fma_f32 / v_pk_add_f32: the same IEEE fma / add per component as the scalar
-        // epilogue of the stand-alone kernels), one v_cvt_pk + one packed integer max per pair
-#ifdef PR_SCALAR_EPI                                         // A/B build: one v_fma_f32 / v_add_f32 per value instead of the packed forms
-        f32x2 v0, v1, v2, v3;
-        asm("v_fma_f32 %0, %1, %2, %3" : "=v"(v0.x) : "v"(lo.x), "v"(s0.x), "v"(h0.x)); asm("v_fma_f32 %0, %1, %2, %3" : "=v"(v0.y) : "v"(lo.y), "v"(s0.y), "v"(h0.y));
-        asm("v_fma_f32 %0, %1, %2, %3" : "=v"(v1.x) : "v"(lo.z), "v"(s0.z), "v"(h0.z)); asm("v_fma_f32 %0, %1, %2, %3" : "=v"(v1.y) : "v"(lo.w), "v"(s0.w), "v"(h0.w));
-        asm("v_fma_f32 %0, %1, %2, %3" : "=v"(v2.x) : "v"(hi.x), "v"(s1.x), "v"(h1.x)); asm("v_fma_f32 %0, %1, %2, %3" : "=v"(v2.y) : "v"(hi.y), "v"(s1.y), "v"(h1.y));
-        asm("v_fma_f32 %0, %1, %2, %3" : "=v"(v3.x) : "v"(hi.z), "v"(s1.z), "v"(h1.z)); asm("v_fma_f32 %0, %1, %2, %3" : "=v"(v3.y) : "v"(hi.w), "v"(s1.w), "v"(h1.w));
-        if (res) {
-            const uint32_t r0 = (*res).x, r1 = (*res).y, r2 = (*res).z, r3 = (*res).w;
-            float a_, b_;
-            unpack_bf16x2(r0, a_, b_); asm("v_add_f32 %0, %0, %1" : "+v"(v0.x) : "v"(a_)); asm("v_add_f32 %0, %0, %1" : "+v"(v0.y) : "v"(b_));
-            unpack_bf16x2(r1, a_, b_); asm("v_add_f32 %0, %0, %1" : "+v"(v1.x) : "v"(a_)); asm("v_add_f32 %0, %0, %1" : "+v"(v1.y) : "v"(b_));
-            unpack_bf16x2(r2, a_, b_); asm("v_add_f32 %0, %0, %1" : "+v"(v2.x) : "v"(a_)); asm("v_add_f32 %0, %0, %1" : "+v"(v2.y) : "v"(b_));
-            unpack_bf16x2(r3, a_, b_); asm("v_add_f32 %0, %0, %1" : "+v"(v3.x) : "v"(a_)); asm("v_add_f32 %0, %0, %1" : "+v"(v3.y) : "v"(b_));
-        }
-#else
         f32x2 v0 = __builtin_elementwise_fma(lo.xy, s0.xy, h0.xy), v1 = __builtin_elementwise_fma(lo.zw, s0.zw, h0.zw);
         f32x2 v2 = __builtin_elementwise_fma(hi.xy, s1.xy, h1.xy), v3 = __builtin_elementwise_fma(hi.zw, s1.zw, h1.zw);
         if (res) {
@@ -294,10 +223,9 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3 
             { float a_, b_; unpack_bf16x2(r3, a_, b_); v3 += f32x2{a_, b_}; }
 #endif
         }
-#endif
         u32x4 o;
-        o.x = relu_pk_bf16(cvt_pk_bf16(v0.x, v0.y)); o.y = relu_pk_bf16(cvt_pk_bf16(v1.x, v1.y));
-        o.z = relu_pk_bf16(cvt_pk_bf16(v2.x, v2.y)); o.w = relu_pk_bf16(cvt_pk_bf16(v3.x, v3.y));
+        o.x = ap_relu_pk(pack_bf16x2(v0.x, v0.y)); o.y = ap_relu_pk(pack_bf16x2(v1.x, v1.y));
+        o.z = ap_relu_pk(pack_bf16x2(v2.x, v2.y)); o.w = ap_relu_pk(pack_bf16x2(v3.x, v3.y));
         ap_rng_note2(rng, o.x, o.y); ap_rng_note2(rng, o.z, o.w);   // fp16 range sentinel
         return o;
     };
@@ -357,7 +285,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3 
         for (int i = tid; i < C3; i += NT) { t3[i] = p.s3[i]; t3[C3 + i] = p.h3[i]; }
         for (int i = tid; i < N1; i += NT) { t1[i] = p.s1[i]; t1[N1 + i] = p.h1[i]; }
     }
-    wait_vmcnt<0>();
+    ap_wait_vm<0>();
 #pragma unroll
     for (int pg = 0; pg < PG; ++pg)
 #pragma unroll
@@ -368,7 +296,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3 
     if constexpr (D == 16) { rd4(std::integral_constant<int, 2>{}, fb0); rd4(std::integral_constant<int, 3>{}, fb0); }
 
     if (PR_ABLATE & 32) {                                    // timing build: the prologue alone
-        wait_lgkmcnt<0>();
+        ap_wait_lgkm<0>();
         asm volatile("" ::"v"(wf[0]), "v"(wf[D - 1]), "v"(xf[0][0]), "v"(xf[PG - 1][NXF - 1]), "v"(ra[0][0]), "v"(outp[0]), "v"(t1p[0]), "v"(resp[0]));
         return;
     }
@@ -398,7 +326,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3 
             // (measured, tools/probes/pair_trace.py: counting the identity loads / the next chunk's operations into these waits moves
             //  the 1.2-2.5k-cycle stall of step 1 into the epilogue's wait for the identity and changes nothing: the loads themselves
             //  take that long under this kernel's own HBM traffic)
-            if (lastc) { if constexpr (rem > 0) wait_vmcnt<LPW * yl>(); } else wait_vmcnt<LPW * (S - 3)>();
+            if (lastc) { if constexpr (rem > 0) ap_wait_vm<LPW * yl>(); } else ap_wait_vm<LPW * (S - 3)>();
             PRSTAMP(3 * j + 1);
             __builtin_amdgcn_s_barrier();
             PRSTAMP(3 * j + 2);
@@ -430,11 +358,11 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3 
                 // otherwise: the pieces of steps 1 .. KP-1 of this chunk (those that were issued)
                 if constexpr (RES) {
                     if constexpr (IDB) {
-                        if (nb == 0) wait_vmcnt<LPW * (S - 1)>(); else wait_vmcnt<(LPW * (SPC - 1) < 60 ? LPW * (SPC - 1) : 60)>();
+                        if (nb == 0) ap_wait_vm<LPW * (S - 1)>(); else ap_wait_vm<(LPW * (SPC - 1) < 60 ? LPW * (SPC - 1) : 60)>();
                     } else {
                         constexpr int nl = KP - 1 < SPC - S ? KP - 1 : (SPC - S > 0 ? SPC - S : 0);
                         constexpr int ys = LPW * (KP - 1) < 60 ? LPW * (KP - 1) : 60;
-                        if (lastc) wait_vmcnt<(LPW * nl < 60 ? LPW * nl : 60)>(); else wait_vmcnt<ys>();
+                        if (lastc) ap_wait_vm<(LPW * nl < 60 ? LPW * nl : 60)>(); else ap_wait_vm<ys>();
                     }
 #pragma unroll
                     for (int pg = 0; pg < PG; ++pg) asm volatile("" : "+v"(cur[pg][0]), "+v"(cur[pg][1]), "+v"(cur[pg][2]), "+v"(cur[pg][3]));
@@ -442,9 +370,9 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3 
                 const uint32_t ta = tb3 + nb * 512;
                 sfor<0, 4>([&](auto Q) {
                     constexpr int q = Q;
-                    const f32x4 s0 = lds_read_f32x4<q * 128>(ta), s1 = lds_read_f32x4<q * 128 + 16>(ta);
-                    const f32x4 h0 = lds_read_f32x4<C3 * 4 + q * 128>(ta), h1 = lds_read_f32x4<C3 * 4 + q * 128 + 16>(ta);
-                    wait_lgkmcnt<0>();
+                    const f32x4 s0 = ap_lds_read_f32x4<q * 128>(ta), s1 = ap_lds_read_f32x4<q * 128 + 16>(ta);
+                    const f32x4 h0 = ap_lds_read_f32x4<C3 * 4 + q * 128>(ta), h1 = ap_lds_read_f32x4<C3 * 4 + q * 128 + 16>(ta);
+                    ap_wait_lgkm<0>();
 #pragma unroll
                     for (int pg = 0; pg < PG; ++pg) {
                         cur[pg][q] = bn8(acc3[pg][2 * q], acc3[pg][2 * q + 1], s0, s1, h0, h1, RES ? &cur[pg][q] : nullptr);
@@ -468,8 +396,8 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3 
     sfor<0, HN * 4>([&](auto I) {
         constexpr int hn = I / 4, q = I % 4;
         const uint32_t ta = tb1 + (hn * 128 + q * 32) * 4;
-        const f32x4 s0 = lds_read_f32x4<0>(ta), s1 = lds_read_f32x4<16>(ta), h0 = lds_read_f32x4<N1 * 4>(ta), h1 = lds_read_f32x4<N1 * 4 + 16>(ta);
-        wait_lgkmcnt<0>();
+        const f32x4 s0 = ap_lds_read_f32x4<0>(ta), s1 = ap_lds_read_f32x4<16>(ta), h0 = ap_lds_read_f32x4<N1 * 4>(ta), h1 = ap_lds_read_f32x4<N1 * 4 + 16>(ta);
+        ap_wait_lgkm<0>();
 #pragma unroll
         for (int pg = 0; pg < PG; ++pg) {
             const u32x4 o = bn8(acc1[pg][hn * 8 + 2 * q], acc1[pg][hn * 8 + 2 * q + 1], s0, s1, h0, h1, nullptr);

@@ -15,6 +15,8 @@
 // Predication (3x3 halo, ragged M) is a pointer select to a 16-byte zero line.
 // Waits are counted by hand (inline asm) and the barrier is the raw s_barrier: __syncthreads()
 // would drain the DMA queue (vmcnt(0)) on every step.
+#include <type_traits>
+
 #include "ap_common.h"
 #include "kernels.h"
 
@@ -35,25 +37,17 @@ namespace {
 
 template <typename T> using Elem2 = ElemKind<T>;
 
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
+#include "conv_prims.inc"
 
-template <int N> __device__ __forceinline__ void wait_lgkmcnt() {
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-    __builtin_amdgcn_sched_barrier(0);      // keep register-only MFMAs below the wait (they ignore "memory")
-}
-// LDS fragment read the compiler does not count: hipcc answers a ds_read pending across the loop back-edge
-// with lgkmcnt(0), which serialises the fragment double-buffering; the waits are placed by hand instead.
+// the fragment read and the MFMA of this file, with their timing-only stubs (RP_ABLATE & 2, & 4)
 template <int OFF> __device__ __forceinline__ u32x4 lds_read_b128(uint32_t addr) {
-    u32x4 r;
 #if RP_ABLATE & 2
-    r = u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
+    u32x4 r = u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
     asm volatile("" : "+v"(r) : "v"(addr));
-#else
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-#endif
     return r;
+#else
+    return ap_lds_read<OFF>(addr);
+#endif
 }
 __device__ __forceinline__ f32x4 rp_mfma_bf16(const u32x4& w, const u32x4& x, const f32x4& c) {
 #if RP_ABLATE & 4
@@ -61,35 +55,12 @@ __device__ __forceinline__ f32x4 rp_mfma_bf16(const u32x4& w, const u32x4& x, co
     asm volatile("" : "+v"(r) : "v"(w), "v"(x));
     return r;
 #else
-    return ap_mfma16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c);
+    return ap_mfma_frag(w, x, c);
 #endif
 }
 
-template <typename T, int FM, int FN>
-__device__ __forceinline__ void mma_chunk2(const u32x4 (&xf)[FM], const u32x4 (&wf)[FN], f32x4 (&acc)[FM][FN]) {
-    if constexpr (Elem2<T>::KIND == K_BF16) {
-#pragma unroll
-        for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-            for (int fn = 0; fn < FN; ++fn)
-                acc[fm][fn] = ap_mfma16(
-                    __builtin_bit_cast(bf16x8, wf[fn]), __builtin_bit_cast(bf16x8, xf[fm]), acc[fm][fn]);
-    } else {
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-                for (int fn = 0; fn < FN; ++fn) {
-                    const uint32_t wv = t == 0 ? wf[fn].x : t == 1 ? wf[fn].y : t == 2 ? wf[fn].z : wf[fn].w;
-                    const uint32_t xv = t == 0 ? xf[fm].x : t == 1 ? xf[fm].y : t == 2 ? xf[fm].z : xf[fm].w;
-                    acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                        __builtin_bit_cast(float, wv), __builtin_bit_cast(float, xv), acc[fm][fn], 0, 0, 0);
-                }
-    }
-}
-
-// MFMA cluster with NP callbacks (one LDS-DMA piece each) spread evenly between the MFMAs
+// MFMA cluster with NP callbacks (one LDS-DMA piece each) spread evenly between the MFMAs.  conv_slab.hip has its own form of
+// this (fixed 4 x 2, tied asm MFMA): conv_prims.inc says why they are not one
 template <typename T, int FM, int FN, int NP, typename F>
 __device__ __forceinline__ void mma_issue(const u32x4 (&xf)[FM], const u32x4 (&wf)[FN], f32x4 (&acc)[FM][FN], F&& piece) {
     constexpr int KIND = Elem2<T>::KIND;
@@ -346,8 +317,8 @@ __global__ void __launch_bounds__(64 * WAVES_M * WAVES_N) conv_pipe_kernel(const
         if constexpr (FN > 3) wf[3] = lds_read_b128<6144>(wa);
     };
     // tile 0 landed (tiles 1 .. S-1 may still be in flight)
-    if (KT >= S) wait_vmcnt<(S - 1) * LPW>();
-    else wait_vmcnt<0>();
+    if (KT >= S) ap_wait_vm_bare<(S - 1) * LPW>();
+    else ap_wait_vm_bare<0>();
     __builtin_amdgcn_s_barrier();
     AP_BSTAMP(3);
     if constexpr (!SPLIT) load_frags(xa0, wa0, xf0, wf0);
@@ -371,20 +342,20 @@ __global__ void __launch_bounds__(64 * WAVES_M * WAVES_N) conv_pipe_kernel(const
         if constexpr (SPLIT) load_frags(xa0 + so, wa0 + so, xf0, wf0);
         load_frags(xa1 + so, wa1 + so, xf1, wf1);            // second half of tile kt (split-bf16: its lo parts)
         AP_STAMP(1);
-        wait_lgkmcnt<NFR>();                                 // first half (read one phase earlier) has landed
+        ap_wait_lgkm<NFR>();                                 // first half (read one phase earlier) has landed
         AP_STAMP(2);
         mma_issue<T, FM, FN, LPW>(xf0, wf0, acc, [&](int i) { if (refill) prep_piece(i); });
         if (refill) advance_tap();
         __builtin_amdgcn_sched_barrier(0);
         AP_STAMP(3);
-        wait_lgkmcnt<0>();                                   // all of this wave's reads of tile kt are done
+        ap_wait_lgkm<0>();                                   // all of this wave's reads of tile kt are done
         AP_STAMP(4);
         if (kt + 1 < KT) {
             // tile kt+1 must have landed; the younger tiles kt+2 .. kt+S-1 may stay in flight
             const int younger = KT - 2 - kt;                 // tiles issued after kt+1
-            if (younger >= S - 2) wait_vmcnt<(S - 2) * LPW>();
-            else if (S > 3 && younger == 1) wait_vmcnt<LPW>();
-            else wait_vmcnt<0>();
+            if (younger >= S - 2) ap_wait_vm_bare<(S - 2) * LPW>();
+            else if (S > 3 && younger == 1) ap_wait_vm_bare<LPW>();
+            else ap_wait_vm_bare<0>();
             AP_STAMP(5);
             if (!(RP_ABLATE & 8)) __builtin_amdgcn_s_barrier();
             AP_STAMP(6);

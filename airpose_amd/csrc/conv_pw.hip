@@ -41,10 +41,10 @@ namespace {
 constexpr int PW_STAGE = 224 * 128;                          // one staging buffer: 224 pixel slots x 64 channels
 constexpr int PW_LDS = 2 * PW_STAGE;
 
-#include "bi_helpers.inc"
+#include "conv_prims.inc"
 
 // dst [N tile][wave][K step][fragment 4][lane 64][8 K values]: row (lane & 15) of fragment f = output channel
-// ntile * 256 + wave * 64 + bi_row_channel(16 f + (lane & 15)), K columns 8 (lane >> 4) .. + 7 of the step's 32
+// ntile * 256 + wave * 64 + ap_row_channel(16 f + (lane & 15)), K columns 8 (lane >> 4) .. + 7 of the step's 32
 __global__ void __launch_bounds__(256) pw_pack_kernel(const bf16_t* __restrict__ w, unsigned char* __restrict__ dst, int cin, int cout, int wld) {
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t per_wave = (size_t)(cin >> 5) * 256, per_nt = 4 * per_wave;
@@ -53,7 +53,7 @@ __global__ void __launch_bounds__(256) pw_pack_kernel(const bf16_t* __restrict__
     const size_t r = idx - (size_t)nt * per_nt;
     const int wv = (int)(r / per_wave), p = (int)(r - (size_t)wv * per_wave);
     const int step = p >> 8, f = (p >> 6) & 3, lane = p & 63;
-    const int ch = nt * 256 + wv * 64 + bi_row_channel(f * 16 + (lane & 15));
+    const int ch = nt * 256 + wv * 64 + ap_row_channel(f * 16 + (lane & 15));
     *(u32x4*)(dst + idx * 16) = *(const u32x4*)(w + (size_t)ch * wld + step * 32 + (lane >> 4) * 8);
 }
 
@@ -97,8 +97,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     u32x4 ar[4][4];
     auto refill = [&](auto SL, u32x4 (&r)[4][4]) __attribute__((always_inline)) {           // ring slot SL <- the next piece of the stream
         constexpr int sl = decltype(SL)::value;
-        bi_gld<0>(r[sl][0], wlane, wp); bi_gld<1024>(r[sl][1], wlane, wp);
-        bi_gld<2048>(r[sl][2], wlane, wp); bi_gld<3072>(r[sl][3], wlane, wp);
+        ap_gld_sbase_pad<0>(r[sl][0], wlane, wp); ap_gld_sbase_pad<1024>(r[sl][1], wlane, wp);
+        ap_gld_sbase_pad<2048>(r[sl][2], wlane, wp); ap_gld_sbase_pad<3072>(r[sl][3], wlane, wp);
         wp += 4096;
         if (++wcnt == KS) { wcnt = 0; wp = wsb; }
     };
@@ -165,15 +165,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
                 sfor<0, 7>([&](auto J) __attribute__((always_inline)) {
                     constexpr int j = decltype(J)::value;
                     const uint32_t v = in ? xoff2[j] + (((inv >> j) & 1u) ? 0u : (uint32_t)toff) : 0u;
-                    bi_gld<0>(r[j], v, sp);
+                    ap_gld_sbase_pad<0>(r[j], v, sp);
                 });
                 return;
             }
             if constexpr (SEG2 == 1) {
                 if (c >= NC1 && c < NC) {                    // (uniform branch: both sides issue exactly seven loads)
                     const unsigned char* sp2 = x2t + (c - NC1) * 128;
-                    bi_gld<0>(r[0], xoff2[0], sp2); bi_gld<0>(r[1], xoff2[1], sp2); bi_gld<0>(r[2], xoff2[2], sp2); bi_gld<0>(r[3], xoff2[3], sp2);
-                    bi_gld<0>(r[4], xoff2[4], sp2); bi_gld<0>(r[5], xoff2[5], sp2); bi_gld<0>(r[6], xoff2[6], sp2);
+                    ap_gld_sbase_pad<0>(r[0], xoff2[0], sp2); ap_gld_sbase_pad<0>(r[1], xoff2[1], sp2); ap_gld_sbase_pad<0>(r[2], xoff2[2], sp2); ap_gld_sbase_pad<0>(r[3], xoff2[3], sp2);
+                    ap_gld_sbase_pad<0>(r[4], xoff2[4], sp2); ap_gld_sbase_pad<0>(r[5], xoff2[5], sp2); ap_gld_sbase_pad<0>(r[6], xoff2[6], sp2);
                     return;
                 }
             }
@@ -181,8 +181,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             const unsigned char* sp = real ? xt + c * 128 : xg;
             const uint32_t vo = real ? xoff : 0u, vo6 = real ? xoff6 : 0u;
             const uint32_t st = real ? 32u * xrow : 0u;
-            bi_gld<0>(r[0], vo, sp); bi_gld<0>(r[1], vo, sp + st); bi_gld<0>(r[2], vo, sp + 2 * (size_t)st); bi_gld<0>(r[3], vo, sp + 3 * (size_t)st);
-            bi_gld<0>(r[4], vo, sp + 4 * (size_t)st); bi_gld<0>(r[5], vo, sp + 5 * (size_t)st); bi_gld<0>(r[6], vo6, sp);   // (xoff6 carries its slot row itself)
+            ap_gld_sbase_pad<0>(r[0], vo, sp); ap_gld_sbase_pad<0>(r[1], vo, sp + st); ap_gld_sbase_pad<0>(r[2], vo, sp + 2 * (size_t)st); ap_gld_sbase_pad<0>(r[3], vo, sp + 3 * (size_t)st);
+            ap_gld_sbase_pad<0>(r[4], vo, sp + 4 * (size_t)st); ap_gld_sbase_pad<0>(r[5], vo, sp + 5 * (size_t)st); ap_gld_sbase_pad<0>(r[6], vo6, sp);   // (xoff6 carries its slot row itself)
         };
         // the last K iteration's staging slots fetch the identity of fragment half q = 0 instead: pixel groups GB .. GB + 6 (group 12 with
         // its junk lanes clamped, the non-existent group 13 = the dummy load)
@@ -190,10 +190,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             constexpr int gb = decltype(GB)::value;
             const unsigned char* sp = rt + (size_t)gb * 16 * orow;
             const size_t st = 16 * (size_t)orow;
-            bi_gld<0>(r[0], idoff, sp); bi_gld<0>(r[1], idoff, sp + st); bi_gld<0>(r[2], idoff, sp + 2 * st); bi_gld<0>(r[3], idoff, sp + 3 * st);
-            bi_gld<0>(r[4], idoff, sp + 4 * st);
-            if constexpr (gb == 0) { bi_gld<0>(r[5], idoff, sp + 5 * st); bi_gld<0>(r[6], idoff, sp + 6 * st); }
-            else { bi_gld<0>(r[5], idoff12, sp + 5 * st); bi_gld<0>(r[6], 0u, xg); }
+            ap_gld_sbase_pad<0>(r[0], idoff, sp); ap_gld_sbase_pad<0>(r[1], idoff, sp + st); ap_gld_sbase_pad<0>(r[2], idoff, sp + 2 * st); ap_gld_sbase_pad<0>(r[3], idoff, sp + 3 * st);
+            ap_gld_sbase_pad<0>(r[4], idoff, sp + 4 * st);
+            if constexpr (gb == 0) { ap_gld_sbase_pad<0>(r[5], idoff, sp + 5 * st); ap_gld_sbase_pad<0>(r[6], idoff, sp + 6 * st); }
+            else { ap_gld_sbase_pad<0>(r[5], idoff12, sp + 5 * st); ap_gld_sbase_pad<0>(r[6], 0u, xg); }
         };
         auto xstore = [&](u32x4 (&r)[7], int stage, int c) __attribute__((always_inline)) {         // c: the chunk the registers hold
             int toff;
@@ -203,12 +203,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             for (int j = 0; j < 7; ++j) {
                 asm volatile("" : "+v"(r[j]));
                 if (K3 && ((inv >> j) & 1u)) r[j] = u32x4{0u, 0u, 0u, 0u};
-                bi_sts(smem, xs_w + stage * PW_STAGE + j * (32 * 128), r[j]);
+                ap_lds_assign(smem, xs_w + stage * PW_STAGE + j * (32 * 128), r[j]);
             }
         };
         xload(xa, 0);
         xload(xb, 1);
-        bi_wait_vm<7>();                                     // chunk 0 (and everything older: the ring, the last tile's stores)
+        ap_wait_vm<7>();                                     // chunk 0 (and everything older: the ring, the last tile's stores)
         __syncthreads();                                     // (every wave is past its last fragment read of the previous tile)
         xstore(xa, 0, 0);
         xload(xa, 2);
@@ -218,15 +218,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             constexpr int stage = decltype(STAGE)::value, sl0 = decltype(SL0)::value;
             constexpr bool first = decltype(FIRST)::value != 0;
             const uint32_t ra = xs_r + stage * PW_STAGE, rb = ra ^ 64u;
-            bi_pipe<2 * NG, 7, 8>(b,
-                [&](auto I, u32x4& d) __attribute__((always_inline)) { constexpr int n = decltype(I)::value, ks = n / NG, g = n % NG; bi_ldsr<g * 2048>(d, ks ? rb : ra); },
+            ap_frag_pipe<2 * NG, 7, 8>(b,
+                [&](auto I, u32x4& d) __attribute__((always_inline)) { constexpr int n = decltype(I)::value, ks = n / NG, g = n % NG; ap_lds_read_to<g * 2048>(d, ks ? rb : ra); },
                 [&](auto I, u32x4& d) __attribute__((always_inline)) {
                     constexpr int n = decltype(I)::value, ks = n / NG, g = n % NG, sl = sl0 + ks;
-                    if constexpr (g == 0 && !first) bi_wait_vm<26>();       // the slot's piece: behind it 12 ring loads and 14 staging loads
+                    if constexpr (g == 0 && !first) ap_wait_vm<26>();       // the slot's piece: behind it 12 ring loads and 14 staging loads
 #pragma unroll
                     for (int f = 0; f < 4; ++f) {
-                        if constexpr (first && stage == 0 && ks == 0) bi_mma0(ac[f][g], r[sl][f], d);
-                        else bi_mma(ac[f][g], r[sl][f], d);
+                        if constexpr (first && stage == 0 && ks == 0) ap_mfma_zero_a(ac[f][g], r[sl][f], d);
+                        else ap_mfma_acc_a(ac[f][g], r[sl][f], d);
                     }
                     if constexpr (g == NG - 1) refill(std::integral_constant<int, sl>{}, r);
                 });
@@ -234,12 +234,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         auto c1_iter = [&](int c, auto FIRST, auto LAST) __attribute__((always_inline)) {
             constexpr bool first = decltype(FIRST)::value != 0, last = decltype(LAST)::value != 0;
             // chunk c from stage 0; chunk c + 1 -> stage 1 (free since the barrier that ended chunk c - 1); then chunk c + 3 requested
-            bi_wait_vm<(first ? 7 : 23)>();
+            ap_wait_vm<(first ? 7 : 23)>();
             xstore(xb, 1, c + 1);
             if constexpr (last && RES) idload(xb, I0{}); else xload(xb, c + 3);
             c1_pair(I0{}, I0{}, FIRST, bf, ar, acc);
             __syncthreads();
-            bi_wait_vm<(first ? 15 : 23)>();
+            ap_wait_vm<(first ? 15 : 23)>();
             if constexpr (!last) xstore(xa, 0, c + 2);
             if constexpr (last && RES) idload(xa, std::integral_constant<int, 7>{}); else xload(xa, c + 4);
             c1_pair(I1{}, I2{}, I0{}, bf, ar, acc);
@@ -250,11 +250,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         c1_iter(NC - 2, I0{}, I1{});
         // the last iteration's staging loads (identity, or nothing) must have landed before their registers are read or reused:
         // behind them the ring loads of the last two K steps
-        bi_wait_vm<8>();
+        ap_wait_vm<8>();
 #pragma unroll
         for (int j = 0; j < 7; ++j) asm volatile("" : "+v"(xa[j]), "+v"(xb[j]));
-        bi_settle28(acc[0], acc[1]);                         // the last MFMA results settle before VALU reads them
-        bi_settle28(acc[2], acc[3]);
+        ap_settle(acc[0], acc[1]);                         // the last MFMA results settle before VALU reads them
+        ap_settle(acc[2], acc[3]);
         // ---- epilogue: BN (+ identity) + ReLU + 16-bit, 16 bytes per lane and (pixel group, fragment half)
         const uint32_t so = (uint32_t)((size_t)m0 * orow) + ochan;
         sfor<0, 2>([&](auto Q) __attribute__((always_inline)) {
@@ -269,22 +269,22 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
                 constexpr int g = decltype(G)::value;
                 u32x4& idr = g < 7 ? xb[g] : xa[g - 7];
                 if constexpr (RES && q == 1) {
-                    bi_wait_vm<2 * NG - 2 - g>();            // behind identity load g of this half: NG - 1 - g (store, load) pairs, g stores
+                    ap_wait_vm<2 * NG - 2 - g>();            // behind identity load g of this half: NG - 1 - g (store, load) pairs, g stores
                     asm volatile("" : "+v"(idr));
                 }
-                const u32x4 o = bi_bn8(acc[2 * q][g], acc[2 * q + 1][g], s0, s1, h0, h1, RES ? &idr : nullptr, rng);
+                const u32x4 o = ap_bn8(acc[2 * q][g], acc[2 * q + 1][g], s0, s1, h0, h1, RES ? &idr : nullptr, rng);
                 const uint32_t vo = (g < NG - 1 || li < TM - 16 * (NG - 1)) ? vrun : 0xffffff00u;     // (junk lanes: dropped by the range check)
                 __builtin_amdgcn_raw_buffer_store_b128(o, yrsrc, vo, 0, 0);
                 vrun += 16u * orow;
                 asm volatile("" : "+v"(vrun));
                 if constexpr (RES && q == 0) {               // the register is consumed: the identity of half q = 1 takes it
                     __builtin_amdgcn_sched_barrier(0);
-                    bi_gld<64>(idr, g == NG - 1 ? idoff12 : idoff, rt + (size_t)g * 16 * orow);
+                    ap_gld_sbase_pad<64>(idr, g == NG - 1 ? idoff12 : idoff, rt + (size_t)g * 16 * orow);
                 }
             });
         });
     }
-    bi_wait_vm<0>();                                         // (the ring ran ahead: nothing may land after the exit)
+    ap_wait_vm<0>();                                         // (the ring ran ahead: nothing may land after the exit)
 #pragma unroll
     for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(ar[j][0]), "+v"(ar[j][1]), "+v"(ar[j][2]), "+v"(ar[j][3]));
     ap_rng_flush(a.range_flag, rng);

@@ -44,7 +44,7 @@ constexpr size_t SP_WAVE_BYTES = (size_t)SP_STEPS * 4096;    // per channel half
 #define SP_ABLATE 0
 #endif
 
-#include "bi_helpers.inc"
+#include "conv_prims.inc"
 
 // K step -> phase, tap, 32-channel quarter.  Phase p: 0 (odd rows, odd cols) | 1 (even, odd) | 2 (odd, even) | 3 (even, even)
 struct SpStep { int phase, dr, dc, j, rs, cs; };
@@ -69,17 +69,10 @@ __global__ void __launch_bounds__(256) conv_s2p_pack_kernel(const bf16_t* __rest
     const int cw = (int)(idx / per_half);
     const int p = (int)(idx - (size_t)cw * per_half);
     const int step = p >> 8, f = (p >> 6) & 3, lane = p & 63;
-    const int ch = cw * 64 + bi_row_channel(f * 16 + (lane & 15));
+    const int ch = cw * 64 + ap_row_channel(f * 16 + (lane & 15));
     const SpStep q = sp_step(step);
     const bf16_t* src = w2 + (size_t)ch * (9 * SP_P) + (q.dr * 3 + q.dc) * SP_P + q.j * 32 + (lane >> 4) * 8;
     *(u32x4*)(dst + idx * 16) = *(const u32x4*)src;
-}
-
-__device__ __forceinline__ void sp_settle14(f32x4 (&p)[7], f32x4 (&q)[7]) {
-    asm volatile("s_nop 15\n\ts_nop 15"
-                 : "+a"(p[0]), "+a"(p[1]), "+a"(p[2]), "+a"(p[3]), "+a"(p[4]), "+a"(p[5]), "+a"(p[6]), "+a"(q[0]), "+a"(q[1]), "+a"(q[2]),
-                   "+a"(q[3]), "+a"(q[4]), "+a"(q[5]), "+a"(q[6]));
-    __builtin_amdgcn_sched_barrier(0);
 }
 
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) conv_s2p_kernel(const ConvS2pArgs a) {
@@ -89,7 +82,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
     const uint32_t lds0 = (uint32_t)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
 
     // both regions start as zeros (every slot a junk lane can reach holds a finite value from the first read on), BatchNorm rows to LDS
-    for (int idx = tid; idx < 2 * SP_REGION / 16; idx += 512) bi_sts(smem, idx * 16, u32x4{0u, 0u, 0u, 0u});
+    for (int idx = tid; idx < 2 * SP_REGION / 16; idx += 512) ap_lds_assign(smem, idx * 16, u32x4{0u, 0u, 0u, 0u});
     if (tid < 2 * SP_P) ((float*)(smem + SP_BN))[tid] = tid < SP_P ? a.scale[tid] : a.shift[tid - SP_P];
 
     const int nunits = a.nunits_pad;                         // quarter images, padded to whole groups of 32
@@ -127,13 +120,13 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
                     const bool ok = cok && row >= 0;
                     const unsigned char* src = ok ? ximg + ((size_t)(row * SP_HI + col) * (SP_P * 2) + (uint32_t)(((dp - 2 * S) & 15) << 4)) : zg + (dp << 4);
                     const uint32_t m0v = lds0 + (uint32_t)(reg * SP_REGION + (16 * R + 4 * j) * 256);
-                    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(m0v), "v"(src) : "memory", "m0");
+                    ap_dma_lds_m0(m0v, src);
                 }
             }
         };
         __syncthreads();                                     // (the zeroing above is done before the first DMA lands)
         if (nmine > 0) dma(u0, 0, 0);
-        bi_wait_vm<0>();
+        ap_wait_vm<0>();
         __syncthreads();
         for (int k = 0; k < nmine; ++k) {
             const int u = u0 + k * ustep;
@@ -141,7 +134,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
             for (int ph = 0; ph < 4; ++ph) {
                 if (ph < 3) { if (!(SP_ABLATE & 1)) dma(u, ph + 1, (ph + 1) & 1); }
                 else if (k + 1 < nmine && !(SP_ABLATE & 1)) dma(u + ustep, 0, 0);
-                bi_wait_vm<0>();
+                ap_wait_vm<0>();
                 __syncthreads();
             }
         }
@@ -161,8 +154,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
     u32x4 ar[SP_RING][4];
     auto refill = [&](auto SL, u32x4 (&r)[SP_RING][4]) __attribute__((always_inline)) {
         constexpr int sl = decltype(SL)::value;
-        bi_gld<0>(r[sl][0], wlane, wp); bi_gld<1024>(r[sl][1], wlane, wp);
-        bi_gld<2048>(r[sl][2], wlane, wp); bi_gld<3072>(r[sl][3], wlane, wp);
+        ap_gld_sbase_pad<0>(r[sl][0], wlane, wp); ap_gld_sbase_pad<1024>(r[sl][1], wlane, wp);
+        ap_gld_sbase_pad<2048>(r[sl][2], wlane, wp); ap_gld_sbase_pad<3072>(r[sl][3], wlane, wp);
         wp += 4096;
         if (++wcnt == SP_STEPS) { wcnt = 0; wp = wsb; }
     };
@@ -179,7 +172,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
     f32x4 acc[4][7];
     u32x4 bf[8];
     __syncthreads();
-    bi_wait_vm<0>();                                         // the first ring pieces
+    ap_wait_vm<0>();                                         // the first ring pieces
     __syncthreads();
     for (int k = 0; k < nmine; ++k) {
         const int u = u0 + k * ustep;
@@ -187,29 +180,29 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
         unit_of(u, img, qy, qx);
         sfor<0, 4>([&](auto PH) __attribute__((always_inline)) {
             constexpr int ph = decltype(PH)::value, s0 = sp_first(ph), ns = sp_count(ph);
-            bi_pipe<ns * 7, 7, 8>(bf,
+            ap_frag_pipe<ns * 7, 7, 8>(bf,
                 [&](auto I, u32x4& d) __attribute__((always_inline)) {
                     constexpr int n = decltype(I)::value, g = n % 7;
                     constexpr SpStep q = sp_step(s0 + n / 7);
-                    bi_ldsr<(g + q.rs) * 4096>(d, tl[ph & 1][q.cs][q.j]);
+                    ap_lds_read_to<(g + q.rs) * 4096>(d, tl[ph & 1][q.cs][q.j]);
                 },
                 [&](auto I, u32x4& d) __attribute__((always_inline)) {
                     constexpr int n = decltype(I)::value, step = s0 + n / 7, g = n % 7, sl = step % SP_RING;
                     // the pieces of steps 0 .. SP_RING - 1 were requested during the previous quarter and are older than its stores: the
                     // wait behind those covered them; later: the piece of this step, SP_RING - 1 younger pieces behind it
-                    if constexpr (g == 0 && step >= SP_RING) bi_wait_vm<4 * (SP_RING - 1)>();
+                    if constexpr (g == 0 && step >= SP_RING) ap_wait_vm<4 * (SP_RING - 1)>();
 #pragma unroll
                     for (int f = 0; f < 4; ++f) {
                         if constexpr ((SP_ABLATE & 4) != 0 && step != 0) asm volatile("" : "+a"(acc[f][g]) : "v"(ar[sl][f]), "v"(d));
-                        else if constexpr (step == 0) bi_mma0(acc[f][g], ar[sl][f], d);
-                        else bi_mma(acc[f][g], ar[sl][f], d);
+                        else if constexpr (step == 0) ap_mfma_zero_a(acc[f][g], ar[sl][f], d);
+                        else ap_mfma_acc_a(acc[f][g], ar[sl][f], d);
                     }
                     if constexpr (g == 6) refill(std::integral_constant<int, sl>{}, ar);
                 });
             if constexpr (ph < 3) __syncthreads();           // this phase's region may be refilled; the next one has landed
         });
-        sp_settle14(acc[0], acc[1]);
-        sp_settle14(acc[2], acc[3]);
+        ap_settle(acc[0], acc[1]);
+        ap_settle(acc[2], acc[3]);
         // ================================================================ bn2 + ReLU + 16-bit, 14 stores of 16 bytes per lane
         const bool live = img < a.N && li < SP_Q;
         const uint32_t col = (uint32_t)(qx * SP_Q + li);
@@ -222,7 +215,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
             const f32x4 h0v = *(const f32x4*)(bn + SP_P + ch), h1v = *(const f32x4*)(bn + SP_P + ch + 4);
 #pragma unroll
             for (int g = 0; g < 7; ++g) {
-                const u32x4 o = bi_bn8(acc[2 * q][g], acc[2 * q + 1][g], s0v, s1v, h0v, h1v, nullptr, rngu);
+                const u32x4 o = ap_bn8(acc[2 * q][g], acc[2 * q + 1][g], s0v, s1v, h0v, h1v, nullptr, rngu);
                 const uint32_t m = ((uint32_t)img * SP_HO + (uint32_t)(qy * SP_Q + rh * 7 + g)) * SP_HO + col;     // linear pixel index
                 const uint32_t off = a.y_tiled ? (uint32_t)(((m >> 4) * (SP_P >> 3) + (uint32_t)(ch >> 3)) * 256u + (m & 15u) * 16u)
                                                : (uint32_t)(m * (SP_P * 2u) + (uint32_t)ch * 2u);
@@ -231,10 +224,10 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
         }
         if (img < a.N) ap_rng_note2(rng, rngu, rngu);        // (a padding quarter of the last group computes relu(shift) and stores nothing)
         // everything older than this wave's 14 stores has landed (the first ring pieces of the next quarter among it)
-        bi_wait_vm<14>();
+        ap_wait_vm<14>();
         __syncthreads();                                     // the fourth barrier of the quarter (the next one's first phase has landed)
     }
-    bi_wait_vm<0>();                                         // (the ring ran ahead: nothing may land after the exit)
+    ap_wait_vm<0>();                                         // (the ring ran ahead: nothing may land after the exit)
 #pragma unroll
     for (int j = 0; j < SP_RING; ++j) asm volatile("" : "+v"(ar[j][0]), "+v"(ar[j][1]), "+v"(ar[j][2]), "+v"(ar[j][3]));
     ap_rng_flush(a.range_flag, li < SP_Q ? rng : 0u);       // (slots 14, 15 of a row are junk lanes: computed, never stored)

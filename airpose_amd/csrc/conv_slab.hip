@@ -19,6 +19,8 @@
 //
 // LDS (80 KiB, two workgroups per CU): slab0 [0, 24K) | slab1 [24K, 48K) | weights0 [48K, 64K) | weights1 [64K, 80K);
 // rows are 128 B with the 16-byte chunk index XOR-swizzled by (row & 7) on the DMA source side.
+#include <type_traits>
+
 #include "ap_common.h"
 #include "kernels.h"
 
@@ -48,33 +50,17 @@ constexpr int WLP = 3;                                      // weight DMA pieces
 constexpr int CLD = BN + 4;
 static_assert(BM * CLD * 4 <= LDS_BYTES, "the fp32 epilogue stage reuses the operand buffers");
 
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void wait_lgkmcnt() {
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-template <int OFF> __device__ __forceinline__ u32x4 lds_read_b128(uint32_t addr) {
-    u32x4 r;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-    return r;
-}
-// MFMA with the accumulator tied in place.  With the nine taps unrolled the register allocator otherwise lets the eight
-// accumulators migrate (v_mfma d, a, b, c with d != c), which costs ~25 registers and spills; spill reloads sit behind
-// s_waitcnt vmcnt(0) and would drain the DMA queue every K step.  (Hazards the compiler no longer sees: consecutive MFMAs
-// here never share an accumulator back to back with different operands, and the epilogue's first VALU read of an
-// accumulator is fenced by s_nop below.)
-__device__ __forceinline__ void mfma_acc(f32x4& c, const u32x4& w, const u32x4& x) {
-    asm volatile(AP_MFMA16_ASM " %0, %1, %2, %0" : "+v"(c) : "v"(w), "v"(x));
-}
+#include "conv_prims.inc"
 
-// 8 MFMAs with NP callbacks spread evenly between them
+// 8 MFMAs (accumulators tied in place: ap_mfma_acc_v) with NP callbacks spread evenly between them.  conv_pipe.hip has its own
+// form of this (element type, placement knob, builtin MFMA): conv_prims.inc says why they are not one
 template <int NP, typename F>
 __device__ __forceinline__ void mma_issue(const u32x4 (&xf)[FM], const u32x4 (&wf)[FN], f32x4 (&acc)[FM][FN], F&& piece) {
     constexpr int NM = FM * FN;
 #pragma unroll
     for (int j = 0; j < NM; ++j) {
         const int fm = j / FN, fn = j % FN;
-        mfma_acc(acc[fm][fn], wf[fn], xf[fm]);
+        ap_mfma_acc_v(acc[fm][fn], wf[fn], xf[fm]);
 #pragma unroll
         for (int k = 0; k < NP; ++k)
             if ((k + 1) * NM / (NP + 1) == j + 1) {
@@ -170,7 +156,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4)))
         if (wave == 7) {
             issue_zero_row(0);
             issue_zero_row(1);
-            wait_vmcnt<0>();                                 // (the same wave overwrites rows of that piece below)
+            ap_wait_vm_bare<0>();                                 // (the same wave overwrites rows of that piece below)
         }
         for (int j = wave - 6; j < need; j += 2) issue_slab(0, 0, j);   // wave 7: the odd pieces, among them the last one
     } else {
@@ -228,11 +214,11 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4)))
 
     auto load_x = [&](const uint32_t (&xa)[FM], uint32_t flip, u32x4 (&xf)[FM]) {
 #pragma unroll
-        for (int fm = 0; fm < FM; ++fm) xf[fm] = lds_read_b128<0>(xa[fm] ^ flip);
+        for (int fm = 0; fm < FM; ++fm) xf[fm] = ap_lds_read<0>(xa[fm] ^ flip);
     };
     auto load_w = [&](uint32_t a, u32x4 (&wf)[FN]) {
-        wf[0] = lds_read_b128<0>(a);
-        wf[1] = lds_read_b128<2048>(a);
+        wf[0] = ap_lds_read<0>(a);
+        wf[1] = ap_lds_read<2048>(a);
     };
     // chunk g4 of the 128-byte row (first K half) sits at position g4 ^ (row & 7); chunk 4 + g4 (second half) at that address ^ 64.
     // A lane whose tap falls outside the image reads a zero row of ITS OWN ROW'S PARITY at the position its own row would
@@ -262,7 +248,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4)))
 
     uint32_t xa[FM];                                         // fragment addresses of the tile whose first half is read next
     tap_addr(pk[0], 0, lds0, xa);
-    wait_vmcnt<0>();
+    ap_wait_vm_bare<0>();
     __builtin_amdgcn_s_barrier();
     u32x4 xf0[FM], wf0[FN], xf1[FM], wf1[FN];
     load_x(xa, 0u, xf0);
@@ -294,7 +280,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4)))
                                                              // the first cluster overwrites them with the next tile's)
             load_w((wa + ws * WT_BYTES) ^ 64u, wf1);
             SL_STAMP(1);
-            wait_lgkmcnt<FM + FN>();                         // first half (read one phase earlier) has landed
+            ap_wait_lgkm<FM + FN>();                         // first half (read one phase earlier) has landed
             SL_STAMP(2);
             mma_issue<FM>(xf0, wf0, acc, [&](int part) {
                 if (!(SL_ABLATE & 2)) {
@@ -306,10 +292,10 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4)))
             });
             __builtin_amdgcn_sched_barrier(0);
             SL_STAMP(3);
-            wait_lgkmcnt<0>();                               // all of this wave's reads of tile kt are done
+            ap_wait_lgkm<0>();                               // all of this wave's reads of tile kt are done
             SL_STAMP(4);
             if (!last) {
-                if (!srole || tap == 8) wait_vmcnt<0>();
+                if (!srole || tap == 8) ap_wait_vm_bare<0>();
                 SL_STAMP(5);
                 __builtin_amdgcn_s_barrier();
                 SL_STAMP(6);
@@ -346,7 +332,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4)))
         scv[fn] = *(const float4*)(p.scale + ch);
         shv[fn] = *(const float4*)(p.shift + ch);
     }
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");          // last MFMA results settle before the epilogue's VALU reads them
+    ap_settle_bare();                                        // last MFMA results settle before the epilogue's VALU reads them
     if (!p.res && p.relu && p.y_tiled) {
         // Fragment-tiled output (t2 of a pair block: [M/16][C/8][16 pixels][8 channels]) straight from the accumulators: a lane holds
         // 4 consecutive channels of pixel lr per fragment, lanes g4 = 2k, 2k+1 the two halves of channel group k, so a wave's 8-byte

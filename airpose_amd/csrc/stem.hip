@@ -72,12 +72,7 @@ __global__ void __launch_bounds__(256) stem_direct_kernel(const float* __restric
 // are the rows of step kb moved up by one conv row, so the fused strip kernel keeps its five fragments in registers and reads
 // ONE new input-row fragment per step instead of five (15 instead of 35 per strip; its K loop is bound by LDS reads).
 __device__ constexpr int stem_kb_of(int step) { return step < 4 ? 2 * step : 2 * (step - 4) + 1; }
-template <int I, int N, typename F> __device__ __forceinline__ void stem_sfor(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        stem_sfor<I + 1, N>(f);
-    }
-}
+#include "conv_prims.inc"
 
 // ------------------------------------------------------------------------------------------------
 // MFMA stem (bf16 throughput path).  One workgroup = 16x16 conv outputs x 64 channels.
@@ -304,7 +299,7 @@ __device__ __forceinline__ void stem_strip_compute(const bf16_t* patch, const bf
         u32x4 xf[5];
         const bf16_t* xbase = patch + (2 * xo + 2 * g) * 4;
         const bf16_t* wbase = wsm + (half * FNH * 16 + lr) * SWLD + g * 8;
-        stem_sfor<0, SKB>([&](auto ST) {
+        sfor<0, SKB>([&](auto ST) {
             constexpr int step = decltype(ST)::value, kb = stem_kb_of(step);
             constexpr bool first = step == 0 || step == 4;   // first step of a parity: all five rows; then one new row per step
             constexpr int rot = first ? 0 : (step < 4 ? step : step - 4);
@@ -638,7 +633,7 @@ __global__ void __launch_bounds__(S2_NT) stem_pool2_kernel(const float* __restri
             ldw(stem_kb_of(0), wf[0]);
 #pragma unroll
             for (int fm = 0; fm < 4; ++fm) xf[fm] = *(const u32x4*)(xb + (2 * fm + stem_kb_of(0)) * FPW * 8);
-            stem_sfor<0, SKB>([&](auto ST) {
+            sfor<0, SKB>([&](auto ST) {
                 constexpr int step = decltype(ST)::value;
                 constexpr bool first = step == 0 || step == 4;
                 constexpr int rot = first ? 0 : (step < 4 ? step : step - 4);
