@@ -211,15 +211,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     return start + i;
 }
 
-// hipFuncSetAttribute and the CU count are per DEVICE: launch-side caches are keyed by the current device id
-// (two nets of one process on two GPUs, e.g. copenet_sep, each get their >64 KiB dynamic-LDS opt-in).
-#define AP_MAX_DEVICES 16
 #define AP_STEM_WLD 240                                      // row stride (elements) of the stem's packed MFMA weights (api.hip packs, stem.hip reads)
-static inline hipError_t ap_current_device(int* dev) {
-    hipError_t e = hipGetDevice(dev);
-    if (e != hipSuccess) return e;
-    return (*dev < 0 || *dev >= AP_MAX_DEVICES) ? hipErrorInvalidDevice : hipSuccess;
-}
 
 // host-side 16-bit helpers (weight packing; api.hip packs for either storage type)
 static inline float host_bf16_to_f32(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }

@@ -183,8 +183,6 @@ extern unsigned long long* g_conv_dbg;   // phase-stamp buffer (ap_debug_set_tra
 // the library's own host-mapped range word while ap_debug_set_range_hook is on and `prec` is AP_PREC_F16, NULL otherwise: what the
 // stand-alone operator entries (api_ops.hip) hand their kernels as range_flag
 int* ops_range_word(int prec);
-hipError_t zero_line(const void** out);
-hipError_t device_cus(int* n);
 int conv_mode();                         // the raw value of ap_set_conv_config, read once: a caller decodes ONE value per launch / per pass
 hipError_t dispatch_conv(ConvArgs& a, int prec /* AP_PREC_* */, hipStream_t st, int mode);
 const char* conv_refusal(const ConvArgs& a, int prec, int mode);   // why dispatch_conv would not run these arguments (NULL: it runs); no launch

@@ -29,7 +29,7 @@ hipError_t ap_internal::launch_conv(const ConvDesc& c, const void* x, int N, int
     ConvArgs a = conv_args(c, x, N, H, W, res, y, relu, y_tiled, x2, H2, rflag);
     if (pool_out && k_bf16::ap_conv_lean_supported(a, prec_kind(prec))) {
         a.y = nullptr; a.pool_out = pool_out; a.dbg = g_conv_dbg;
-        hipError_t e = zero_line(&a.zero);
+        hipError_t e = ap_zero_line(&a.zero);
         if (e != hipSuccess) return e;
         *pooled = true;
         return H16(prec, ap_launch_conv_lean)(a, st);
@@ -88,7 +88,7 @@ hipError_t ap_internal::launch_bneck2(const ConvDesc& c1, const ConvDesc& c2, co
     a.s1 = c1.scale; a.h1 = c1.shift; a.s2 = c2.scale; a.h2 = c2.shift; a.s3 = c3.scale; a.h3 = c3.shift;
     a.N = N; a.H = H; a.W = W; a.range_flag = rflag; a.dbg = g_conv_dbg;
     if (c1n) { a.w1n = c1n->w; a.s1n = c1n->scale; a.h1n = c1n->shift; a.t1n = t1n; a.y_even = y_even; }
-    hipError_t e = zero_line(&a.zero);
+    hipError_t e = ap_zero_line(&a.zero);
     if (e != hipSuccess) return e;
     return H16(prec, ap_launch_bneck2)(a, ds, st);
 }
@@ -105,7 +105,7 @@ hipError_t ap_internal::launch_conv_img3(const void* x, const void* wfrag, const
                                          int prec, int* rflag, hipStream_t st) {
     ConvImg3Args a{};
     a.x = x; a.y = y; a.wfrag = wfrag; a.scale = scale; a.shift = shift; a.N = N; a.y_tiled = y_tiled; a.range_flag = rflag;
-    hipError_t e = zero_line(&a.zero);
+    hipError_t e = ap_zero_line(&a.zero);
     if (e != hipSuccess) return e;
     return H16(prec, ap_launch_conv_img3)(a, st);
 }
@@ -114,7 +114,7 @@ hipError_t ap_internal::launch_conv_s2p(const void* x, const void* wfrag, const 
                                         int prec, int* rflag, hipStream_t st) {
     ConvS2pArgs a{};
     a.x = x; a.y = y; a.wfrag = wfrag; a.scale = scale; a.shift = shift; a.N = N; a.y_tiled = y_tiled; a.range_flag = rflag;
-    hipError_t e = zero_line(&a.zero);
+    hipError_t e = ap_zero_line(&a.zero);
     if (e != hipSuccess) return e;
     return H16(prec, ap_launch_conv_s2p)(a, st);
 }

@@ -49,8 +49,8 @@ int smplx_run(ap_smplx* h, SmplxFwdArgs a, bool body_only, hipStream_t st) {
     HIP_TRY(ap_launch_smplx_prep(m, a, st));
     if (stages) HIP_TRY(h->tm.rec(st, &ev[1]));
     if (fused) {
-        int n_cu = 0;
-        HIP_TRY(device_cus(&n_cu));
+        int dev = 0, n_cu = 0;
+        HIP_TRY(ap_device(&dev, &n_cu));
         HIP_TRY(ap_launch_smplx_lbs_fused(m, a, n_cu, h->merge_bones, st));
         if (stages) { HIP_TRY(h->tm.rec(st, &ev[2])); ev[3] = ev[2]; }        // stage 1 = the fused kernel, stage 2 empty
     } else {

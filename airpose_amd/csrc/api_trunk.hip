@@ -12,7 +12,6 @@ namespace {
 // conv_mode() reads it, once per launch (dispatch_conv's three-argument form) or once per pass (trunk_chunk, which hands the value
 // down), so handles on different threads never see a torn setting.
 std::atomic<int> g_conv_mode{-1};
-void* g_zero[AP_MAX_DEVICES] = {nullptr};   // per-device 256-byte zero line
 // ap_debug_set_range_hook: one host-mapped word for the process, allocated on first use and kept; g_ops_range is that word while
 // the hook is on and NULL while it is off (one atomic pointer: a launch sees the old or the new value)
 int* g_ops_word = nullptr;
@@ -24,33 +23,6 @@ int* ap_internal::ops_range_word(int prec) {
 }
 
 int ap_internal::conv_mode() { return g_conv_mode.load(std::memory_order_relaxed); }
-
-hipError_t ap_internal::zero_line(const void** out) {
-    int dev = 0;
-    hipError_t e = ap_current_device(&dev);
-    if (e != hipSuccess) return e;
-    if (!g_zero[dev]) {
-        e = hipMalloc(&g_zero[dev], 256);
-        if (e != hipSuccess) return e;
-        e = hipMemset(g_zero[dev], 0, 256);
-        if (e != hipSuccess) return e;
-    }
-    *out = g_zero[dev];
-    return hipSuccess;
-}
-
-hipError_t ap_internal::device_cus(int* n) {
-    static int cus[AP_MAX_DEVICES] = {};
-    int dev = 0;
-    hipError_t e = ap_current_device(&dev);
-    if (e != hipSuccess) return e;
-    if (!cus[dev]) {
-        e = hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev);
-        if (e != hipSuccess) return e;
-    }
-    *n = cus[dev];
-    return hipSuccess;
-}
 
 namespace {
 // choose the tile configuration: large tiles need enough tiles to fill 256 CUs (1 workgroup per CU)
@@ -111,7 +83,7 @@ hipError_t ap_internal::dispatch_conv(ConvArgs& a, int prec /* AP_PREC_* */, hip
     const int cfg = conv_config(a, is_bf16, mode);
     if (conv_refusal(a, prec, mode)) return hipErrorInvalidValue;
     if (cfg == 100) return H16(prec, ap_launch_conv)(a, is_bf16, st);
-    hipError_t e = zero_line(&a.zero);
+    hipError_t e = ap_zero_line(&a.zero);
     if (e != hipSuccess) return e;
     a.dbg = g_conv_dbg;
     if (cfg == 17) {                                         // lean pointwise kernel; other shapes: the ring kernel's tile
@@ -264,8 +236,8 @@ int trunk_chunk(ap_net* h, ap_net::TrunkWs& w, const float* x0, int n0, const fl
     const int prec = h->prec;                                // selects the kernel set (H16) and, as prec_kind, the storage kind
     const int n = n0 + n1;
     const int mode = conv_mode();                            // ONE schedule for the whole pass, whatever a setter does meanwhile
-    int cus = 0;
-    HIP_TRY(device_cus(&cus));
+    int dev = 0, cus = 0;
+    HIP_TRY(ap_device(&dev, &cus));
     if (h->blocks.size() > MAX_BLOCKS) return fail(AP_ESTATE, "trunk: more bottleneck blocks than a pass plans");
     BlockPlan plan[MAX_BLOCKS];
     plan_pass(h, n, cus, mode, shared, plan);

@@ -377,21 +377,14 @@ hipError_t ap_launch_block_img_pack(const void* w1, const void* w2, const void* 
 }
 
 hipError_t ap_launch_block_img(const BlkImgArgs& a, hipStream_t st) {
-    static int n_cu_dev[AP_MAX_DEVICES] = {};
+    static ApDeviceOnce optin;
     if (a.N <= 0 || !a.x || !a.y || !a.wfrag || !a.s1 || !a.h1 || !a.s2 || !a.h2 || !a.s3 || !a.h3) return hipErrorInvalidValue;
     if ((size_t)a.N * (BI_PIX * BI_C * 2) >= 0xffffff00ull) return hipErrorInvalidValue;                       // 32-bit offsets, out-of-range marker
-    int dev = 0;
-    hipError_t e = ap_current_device(&dev);
+    int dev = 0, n_cu = 0;
+    hipError_t e = ap_device(&dev, &n_cu);
+    if (e == hipSuccess) e = ap_lds_optin(optin, dev, {{blk_img_kernel, BI_T_BYTES}});
     if (e != hipSuccess) return e;
-    if (!n_cu_dev[dev]) {
-        int n = 0;
-        e = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)blk_img_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BI_T_BYTES);
-        if (e != hipSuccess) return e;
-        n_cu_dev[dev] = n;
-    }
-    const int grid = a.N < n_cu_dev[dev] ? a.N : n_cu_dev[dev];
+    const int grid = a.N < n_cu ? a.N : n_cu;
     hipLaunchKernelGGL(blk_img_kernel, dim3(grid), dim3(256), BI_T_BYTES, st, a);
     return hipGetLastError();
 }

@@ -523,32 +523,21 @@ bneck2_kernel(const BneckArgs a) {
 
 // layer1 bottleneck, second cut: ds = 0 identity block (cin = 256), ds = 1 first block (cin = 64, W3 rows = [conv3 | downsample])
 hipError_t ap_launch_bneck2(BneckArgs a, int ds, hipStream_t st) {
-    static int n_cu_dev[AP_MAX_DEVICES] = {};
+    static ApDeviceOnce optin;
     if (a.H % B2_TS || a.W % B2_TS || a.N <= 0) return hipErrorInvalidValue;
     if ((size_t)a.N * a.H * a.W * 512 >= 0xffff0000ull) return hipErrorInvalidValue;      // 32-bit offsets, out-of-range marker
-    int dev = 0;
-    hipError_t e = ap_current_device(&dev);
+    constexpr int lds_ds = B2Map<true>::TOTAL, lds_id = B2Map<false>::TOTAL, lds_tail = B2Map<false, true>::TOTAL;
+    int dev = 0, n_cu = 0;
+    hipError_t e = ap_device(&dev, &n_cu);
+    if (e == hipSuccess)
+        e = ap_lds_optin(optin, dev, {{bneck2_kernel<false, false>, lds_id}, {bneck2_kernel<true, false>, lds_ds}, {bneck2_kernel<false, true>, lds_tail}});
     if (e != hipSuccess) return e;
-    if (!n_cu_dev[dev]) {
-        int n = 0;
-        e = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)bneck2_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, B2Map<false>::TOTAL);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)bneck2_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, B2Map<true>::TOTAL);
-        if (e != hipSuccess) return e;
-        constexpr int lds_t = B2Map<false, true>::TOTAL;
-        e = hipFuncSetAttribute((const void*)bneck2_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_t);
-        if (e != hipSuccess) return e;
-        n_cu_dev[dev] = n;
-    }
     a.tiles_x = a.W / B2_TS;
     a.tiles_per_img = a.tiles_x * (a.H / B2_TS);
     a.total = a.N * a.tiles_per_img;
-    const int grid = a.total < n_cu_dev[dev] ? a.total : n_cu_dev[dev];
+    const int grid = a.total < n_cu ? a.total : n_cu;
     if (a.w1n && (ds || !a.s1n || !a.h1n || !a.t1n)) return hipErrorInvalidValue;
     if ((size_t)a.N * a.H * a.W * 256 >= 0xffff0000ull) return hipErrorInvalidValue;
-    constexpr int lds_ds = B2Map<true>::TOTAL, lds_id = B2Map<false>::TOTAL, lds_tail = B2Map<false, true>::TOTAL;
     if (ds) hipLaunchKernelGGL((bneck2_kernel<true, false>), dim3(grid), dim3(512), lds_ds, st, a);
     else if (a.w1n) hipLaunchKernelGGL((bneck2_kernel<false, true>), dim3(grid), dim3(512), lds_tail, st, a);
     else hipLaunchKernelGGL((bneck2_kernel<false, false>), dim3(grid), dim3(512), lds_id, st, a);

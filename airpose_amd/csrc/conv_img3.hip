@@ -243,23 +243,16 @@ hipError_t ap_launch_conv_img3_pack(const void* w2, void* dst, hipStream_t st) {
 }
 
 hipError_t ap_launch_conv_img3(const ConvImg3Args& a, hipStream_t st) {
-    static int n_cu_dev[AP_MAX_DEVICES] = {};
+    static ApDeviceOnce optin;
     if (a.N <= 0 || !a.x || !a.y || !a.wfrag || !a.scale || !a.shift || !a.zero) return hipErrorInvalidValue;
     if ((size_t)a.N * (CI_H * CI_H * CI_P * 2) >= 0xffff0000ull) return hipErrorInvalidValue;                     // 32-bit offsets, out-of-range marker
-    int dev = 0;
-    hipError_t e = ap_current_device(&dev);
+    int dev = 0, n_cu = 0;
+    hipError_t e = ap_device(&dev, &n_cu);
+    if (e == hipSuccess) e = ap_lds_optin(optin, dev, {{conv_img3_kernel, CI_LDS}});
     if (e != hipSuccess) return e;
-    if (!n_cu_dev[dev]) {
-        int n = 0;
-        e = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)conv_img3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CI_LDS);
-        if (e != hipSuccess) return e;
-        n_cu_dev[dev] = n;
-    }
     // half images in groups of 16 (8 images: both halves of an image on one XCD); grid: one workgroup per CU, a multiple of 16
     const int nhalf16 = (2 * a.N + 15) / 16 * 16;
-    int grid = n_cu_dev[dev] / 16 * 16;
+    int grid = n_cu / 16 * 16;
     if (grid < 16) grid = 16;
     if (grid > nhalf16) grid = nhalf16;
     ConvImg3Args b = a;

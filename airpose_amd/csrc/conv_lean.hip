@@ -268,15 +268,11 @@ hipError_t ap_launch_conv_lean(ConvArgs a, hipStream_t st) {
     if (a.pool_out) {
         // conv + BatchNorm + identity + ReLU + AvgPool2d(7) + view: 7 x 7 images, every pixel of an image in one super-tile
         if (a.Ho * a.Wo != POOL_PIX || a.M != a.N * POOL_PIX || !a.res || !a.relu) return hipErrorInvalidValue;
-        static bool attr_set[AP_MAX_DEVICES] = {};
+        static ApDeviceOnce optin;
         int dev = 0;
-        hipError_t e = ap_current_device(&dev);
+        hipError_t e = ap_device(&dev, nullptr);
+        if (e == hipSuccess) e = ap_lds_optin(optin, dev, {{conv_lean_kernel<true>, LDS_BYTES + CARRY_BYTES}});
         if (e != hipSuccess) return e;
-        if (!attr_set[dev]) {
-            e = hipFuncSetAttribute((const void*)conv_lean_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES + CARRY_BYTES);
-            if (e != hipSuccess) return e;
-            attr_set[dev] = true;
-        }
         a.mtiles = (a.N + POOL_IMGS - 1) / POOL_IMGS;
         hipLaunchKernelGGL(conv_lean_kernel<true>, dim3(a.mtiles * a.ntiles), dim3(NT), LDS_BYTES + CARRY_BYTES, st, a);
         return hipGetLastError();

@@ -410,18 +410,14 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3 
 
 template <int P, int P2, int C3, int N1, bool RES, int NW, int S, int D, bool IDB, int PG = 1>
 hipError_t launch_pair(const PairArgs& a, hipStream_t st) {
-    static bool attr_set[AP_MAX_DEVICES] = {};
+    static ApDeviceOnce optin;
     auto kern = conv_pair_kernel<P, P2, C3, N1, RES, NW, S, D, IDB, PG>;
     constexpr int lds = S * PR_TILE + (2 * C3 + 2 * N1) * 4;
     static_assert(NW == 8 || PG == 2 || lds <= 81920, "two workgroups per CU");
     int dev = 0;
-    hipError_t e = ap_current_device(&dev);
+    hipError_t e = ap_device(&dev, nullptr);
+    if (e == hipSuccess) e = ap_lds_optin(optin, dev, {{kern, lds}});
     if (e != hipSuccess) return e;
-    if (!attr_set[dev]) {
-        e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
     hipLaunchKernelGGL(kern, dim3((a.M + 16 * NW * PG - 1) / (16 * NW * PG)), dim3(64 * NW), lds, st, a);
     return hipGetLastError();
 }

@@ -601,18 +601,14 @@ __global__ void __launch_bounds__(64 * WAVES_M * WAVES_N) conv_pipe_kernel(const
 
 template <typename T, int BM, int BN, int WM, int WN, int S, bool DIRECT>
 hipError_t launch_pipe(ConvArgs a, hipStream_t st) {
-    static bool attr_set[AP_MAX_DEVICES] = {};
+    static ApDeviceOnce optin;
     auto kern = conv_pipe_kernel<T, BM, BN, WM, WN, S, DIRECT>;
     constexpr int ring = S * (BM + BN) * 128, epi = BM * (BN + 4) * 4;
     constexpr int lds = ring > epi ? ring : epi;
     int dev = 0;
-    hipError_t e = ap_current_device(&dev);
+    hipError_t e = ap_device(&dev, nullptr);
+    if (e == hipSuccess) e = ap_lds_optin(optin, dev, {{kern, lds}});
     if (e != hipSuccess) return e;
-    if (!attr_set[dev]) {
-        e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
     if (a.x2 && BN < 128) return hipErrorInvalidValue;       // the 64-wide tiles carry no second K segment: refuse, never drop it
     // the second K segment addresses x2 with 32-bit byte offsets (0xffffffff = "row predicated off"): refuse a tensor
     // that does not fit instead of wrapping (fp32 at >= 1338 images of layer2.0 would)

@@ -334,27 +334,16 @@ int ap_conv_pw_grid(long M, int Cout, int n_cu) {
 }
 
 hipError_t ap_launch_conv_pw(const PwArgs& a, hipStream_t st) {
-    static int n_cu_dev[AP_MAX_DEVICES] = {};
+    static ApDeviceOnce optin;
     if (!a.x || !a.y || !a.wfrag || !a.scale || !a.shift || !a.relu) return hipErrorInvalidValue;
     if (a.k3 ? !ap_conv_pw_k3_supported(a) : a.x2 ? !ap_conv_pw_ds_supported(a) : !ap_conv_pw_supported(a.M, a.Cin, a.Cout)) return hipErrorInvalidValue;
-    int dev = 0;
-    hipError_t e = ap_current_device(&dev);
+    int dev = 0, n_cu = 0;
+    hipError_t e = ap_device(&dev, &n_cu);
+    if (e == hipSuccess)
+        e = ap_lds_optin(optin, dev, {{conv_pw_kernel<13, false, 0>, PW_LDS}, {conv_pw_kernel<13, true, 0>, PW_LDS},
+                                      {conv_pw_kernel<13, false, 1>, PW_LDS}, {conv_pw_kernel<13, false, 2>, PW_LDS}});
     if (e != hipSuccess) return e;
-    if (!n_cu_dev[dev]) {
-        int n = 0;
-        e = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)conv_pw_kernel<13, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, PW_LDS);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)conv_pw_kernel<13, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, PW_LDS);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)conv_pw_kernel<13, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, PW_LDS);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)conv_pw_kernel<13, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, PW_LDS);
-        if (e != hipSuccess) return e;
-        n_cu_dev[dev] = n;
-    }
-    const int grid = ap_conv_pw_grid(a.M, a.Cout, n_cu_dev[dev]);
+    const int grid = ap_conv_pw_grid(a.M, a.Cout, n_cu);
     if (a.k3) hipLaunchKernelGGL((conv_pw_kernel<13, false, 2>), dim3(grid), dim3(256), PW_LDS, st, a);
     else if (a.x2) hipLaunchKernelGGL((conv_pw_kernel<13, false, 1>), dim3(grid), dim3(256), PW_LDS, st, a);
     else if (a.res) hipLaunchKernelGGL((conv_pw_kernel<13, true, 0>), dim3(grid), dim3(256), PW_LDS, st, a);

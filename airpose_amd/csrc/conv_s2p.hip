@@ -250,23 +250,16 @@ hipError_t ap_launch_conv_s2p_pack(const void* w2, void* dst, hipStream_t st) {
 }
 
 hipError_t ap_launch_conv_s2p(const ConvS2pArgs& a, hipStream_t st) {
-    static int n_cu_dev[AP_MAX_DEVICES] = {};
+    static ApDeviceOnce optin;
     if (a.N <= 0 || !a.x || !a.y || !a.wfrag || !a.scale || !a.shift || !a.zero) return hipErrorInvalidValue;
     if ((size_t)a.N * (SP_HI * SP_HI * SP_P * 2) >= 0xffff0000ull) return hipErrorInvalidValue;                   // 32-bit offsets, out-of-range marker
-    int dev = 0;
-    hipError_t e = ap_current_device(&dev);
+    int dev = 0, n_cu = 0;
+    hipError_t e = ap_device(&dev, &n_cu);
+    if (e == hipSuccess) e = ap_lds_optin(optin, dev, {{conv_s2p_kernel, SP_LDS}});
     if (e != hipSuccess) return e;
-    if (!n_cu_dev[dev]) {
-        int n = 0;
-        e = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)conv_s2p_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SP_LDS);
-        if (e != hipSuccess) return e;
-        n_cu_dev[dev] = n;
-    }
     // quarter images in groups of 32 (8 images: the four quarters of an image on one XCD); grid: one workgroup per CU, a multiple of 32
     const int nu32 = (4 * a.N + 31) / 32 * 32;
-    int grid = n_cu_dev[dev] / 32 * 32;
+    int grid = n_cu / 32 * 32;
     if (grid < 32) grid = 32;
     if (grid > nu32) grid = nu32;
     ConvS2pArgs b = a;

@@ -477,16 +477,12 @@ bool ap_conv_slab_supported(const ConvArgs& a, int kind) {
 }
 
 hipError_t ap_launch_conv_slab(ConvArgs a, hipStream_t st) {
-    static bool attr_set[AP_MAX_DEVICES] = {};
+    static ApDeviceOnce optin;
     if (!a.zero || !ap_conv_slab_supported(a, K_BF16)) return hipErrorInvalidValue;
     int dev = 0;
-    hipError_t e = ap_current_device(&dev);
+    hipError_t e = ap_device(&dev, nullptr);
+    if (e == hipSuccess) e = ap_lds_optin(optin, dev, {{conv_slab_kernel, LDS_BYTES}});
     if (e != hipSuccess) return e;
-    if (!attr_set[dev]) {
-        e = hipFuncSetAttribute((const void*)conv_slab_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
     a.mtiles = (a.M + BM - 1) / BM;
     a.ntiles = (a.Cout + BN - 1) / BN;
     {

@@ -564,15 +564,21 @@ hipError_t ap_launch_fit_adam(const FitArgs& a, int step, hipStream_t st) {
 
 hipError_t ap_launch_fit_decode(const float* z, int L, const float* w1t, const float* b1, const float* w2t, const float* b2,
                                 const float* w3t, const float* b3, float* H1, float* H2, float* O, float* aa, hipStream_t st) {
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(fit_decode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, FIT_LDS_FLOATS * 4);
-    if (attr != hipSuccess) return attr;
+    static ApDeviceOnce optin;
+    int dev = 0;
+    hipError_t e = ap_device(&dev, nullptr);
+    if (e == hipSuccess) e = ap_lds_optin(optin, dev, {{fit_decode_kernel, FIT_LDS_FLOATS * 4}});
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(fit_decode_kernel, dim3((L + DR - 1) / DR), dim3(1024), FIT_LDS_FLOATS * 4, st, z, L, w1t, b1, w2t, b2, w3t, b3, H1, H2, O, aa);
     return hipGetLastError();
 }
 hipError_t ap_launch_fit_backprop_adam(const FitArgs& a, const float* w3, const float* w2, const float* w1, const float* H1,
                                        const float* H2, int step, hipStream_t st) {
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(fit_backprop_adam_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, FIT_LDS_FLOATS * 4);
-    if (attr != hipSuccess) return attr;
+    static ApDeviceOnce optin;
+    int dev = 0;
+    hipError_t e = ap_device(&dev, nullptr);
+    if (e == hipSuccess) e = ap_lds_optin(optin, dev, {{fit_backprop_adam_kernel, FIT_LDS_FLOATS * 4}});
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(fit_backprop_adam_kernel, dim3((a.L + DR - 1) / DR), dim3(1024), FIT_LDS_FLOATS * 4, st, a, w3, w2, w1, H1, H2, adam_scales(a.lr, step));
     return hipGetLastError();
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "ap_device.h"    // what the launchers behind this interface cache per device: LDS opt-ins, the CU count
 
 struct ConvArgs {
     const void* x;        // NHWC activations [N][H][W][ldx], element type T

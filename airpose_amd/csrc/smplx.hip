@@ -824,7 +824,7 @@ bool ap_smplx_lbs_fused_supported(const SmplxModelDev& m) {
 size_t ap_smplx_dirs_frag_bytes(int V) { return (size_t)((V + 15) / 16) * T_KS_PACK * 6 * 1024; }
 
 hipError_t ap_launch_smplx_lbs_fused(const SmplxModelDev& m, const SmplxFwdArgs& a, int n_cu, int merged, hipStream_t st) {
-    static bool attr_set[AP_MAX_DEVICES] = {};
+    static ApDeviceOnce optin;
     if (!ap_smplx_lbs_fused_supported(m)) return hipErrorInvalidValue;
     constexpr int NBM = 22;
     auto lds_of = [](int nbj, int bb) { return bb * nbj * 12 * 4 + bb * T_CROW + bb * 64; };
@@ -832,17 +832,11 @@ hipError_t ap_launch_smplx_lbs_fused(const SmplxModelDev& m, const SmplxFwdArgs&
     const bool mg = merged && m.nb == NBM && m.skin_idx8b && m.skin_w4b;
     const bool wide = mg && merged == 2 && a.n >= 256;
     int dev = 0;
-    hipError_t e = ap_current_device(&dev);
+    hipError_t e = ap_device(&dev, nullptr);
+    if (e == hipSuccess)
+        e = ap_lds_optin(optin, dev, {{smplx_lbs_tail_kernel<T_MAXJ, 32>, lds_of(T_MAXJ, 32)}, {smplx_lbs_tail_kernel<NBM, 32>, lds_of(NBM, 32)},
+                                      {smplx_lbs_tail_kernel<NBM, 64>, lds_of(NBM, 64)}});
     if (e != hipSuccess) return e;
-    if (!attr_set[dev]) {
-        e = hipFuncSetAttribute((const void*)smplx_lbs_tail_kernel<T_MAXJ, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_of(T_MAXJ, 32));
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)smplx_lbs_tail_kernel<NBM, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_of(NBM, 32));
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)smplx_lbs_tail_kernel<NBM, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_of(NBM, 64));
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
     // body groups x vertex ranges ~ one workgroup per CU; 8 | n_vr keeps the blocks of one range on one XCD (block b runs on XCD
     // b % 8), so its direction rows are fetched from HBM once and served to the other body groups from that XCD's L2
     const int bb = wide ? 64 : 32, gw = T_NW / (bb / 32);

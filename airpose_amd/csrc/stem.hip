@@ -1062,16 +1062,12 @@ hipError_t ap_launch_stem_conv_mfma(const float* x0, const float* x1, int n_spli
 #ifndef AP_F16
 hipError_t ap_launch_stem_conv_mfma_split(const float* x0, const float* x1, int n_split, const void* w_hi, const void* w_lo,
                                           const float* scale, const float* shift, void* y, int n_img, hipStream_t st) {
-    static bool attr_set[AP_MAX_DEVICES] = {};
+    static ApDeviceOnce optin;
     constexpr int lds = (2 * 64 * SWLD + 2 * (SP * SPW * 4 + 32)) * 2;
     int dev = 0;
-    hipError_t e = ap_current_device(&dev);
+    hipError_t e = ap_device(&dev, nullptr);
+    if (e == hipSuccess) e = ap_lds_optin(optin, dev, {{stem_mfma_split_kernel, lds}});
     if (e != hipSuccess) return e;
-    if (!attr_set[dev]) {
-        e = hipFuncSetAttribute((const void*)stem_mfma_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
     hipLaunchKernelGGL(stem_mfma_split_kernel, dim3(SO / 16, 1, n_img), dim3(256), lds, st, x0, x1, n_split,
                        (const bf16_t*)w_hi, (const bf16_t*)w_lo, scale, shift, (bsplit_t*)y);
     return hipGetLastError();
@@ -1082,20 +1078,13 @@ hipError_t ap_launch_stem_pool(const float* x0, const float* x1, int n_split, co
                                 const float* shift, void* y_pooled, int n_img, int* range_flag, int form, hipStream_t st,
                                 unsigned long long* dbg) {
     if (form == 2) {                                         // persistent form: one workgroup per CU, contiguous ranges of strips
-        static int n_cu_dev[AP_MAX_DEVICES] = {};
-        int dev = 0;
-        hipError_t e = ap_current_device(&dev);
+        static ApDeviceOnce optin;
+        int dev = 0, n_cu = 0;
+        hipError_t e = ap_device(&dev, &n_cu);
+        if (e == hipSuccess) e = ap_lds_optin(optin, dev, {{stem_pool2_kernel, S2_LDS}});
         if (e != hipSuccess) return e;
-        if (!n_cu_dev[dev]) {
-            int n = 0;
-            e = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-            if (e != hipSuccess) return e;
-            e = hipFuncSetAttribute((const void*)stem_pool2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, S2_LDS);
-            if (e != hipSuccess) return e;
-            n_cu_dev[dev] = n > 0 ? n : 1;
-        }
         const int total = n_img * (PO / 2);
-        const int per = (total + n_cu_dev[dev] - 1) / n_cu_dev[dev];
+        const int per = (total + n_cu - 1) / n_cu;
         const int grid = (total + per - 1) / per;
         hipLaunchKernelGGL(stem_pool2_kernel, dim3(grid), dim3(S2_NT), S2_LDS, st, x0, x1, n_split, (const bf16_t*)w_packed, scale,
                            shift, (bf16_t*)y_pooled, range_flag, total, per, dbg);
@@ -1109,17 +1098,13 @@ hipError_t ap_launch_stem_pool(const float* x0, const float* x1, int n_split, co
 #ifndef AP_F16
 hipError_t ap_launch_stem_pool_split(const float* x0, const float* x1, int n_split, const void* w_hi, const void* w_lo,
                                      const float* scale, const float* shift, void* y_pooled, int n_img, hipStream_t st) {
-    static bool attr_set[AP_MAX_DEVICES] = {};
+    static ApDeviceOnce optin;
     constexpr int pb = 2 * (FROWS * FPW * 4 + 32) * 2, vb = 2 * SO * SC * 4;
     constexpr int lds = 2 * 64 * SWLD * 2 + (pb > vb ? pb : vb) + 128 * 4;
     int dev = 0;
-    hipError_t e = ap_current_device(&dev);
+    hipError_t e = ap_device(&dev, nullptr);
+    if (e == hipSuccess) e = ap_lds_optin(optin, dev, {{stem_pool_split_kernel, lds}});
     if (e != hipSuccess) return e;
-    if (!attr_set[dev]) {
-        e = hipFuncSetAttribute((const void*)stem_pool_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
     hipLaunchKernelGGL(stem_pool_split_kernel, dim3(PO / 2, n_img), dim3(448), lds, st, x0, x1, n_split, (const bf16_t*)w_hi,
                        (const bf16_t*)w_lo, scale, shift, (bsplit_t*)y_pooled);
     return hipGetLastError();
