@@ -20,6 +20,8 @@ Public mirrors of the reference interfaces:
                                           the batch dict of the trainers, TrainingLoss, EvalMetrics and MeshMetrics out
   CropAugment (augment.py)             <- the imgaug list commented out at copenet/src/copenet/dsets/aerialpeople.py:72-76: blur, colour,
                                           gamma, noise and occluders on the crops of the two batch classes (imgaug parity UNPINNED)
+  CameraRoll (roll.py)                 <- no counterpart in the reference (its unused rottrans_tfm moves the world frame, no pixel): a
+                                          roll of the camera about its optical axis, the crops and every label together
 The compute lives in libairpose_hip.so (include/airpose_hip.h); nothing here falls back to CPU.
 """
 __version__ = "0.1.0"
@@ -60,4 +62,7 @@ def __getattr__(name):
     if name == "CropAugment":                                             # likewise (augment.py)
         from .augment import CropAugment
         return CropAugment
+    if name == "CameraRoll":                                              # likewise (roll.py)
+        from .roll import CameraRoll
+        return CameraRoll
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

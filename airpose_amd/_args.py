@@ -1,6 +1,6 @@
-"""The argument rules the data-path classes share (RealSequenceBatches, SyntheticBatches, CropAugment, AirPosePlusSequence) and, for
-the device, the metric classes behind _stream_metric.py: the refusals in `owner`'s name, worded once.  A class checks what every
-argument is first and where it lives last, so that a wrong argument is named as such on any machine.
+"""The argument rules the data-path classes share (RealSequenceBatches, SyntheticBatches, CropAugment, CameraRoll,
+AirPosePlusSequence) and, for the device, the metric classes behind _stream_metric.py: the refusals in `owner`'s name, worded once.
+A class checks what every argument is first and where it lives last, so that a wrong argument is named as such on any machine.
 """
 import operator
 
@@ -46,3 +46,13 @@ def lives_on(owner, t, dev, name, anchor):
         raise RuntimeError("%s: %s lives on %s; it must be a CUDA (ROCm) tensor, there is no CPU path" % (owner, name, t.device))
     if dev is not None and t.device != dev:
         raise RuntimeError("%s: %s lives on %s, %s on %s" % (owner, name, t.device, anchor, dev))
+
+
+def pair_view(a, b):
+    """a and b as ONE (2, ...) tensor without a copy where b lies right behind a in one allocation (the batch classes' views of
+    their (2, n, ...) outputs), else None"""
+    if not (a.is_contiguous() and b.is_contiguous() and a.shape == b.shape and a.dtype == b.dtype and a.device == b.device):
+        return None
+    if a.untyped_storage().data_ptr() != b.untyped_storage().data_ptr() or b.storage_offset() != a.storage_offset() + a.numel():
+        return None
+    return a.as_strided((2,) + tuple(a.shape), (a.numel(),) + tuple(a.stride()))

@@ -99,10 +99,16 @@ SIGNATURES = {
     # crop augmentation (augment.hip); cfg is a HOST array of AUG_CFG floats
     "apg_augment_draw": (_i, [_i, _u64, _i, _vp, _vp, _i, _c.POINTER(_f)] + [_vp] * 7 + [_vp]),
     "apg_augment_crops": (_i, [_i, _u64, _i, _vp, _vp, _i] + [_vp] * 10 + [_vp]),
+    # camera roll (roll.hip): 11 inputs and 10 outputs of apg_roll_labels, all device pointers (a label may be NULL)
+    "apg_roll_draw": (_i, [_i, _u64, _i, _vp, _vp, _i, _f, _f, _vp, _vp]),
+    "apg_roll_labels": (_i, [_i] * 9 + [_vp, _i] + [_vp] * 11 + [_vp] * 10 + [_vp]),
+    "apg_roll_crops": (_i, [_i] * 6 + [_vp, _vp, _vp, _i] + [_vp] * 4 + [_vp]),
 }
 # include/airpose_grad.h: APG_AUG_*; the last four are the bits of status
 AUG_TILE, AUG_THREADS, AUG_MAX_RADIUS, AUG_MAX_RECTS, AUG_CFG = 32, 256, 6, 4, 18
 AUG_BLUR_CLAMPED, AUG_NONFINITE, AUG_RECT_CLIPPED, AUG_BAD_BOX = 1, 2, 4, 8
+ROLL_THREADS = 256       # include/airpose_grad.h: APG_ROLL_THREADS
+ROLL_CENTRE_OUT, ROLL_OFF_CANVAS = 1, 2                      # include/airpose_grad.h: APG_ROLL_*, the bits of status
 SYNTH_ORIGINS = {"region": 0, "frame": 1}                    # include/airpose_grad.h: APG_SYNTH_ORIGIN_*
 SYNTH_CLAMPED, SYNTH_WIDENED, SYNTH_OUTSIDE = 1, 2, 4        # include/airpose_grad.h: APG_SYNTH_*, the bits of status
 SYNTH_THREADS = 128      # include/airpose_grad.h: APG_SYNTH_THREADS

@@ -205,15 +205,7 @@ class CropAugment:
         return out
 
     # ---------------------------------------------------------------------------------------- the batch dict
-    @staticmethod
-    def _pair_view(a, b):
-        """a and b as ONE (2, ...) tensor without a copy where b lies right behind a in one allocation (the batch classes' views of
-        their (2, n, ...) outputs), else None"""
-        if not (a.is_contiguous() and b.is_contiguous() and a.shape == b.shape and a.dtype == b.dtype and a.device == b.device):
-            return None
-        if a.untyped_storage().data_ptr() != b.untyped_storage().data_ptr() or b.storage_offset() != a.storage_offset() + a.numel():
-            return None
-        return a.as_strided((2,) + tuple(a.shape), (a.numel(),) + tuple(a.stride()))
+    _pair_view = staticmethod(A.pair_view)                  # (shared with CameraRoll: _args.py)
 
     def __call__(self, batch, index, epoch=0):
         if not isinstance(batch, dict):

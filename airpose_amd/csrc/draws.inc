@@ -1,4 +1,4 @@
-// The data path's random draws, once, for synth_batch.hip and augment.hip (libairpose_grad.so).  Included inside each file's unnamed
+// The data path's random draws, once, for synth_batch.hip, augment.hip and roll.hip (libairpose_grad.so).  Included inside each file's unnamed
 // namespace.
 //
 // Philox4x32-10 of Random123: ten rounds, the key bumped by the Weyl constants between them.  Key = (seed's low word, seed's high
@@ -7,6 +7,7 @@
 //     block 0, camera 0 / 1      apg_synth_batch's jitter: words 0 .. 3 the ymin, ymax, xmin, xmax side offsets
 //     block 0, camera 2          apg_synth_batch's flip: bit 31 of word 0
 //     block 1 .. 14, camera 0 / 1   apg_augment_draw's parameter set (block k, word w as the header lists them)
+//     block 15, camera 0 / 1        apg_roll_draw's gate (word 0) and angle (word 1)
 //     block 0x80000000 | pixel   apg_augment_crops' noise of pixel row * 224 + column
 // A new stream takes a block (or a camera value) none of these uses.
 struct U4 { uint32_t w[4]; };

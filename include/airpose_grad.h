@@ -909,6 +909,90 @@ int apg_augment_crops(int n, uint64_t seed, int epoch, const int* index, const i
                       const int* crops, const float* blur_taps, const float* color, const float* gamma, const float* noise_sigma, const int* rects,
                       const float* rect_rgb, float* out, int* status, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Camera roll (roll.hip): the geometric augmentation of the training chain, a ROLL OF THE CAMERA ABOUT ITS OPTICAL AXIS by an angle
+ * theta, applied to the crops and to every label of a SyntheticBatches / RealSequenceBatches dict without leaving the device.  It is a
+ * rigid motion of the camera, so no label becomes approximate and the two views stay consistent through extr.  The reference has
+ * no image-plane augmentation: its rottrans_tfm (not called) moves the WORLD frame -- extr and the *_wrt_origin labels -- and no pixel.
+ * Flips (a mirrored body is no rigid motion) and zoom (it changes the depth to predict at a fixed focal length) are not built.
+ * THIS TEXT is the contract.  Additive under ABI 2: a binding tells a library that has them by looking up apg_roll_crops.  Stateless,
+ * no workspace; three launches on `stream` (one per entry), no host copy, no synchronisation; all pointers are device pointers to
+ * contiguous arrays, 4-byte aligned (the canvases: any alignment).  Compiled with -ffp-contract=off: outside apg_roll_draw's cos and sin every operation below is ONE
+ * fp32 rounding of + - * / in the written order (parentheses are the order), no fused multiply-add, so that a numpy float32
+ * restatement gives the same bits.
+ *
+ * Per sample i < n and suffix s the camera is (cam[i] & 1) ^ s with cam (n) int32 on the device (SyntheticBatches' cam0), or
+ * cam_all ^ s when cam is NULL (cam_all = 0 or 1: RealSequenceBatches' cam).  rot (2, n, 2) = (c, sn) = (cos theta, sin theta), drawn
+ * or planted; it is not normalised.  From intr (2, n, 3, 3), indexed by suffix: fx = K[0][0], fy = K[1][1], cx = K[0][2], cy =
+ * K[1][2], tx = sn * (fx / fy), ty = sn * (fy / fx), and
+ *     A(theta)  (x, y) = ((c * x) - (tx * y), (ty * x) + (c * y))        (R2(theta) when fx = fy)
+ *     A(-theta) (x, y) = ((c * x) + (tx * y), (c * y) - (ty * x))
+ *     Rz(theta) (x, y) = ((c * x) - (sn * y), (sn * x) + (c * y)).
+ * Pixel-index coordinates are the projection's coordinates, as the reference treats them.
+ *
+ * apg_roll_labels, per (s, i):
+ *   The decision.  A row whose (c, sn) is exactly (1, 0) is un-rolled and is not tested; its tx and ty are exactly 0 whatever intr
+ *     holds (a zero focal length cannot make its OFF_CANVAS corners NaN).  Otherwise (u, v) = A(theta) (bb_x * cx,
+ *     bb_y * cy), bb'_x = u / cx, bb'_y = v / cy: the crop box's centre turned about the principal point.  The refusal rule: unless
+ *     |bb'_x| <= 1 and |bb'_y| <= 1 (a NaN fails it too) the crop centre would leave a frame centred on the principal point, the
+ *     (sample, view) is left un-rolled, (c, sn) := (1, 0) exactly, and APG_ROLL_CENTRE_OUT is set.
+ *   rot_used (2, n, 2) = the (c, sn) in force; bb_out (2, n, 3) = (bb'_x, bb'_y, bb_2); status (2, n) int32.
+ *   An un-rolled row COPIES bb and every label bit for bit.  A rolled row:
+ *     verts (2, n, V, 3), joints (2, n, J, 3), trans (2, n, 3): (x', y') = Rz(theta) (x, y), z copied;
+ *     orient (2, n, 3, 3) = Rz R: per column, rows 0 and 1 mixed by Rz(theta), row 2 copied;
+ *     extr (2, n, 4, 4): per column (the translation column included), rows 0 and 1 mixed by Rz(theta), rows 2 and 3 copied;
+ *     j2d (2, n, P, pstride): (d_x, d_y) = (x - cx, y - cy), p' = (cx + a_x, cy + a_y) with a = A(theta) d;
+ *     j2d_crop (2, n, P, pstride): A(theta) applied to the vector itself (it is measured from the crop centre);
+ *     with pstride = 3 the third column (the real dict's confidence) is copied bit for bit.
+ *   A label pointer that is NULL means the dict has no such key: nothing is read or written for it and its count is not looked at.
+ *   crops (2, n, 4) int32 = y0, y1, x0, x1 on the camera's canvas, NOT changed: it keeps describing the un-rolled box, whose height
+ *     and width are what apg_augment_crops reads.  scale, pad, crop_info and intr are not touched either.
+ *   APG_ROLL_OFF_CANVAS, the "black wedge" signal: with hw = w * 0.5, hh = h * 0.5 (w = x1 - x0, h = y1 - y0) and the centre m =
+ *     (x0 + hw, y0 + hh), a corner is q = m + A(-theta) (+-hw, +-hh); the bit is set unless all four have 0 <= q_x <= Wc and
+ *     0 <= q_y <= Hc, the size of the camera's canvas.  Status words are written with plain vector stores by one thread per (s, i).
+ *   One thread per item (a vertex, a joint, a point, a column): every label byte is read once and written once.  An output must
+ *   not overlap its input.
+ *
+ * apg_roll_crops: im (2, n, 3, 224, 224) from the cameras' canvases, frames0 (n, Hc0, Wc0, 3) and frames1 (n, Hc1, Wc1, 3) uint8,
+ * both indexed by CAMERA (SyntheticBatches' one (2, n, Hc, Wc, 3) tensor is frames0 and frames0 + n Hc Wc 3 with equal sizes;
+ * RealSequenceBatches' frames0 / frames1 as they are); bgr as ap_preprocess_crops; crops as above; rot_used as apg_roll_labels wrote
+ * it; intr as above (it gives tx, ty).  One thread per output pixel, as preprocess_kernel.
+ *   A row whose (c, sn) is exactly (1, 0) runs preprocess_px.inc itself: bit-identical to apg_synth_crops / ap_preprocess_crops.
+ *   A rolled row takes the un-rolled box's h, w, scale, dw, dh, the pads and, for output pixel (ox, oy), dx = ox - left, dy = oy -
+ *     top exactly as preprocess_px.inc computes them.  Padding pixels (outside 0 <= dx < dw, 0 <= dy < dh) are written as
+ *     preprocess_px writes them: (0 - mean) / std.  A content pixel takes the source position BEFORE the floor, fx_ =
+ *     (float)((dx + 0.5) * (1.0 / ((double)dw / (double)w)) - 0.5) and fy_ likewise (fp64, each operation rounded once, then one
+ *     rounding to fp32), and samples the canvas at
+ *         q = (x0 + hw, y0 + hh) + A(-theta) (fx_ - hw, fy_ - hh).
+ *     The sample is bilinear with the zero continuation: a tap outside the canvas contributes 0, so the image is continuous in q.
+ *     Unless -1 < q_x < Wc and -1 < q_y < Hc no tap lies on the canvas and the value is 0.  Else i = floor(q), a = q - i, a tap is
+ *     byte / 255 of channel (2 - ch when bgr), top = (t00 * (1 - a_x)) + (t01 * a_x), bot likewise, v = (top * (1 - a_y)) +
+ *     (bot * a_y).  Then (v - mean) / std, mean 0.485, 0.456, 0.406, std 0.229, 0.224, 0.225.
+ *   A row whose box breaks 0 <= y0 < y1 <= Hc, 0 <= x0 < x1 <= Wc is neither read through nor written, as in apg_synth_crops.
+ *
+ * apg_roll_draw writes rot (2, n, 2) and nothing else: one thread per (s, i).  Philox4x32-10, key = (seed's low word, seed's high
+ * word), counter = (index[i], epoch, camera, 15): block 15, camera 0 / 1, which no other stream uses (apg_synth_batch block 0,
+ * apg_augment_draw blocks 1 .. 14, the noise blocks >= 2^31).  u = (word >> 8) * 2^-24.  Word 0 is the gate, on when u < p; word 1
+ * the angle, ((2 * u) - 1) * max_rad in fp32; cos and sin of that fp32 angle are taken in fp64 and rounded once.  Gate off gives
+ * exactly (1, 0); so do p = 0 and max_rad = 0.  A draw depends on (seed, index, epoch, camera) alone.
+ *
+ * APG_EINVAL before any GPU call, the message naming the argument: n outside 1 .. 65535, a NULL or misaligned pointer (cam may be
+ * NULL; a label may be NULL, its output is needed when it is not), cam_all outside 0 .. 1, p outside 0 .. 1, max_rad outside 0 .. pi,
+ * a canvas side outside 1 .. 2^20, V outside 1 .. 2^24, J or P outside 1 .. 2^16, pstride other than 2 or 3, bgr outside 0 .. 1, an
+ * output overlapping its input, im overlapping a canvas. */
+#define APG_ROLL_THREADS 256
+#define APG_ROLL_CENTRE_OUT 1
+#define APG_ROLL_OFF_CANVAS 2
+int apg_roll_draw(int n, uint64_t seed, int epoch, const int* index, const int* cam, int cam_all, float p, float max_rad, float* rot,
+                  void* stream);
+int apg_roll_labels(int n, int V, int J, int P, int pstride, int Hc0, int Wc0, int Hc1, int Wc1, const int* cam, int cam_all,
+                    const float* rot, const float* intr, const float* bb, const int* crops, const float* verts, const float* joints,
+                    const float* orient, const float* trans, const float* extr, const float* j2d, const float* j2d_crop,
+                    float* rot_used, float* bb_out, int* status, float* verts_out, float* joints_out, float* orient_out,
+                    float* trans_out, float* extr_out, float* j2d_out, float* j2d_crop_out, void* stream);
+int apg_roll_crops(int n, int Hc0, int Wc0, int Hc1, int Wc1, int bgr, const unsigned char* frames0, const unsigned char* frames1,
+                   const int* cam, int cam_all, const int* crops, const float* intr, const float* rot_used, float* im, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,11 @@ per kernel, the v_pk_{fma,mul,add}_f32 instructions are counted, how many of the
 reads.  Packed fp32 math with op_sel on LDS operands is the signature of the wrong-answer hazard csrc/Makefile describes at
 FLAGS_smplx; tests/test_packed_math_scan.py holds the committed list to the Makefile's flags.  Needs hipcc, no GPU.
 
-    python tools/packed_math_scan.py                   # the table
+The committed list holds the sources of the Makefile's SRCS and GRAD_SRCS.  A source linked through another *_SRCS variable
+(linked_apart(): ROLL_SRCS) is scanned and printed with the rest and left out of the list: the test that adds such a source scans it
+live instead (tests/test_roll_abi.py), and that test also holds that every .hip file of csrc is in one set or the other.
+
+    python tools/packed_math_scan.py                   # the table, every source that is linked
     python tools/packed_math_scan.py --write           # ... and tests/packed_math_scan.json, the list the test reads
     python tools/packed_math_scan.py --drop-flag smplx # the table of ONE source without its FLAGS_ entry (what a flag removes)
 """
@@ -35,6 +39,16 @@ def makefile():
     h16 = [s[:-4] for s in var("H16SRCS")]
     rest = [s[:-4] for s in var("SRCS") + var("GRAD_SRCS") if s.endswith(".hip")]
     return os.environ.get("HIPCC", var("HIPCC")[0]), common, flags, h16, h16 + rest
+
+
+def linked_apart():
+    """-> the kernel sources (names without .hip) that the Makefile links through a *SRCS variable other than SRCS, GRAD_SRCS and
+    H16SRCS (APISRCS is the host layer: no kernel, never scanned): scanned like the others, not part of the committed list"""
+    text = open(os.path.join(CSRC, "Makefile")).read()
+    listed = set(makefile()[4])
+    found = [s[:-4] for m in re.finditer(r"^(\w*SRCS)\s*\??=\s*(.*)$", text, re.M) if m.group(1) != "APISRCS"
+             for s in m.group(2).split() if s.endswith(".hip")]
+    return sorted(set(found) - listed)
 
 
 def demangle(names):
@@ -107,7 +121,8 @@ def main():
     ap.add_argument("--drop-flag", metavar="SOURCE", help="scan only SOURCE, without its FLAGS_ entry")
     ap.add_argument("-j", type=int, default=min(8, os.cpu_count() or 1))
     a = ap.parse_args()
-    table = scan_sources([a.drop_flag] if a.drop_flag else None, bool(a.drop_flag), a.j)
+    listed, apart = makefile()[4], linked_apart()
+    table = scan_sources([a.drop_flag] if a.drop_flag else listed + apart, bool(a.drop_flag), a.j)
     print("%-34s %-72s %7s %7s %8s" % ("source", "kernel", "packed", "op_sel", "ds_reads"))
     for r in table:
         if r["packed"]:
@@ -117,9 +132,9 @@ def main():
     if a.write and not a.drop_flag:
         with open(OUT, "w") as f:
             json.dump(dict(command="python tools/packed_math_scan.py --write", columns=list(COLUMNS),
-                           kernels=[[r[c] for c in COLUMNS] for r in table]), f, indent=0)
+                           kernels=[[r[c] for c in COLUMNS] for r in table if r["source"][:-4] in listed]), f, indent=0)
             f.write("\n")
-        print("wrote", os.path.relpath(OUT, REPO))
+        print("wrote", os.path.relpath(OUT, REPO), "(without the sources linked apart: %s)" % " ".join(apart) if apart else "")
     return 0
 
 
