@@ -8,6 +8,8 @@ Public mirrors of the reference interfaces:
   TrainingLoss (loss.py)               <- get_loss of copenet_twoview / copenet_singleview / hmr / muhmr
   RealDataLoss (loss_real.py)          <- get_loss of the copenet_real fine-tune trainers (2-D keypoints + VPoser prior)
   FusedAdam (optim.py)                 <- torch.optim.Adam(..., amsgrad=True) of the trainers' configure_optimizers
+  clip_grad_norm_ (optim.py)           <- torch.nn.utils.clip_grad_norm_, Lightning's --gradient_clip_val; FusedAdam(max_grad_norm=,
+                                          skip_nonfinite=) is the fused form, with --terminate_on_nan's guard on the device
   EvalMetrics (eval_metrics.py)        <- test_epoch_end of the four trainers: MPJPE, MPE, angle error
   Renderer (renderer.py)               <- utils/renderer.py Renderer: visualize_tb of the trainers' summaries(), without pyrender
   MeshMetrics (mesh_metrics.py)        <- no counterpart in the reference: MPJPE / PVE, absolute, root- and Procrustes-aligned
@@ -38,6 +40,9 @@ def __getattr__(name):
     if name == "FusedAdam":                                               # likewise (optim.py)
         from .optim import FusedAdam
         return FusedAdam
+    if name == "clip_grad_norm_":                                         # likewise (optim.py)
+        from .optim import clip_grad_norm_
+        return clip_grad_norm_
     if name == "EvalMetrics":                                             # likewise (eval_metrics.py)
         from .eval_metrics import EvalMetrics
         return EvalMetrics

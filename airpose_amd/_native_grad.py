@@ -72,6 +72,11 @@ SIGNATURES = {
     "apg_real_loss_fwd_bwd": (_i, [_i] * 6 + [_f, _c.POINTER(_f), _vp, _vpp, _vpp, _vp, _vpp, _vp, _i64, _vp]),
     # the optimizer step (optim.hip)
     "apg_adam_step": (_i, [_i] + [_vpp] * 5 + [_c.POINTER(_i64)] * 2 + [_c.c_double] * 5 + [_vp]),
+    # gradient clipping and the non-finite guard (guard/grad_guard.hip)
+    "apg_grad_norm_workspace_bytes": (_i64, [_i, _c.POINTER(_i64)]),
+    "apg_grad_norm": (_i, [_i, _vpp, _c.POINTER(_i64), _c.c_double, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "apg_grad_scale": (_i, [_i, _vpp, _c.POINTER(_i64), _vp, _vp]),
+    "apg_adam_step_guarded": (_i, [_i] + [_vpp] * 5 + [_c.POINTER(_i64)] * 2 + [_c.c_double] * 5 + [_vp, _vp]),
     # the evaluation metrics (eval_metrics.hip)
     "apg_eval_workspace_bytes": (_i64, [_i, _i]),
     "apg_eval_acc_doubles": (_i64, []),
@@ -107,7 +112,8 @@ SIGNATURES = {
 # include/airpose_grad.h: APG_AUG_*; the last four are the bits of status
 AUG_TILE, AUG_THREADS, AUG_MAX_RADIUS, AUG_MAX_RECTS, AUG_CFG = 32, 256, 6, 4, 18
 AUG_BLUR_CLAMPED, AUG_NONFINITE, AUG_RECT_CLIPPED, AUG_BAD_BOX = 1, 2, 4, 8
-ROLL_THREADS = 256       # include/airpose_grad.h: APG_ROLL_THREADS
+GUARD_BYTES, GRAD_NORM_BATCH = 16, 192    # include/airpose_grad.h: APG_GUARD_BYTES, APG_GRAD_NORM_BATCH
+ROLL_THREADS = 256      # include/airpose_grad.h: APG_ROLL_THREADS
 ROLL_CENTRE_OUT, ROLL_OFF_CANVAS = 1, 2                      # include/airpose_grad.h: APG_ROLL_*, the bits of status
 SYNTH_ORIGINS = {"region": 0, "frame": 1}                    # include/airpose_grad.h: APG_SYNTH_ORIGIN_*
 SYNTH_CLAMPED, SYNTH_WIDENED, SYNTH_OUTSIDE = 1, 2, 4        # include/airpose_grad.h: APG_SYNTH_*, the bits of status

@@ -1,5 +1,5 @@
 // Internal helpers shared by the sources of libairpose_grad.so (head_mlp.hip, head_grad.hip, head_local_grad.hip, geom_grad.hip,
-// trunk_grad.hip, trunk_grad_bf16.hip, loss_grad.hip, loss_real_grad.hip, optim.hip, eval_metrics.hip, render.hip, eval_align.hip, xview_metrics.hip, seq_fit.hip, seq_batch.hip, synth_batch.hip, augment.hip, roll.hip).  Texts that only some of them share are includes of their own: trunk_elem.inc
+// trunk_grad.hip, trunk_grad_bf16.hip, loss_grad.hip, loss_real_grad.hip, optim.hip, eval_metrics.hip, render.hip, eval_align.hip, xview_metrics.hip, seq_fit.hip, seq_batch.hip, synth_batch.hip, augment.hip, roll.hip, guard/grad_guard.hip).  Texts that only some of them share are includes of their own: trunk_elem.inc
 // and trunk_walk.inc (the two trunks), loss_common.inc (the losses and geom_grad.hip), metric_common.inc (eval_metrics.hip, eval_align.hip, xview_metrics.hip),
 // draws.inc (synth_batch.hip, augment.hip, roll.hip), preprocess_px.inc (synth_batch.hip, roll.hip, and stem.hip of libairpose_hip.so).
 #pragma once

@@ -378,6 +378,67 @@ int apg_adam_step(int ntensors, const void* const* p, const void* const* g, cons
                   double weight_decay, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Gradient clipping and the non-finite guard (guard/grad_guard.hip): torch.nn.utils.clip_grad_norm_'s global L2 norm and clip coefficient,
+ * and a flag for a NaN or Inf gradient, computed on the device in ONE read of the gradients and consumed by the Adam kernel in the
+ * same step -- no host copy, no synchronisation, no second pass over the gradients.  Additive under ABI 2: a binding tells a library
+ * that has these entries by looking up apg_grad_norm.
+ *
+ * The guard record, APG_GUARD_BYTES = 16 bytes of device memory, 4-byte aligned, written in full by every apg_grad_norm call:
+ *   offset 0   float   coef   (float) min(1, max_norm / (sqrt(S) + 1e-6)): formed in fp64 and rounded once; torch's clip_coef_clamped
+ *   offset 4   float   norm   (float) sqrt(S)
+ *   offset 8   int32   skip   1 when S is non-finite and skip_nonfinite was set, else 0; when it is 1, coef is written as 1
+ *   offset 12  int32          reserved, written as 0
+ * S = sum of g^2 over every element of every tensor, accumulated in fp64 from the first add.  The square of a float is exact in fp64,
+ * so S cannot overflow for any fp32 gradients (|g| = 1e19 everywhere gives a finite norm), tiny gradients do not flush (|g| = 1e-30
+ * gives a non-zero norm), and S is non-finite exactly when some element is NaN or +-Inf: that is what "non-finite" means here.
+ * With a non-finite S and skip_nonfinite = 0, coef is written as NaN, so a step that consumes it turns everything it touches into NaN
+ * and the failure cannot be overlooked.  (torch's own coefficient is NaN for a NaN norm and 0 for an Inf norm, where 0 * Inf then makes
+ * NaN of the offending elements only.)  For a list without any element coef is 1 and norm is 0, whatever max_norm is.
+ *
+ * apg_grad_norm
+ *   g, numel: HOST arrays of ntensors fp32 device pointers and element counts (numel[i] = 0: accepted, the pointer may be NULL).
+ *   max_norm >= 0; +inf: guard only (coef = 1 for every finite S).  skip_nonfinite: 0 or not 0.
+ *   workspace: at least apg_grad_norm_workspace_bytes(ntensors, numel) bytes (8 per 4096-element chunk and per tensor; negative
+ *     for a bad list), 8-byte aligned; the chunk partials and the per-tensor sums.  It carries nothing from call to call and needs no
+ *     initialisation.
+ *   guard: the record above.  per_tensor: NULL, or ntensors device floats, per_tensor[i] = (float) sqrt(S_i), S_i the tensor's own sum
+ *     (0 for a tensor without elements).
+ *   counters: NULL, or two device int64 (8-byte aligned) the caller zeroes once: [0] += 1 per call ("seen"), [1] += 1 per call that
+ *     set skip ("skipped"); added by one thread of the last launch, stream-ordered, no atomics.
+ * Partition and order (apg_adam_step's partition): 4096-element chunks of one tensor, one workgroup of 256 threads each; the tensors
+ * travel in the kernels' argument blocks, APG_GRAD_NORM_BATCH = 192 per launch (an empty tensor takes a slot).  Thread t of a chunk
+ * owns the float quads at (i * 256 + t) * 4, i = 0 .. 3, moved as one 16-byte access where the tensor's pointer is 16-byte aligned and
+ * as four 4-byte accesses otherwise; the last numel mod 4 elements of a tensor are taken one by one by the thread whose quad they
+ * start.  An element has the same owner and the same arithmetic on every path.  A thread adds its squares in element order; the 64
+ * lanes of a wave are added by the tree l += l + 32, 16, 8, 4, 2, 1; the four waves as ((w0 + w1) + w2) + w3; a second launch adds a
+ * tensor's chunks in chunk order (S_i) and a last one the S_i in tensor order (S).  No floating-point atomics, no arrival counter: the
+ * order depends on the sizes alone, so norm, coef and per_tensor are bit-identical from run to run and for every alignment.
+ * 2 ceil(ntensors / 192) + 1 launches (1 for an empty list: the record is always written), no host synchronisation.
+ *
+ * apg_grad_scale: g[i][k] = g[i][k] * coef in place for the same table, one correctly rounded product per element, coef read from the
+ * guard record on the device.  Where coef == 1 (nothing to clip, or a skipped step) every workgroup returns without a store: the
+ * gradients keep their bits, -0 and NaN payloads included.  ceil(ntensors / 192) launches.
+ *
+ * apg_adam_step_guarded: apg_adam_step with the record.  Every workgroup loads coef and skip.  With skip = 1 it returns before its first
+ * store: p, m, v, vmax keep their bits.  Otherwise g2 = coef * g (one correctly rounded product, never fused into what follows) and
+ * apg_adam_step's sequence runs on g2; g itself is read only.  With coef = 1 and skip = 0 the result is apg_adam_step's, bit for bit.
+ * step[i] is the host's count and advances whether or not the device skips: see FusedAdam (airpose_amd/optim.py).
+ *
+ * APG_EINVAL, before any launch and with nothing written, the message naming the argument: ntensors < 0, a NULL g table or numel
+ * array, numel[i] < 0 or too large, a NULL pointer of a tensor with elements, a pointer that is not 4-byte aligned, max_norm < 0 or
+ * NaN, a NULL or misaligned guard, a workspace that is NULL, misaligned or smaller than apg_grad_norm_workspace_bytes says; for
+ * apg_adam_step_guarded also every refusal of apg_adam_step. */
+#define APG_GUARD_BYTES 16
+#define APG_GRAD_NORM_BATCH 192
+int64_t apg_grad_norm_workspace_bytes(int ntensors, const int64_t* numel);
+int apg_grad_norm(int ntensors, const void* const* g, const int64_t* numel, double max_norm, int skip_nonfinite, void* workspace,
+                  int64_t workspace_bytes, void* guard, float* per_tensor, int64_t* counters, void* stream);
+int apg_grad_scale(int ntensors, const void* const* g, const int64_t* numel, const void* guard, void* stream);
+int apg_adam_step_guarded(int ntensors, const void* const* p, const void* const* g, const void* const* m, const void* const* v,
+                          const void* const* vmax, const int64_t* numel, const int64_t* step, double lr, double beta1, double beta2,
+                          double eps, double weight_decay, const void* guard, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The real-data fine-tuning loss (loss_real_grad.hip): get_loss of the reference's copenet_real trainers (copenet_twoview.py:100-160,
  * copenet_twoview_sep.py:93-150, hmr.py:82-118, hmr_camswap_difffl.py:92-128, spin.py:86-122) and the gradient of the total with
  * respect to every prediction, in one pass.  2-D keypoints with detector confidences, no 3-D ground truth, a VPoser prior on the body

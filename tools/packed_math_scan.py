@@ -6,8 +6,9 @@ reads.  Packed fp32 math with op_sel on LDS operands is the signature of the wro
 FLAGS_smplx; tests/test_packed_math_scan.py holds the committed list to the Makefile's flags.  Needs hipcc, no GPU.
 
 The committed list holds the sources of the Makefile's SRCS and GRAD_SRCS.  A source linked through another *_SRCS variable
-(linked_apart(): ROLL_SRCS) is scanned and printed with the rest and left out of the list: the test that adds such a source scans it
-live instead (tests/test_roll_abi.py), and that test also holds that every .hip file of csrc is in one set or the other.
+(linked_apart(): ROLL_SRCS) or from a directory below csrc (linked_below(): GUARD_UNITS) is scanned and printed with the rest and left
+out of the list: the test that adds such a source scans it live instead (tests/test_roll_abi.py, tests/test_gradnorm_abi.py), and
+those tests also hold that every .hip file of csrc and below is in one of the sets.
 
     python tools/packed_math_scan.py                   # the table, every source that is linked
     python tools/packed_math_scan.py --write           # ... and tests/packed_math_scan.json, the list the test reads
@@ -49,6 +50,14 @@ def linked_apart():
     found = [s[:-4] for m in re.finditer(r"^(\w*SRCS)\s*\??=\s*(.*)$", text, re.M) if m.group(1) != "APISRCS"
              for s in m.group(2).split() if s.endswith(".hip")]
     return sorted(set(found) - listed)
+
+
+def linked_below():
+    """-> the kernel sources (paths below csrc without .hip) the Makefile links from a directory of their own, through a variable
+    that is not named *SRCS (GUARD_UNITS: guard/grad_guard): scanned like the others, not part of the committed list either; the
+    test that adds such a source scans it live (tests/test_gradnorm_abi.py)"""
+    text = open(os.path.join(CSRC, "Makefile")).read()
+    return sorted(s[:-4] for m in re.finditer(r"^(\w+_UNITS)\s*\??=\s*(.*)$", text, re.M) for s in m.group(2).split() if s.endswith(".hip"))
 
 
 def demangle(names):
@@ -121,7 +130,7 @@ def main():
     ap.add_argument("--drop-flag", metavar="SOURCE", help="scan only SOURCE, without its FLAGS_ entry")
     ap.add_argument("-j", type=int, default=min(8, os.cpu_count() or 1))
     a = ap.parse_args()
-    listed, apart = makefile()[4], linked_apart()
+    listed, apart = makefile()[4], linked_apart() + linked_below()
     table = scan_sources([a.drop_flag] if a.drop_flag else listed + apart, bool(a.drop_flag), a.j)
     print("%-34s %-72s %7s %7s %8s" % ("source", "kernel", "packed", "op_sel", "ds_reads"))
     for r in table:
